@@ -7,7 +7,13 @@ database: scan kernel(s) -> candidate records -> (N>1: RCCL gather to rank 0) ->
 cluster/verify on rank 0 -> final hits resident on the host of rank 0.
 
     python bench.py --gpus 1 --steps 2 --warmup 1
+    python bench.py --gpus 1 --steps 2 --warmup 1 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times --steps steps and prints the line (its headline figures are those of the timed
+steps); --dump-outputs DIR also writes the final hits of the last timed step there (dump_outputs).  --full adds
+everything else the benchmark measures and checks: the pm_scan leg, the planted-site check, the roofline figures
+from the committed counters and the streaming-read probe, and the CPU baseline (the reference on a sample).
 
 The database is sharded by stream position across ranks: rank r holds and scans
 stream range [r*S, (r+1)*S) plus a 256-byte halo on either side; every rank holds all patterns.
@@ -346,6 +352,22 @@ def issue_roofline(args, shard, kms):
     return out
 
 
+DUMP_ROWS = 1_900_000       # --dump-outputs: at most this many hits (4 float64 columns: 61 MB)
+
+
+def dump_outputs(d, fin):
+    """--dump-outputs: what a caller of the timed step receives, its final hits in (end, pid, k) order, as float64 columns
+    hit_end.npy (stream index of the hit's last base), hit_pid.npy (pattern id), hit_k.npy (distance); hit_rows.npy holds
+    the row of each within all hits and hit_count.npy their number.  More than DUMP_ROWS hits: a fixed, seeded sample of
+    the rows (in order), so that two builds compare row for row."""
+    os.makedirs(d, exist_ok=True)
+    n = fin.size
+    rows = np.arange(n) if n <= DUMP_ROWS else np.sort(np.random.default_rng(20260101).choice(n, DUMP_ROWS, replace=False))
+    for name, col in (("hit_end", fin["end"]), ("hit_pid", fin["pid"]), ("hit_k", fin["k"]), ("hit_rows", rows)):
+        np.save(os.path.join(d, name + ".npy"), col[rows].astype(np.float64) if name != "hit_rows" else col.astype(np.float64))
+    np.save(os.path.join(d, "hit_count.npy"), np.array([n], dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -360,7 +382,7 @@ def main():
     ap.add_argument("--kernel", choices=["auto", "bitpar", "seed"], default="auto")
     ap.add_argument("--odd", type=int, default=0, help="replace this many primers by ones with an N in the middle (they go to the bit-parallel residue engine)")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="strong")
-    ap.add_argument("--cpu-sample", type=int, default=0, help="bases for the CPU baseline (0 = auto, -1 = skip)")
+    ap.add_argument("--cpu-sample", type=int, default=0, help="--full: bases for the CPU baseline (0 = auto, -1 = skip)")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-cpu-all", action="store_true", help="skip the one-reference-process-per-core figure")
     ap.add_argument("--cpu-procs", type=int, default=0, help="processes for the all-cores figure (0 = every host core)")
@@ -372,10 +394,12 @@ def main():
     ap.add_argument("--landing", type=int, default=1 << 24, help="records the host landing zones hold (hit-dense streams need more)")
     ap.add_argument("--pair-stats", action="store_true", help="count blocks, rounds and key hits in the pair kernel (PM_SEED_DEBUG bit 5; a measurement build of the same kernel)")
     ap.add_argument("--plant-run", type=int, default=0, help="A x this many across the middle of the stream, and the primer A x length with it")
-    ap.add_argument("--scan-passes", type=int, default=3, help="timed whole-stream passes through pm_scan itself after the timed region (0 = skip; single GPU only)")
+    ap.add_argument("--scan-passes", type=int, default=3, help="--full: timed whole-stream passes through pm_scan itself after the timed region (0 = skip; single GPU only)")
     ap.add_argument("--scan-chunk", type=int, default=1 << 30, help="stream bytes per pm_scan range (the compiled plugin default: 1 GiB)")
     ap.add_argument("--scan-cap", type=int, default=1 << 20, help="records the caller takes per pm_scan call")
     ap.add_argument("--capacity", type=int, default=0, help="initial record capacity (0 = default; small values exercise the grow-and-rescan path)")
+    ap.add_argument("--full", action="store_true", help="also the pm_scan leg, the planted-site check, the roofline figures and the CPU baseline")
+    ap.add_argument("--dump-outputs", default="", help="rank 0 writes the final hits of the last timed step to this directory as float64 .npy files")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -719,7 +743,7 @@ def main():
     desc = pm.describe()                                            # (the timed steps' launch geometry, not the pm_scan leg's ranges)
     scan_stats = pm.scan_stats()
     pm_scan_ms, pm_scan_hits, scan_hits_arr = None, None, None
-    if not use_dist and args.scan_passes > 0:
+    if args.full and not use_dist and args.scan_passes > 0:
         torch.cuda.synchronize()
         caller = np.zeros(args.landing, dtype=sat_amd.HIT_DTYPE)
         times = []
@@ -741,13 +765,15 @@ def main():
         pm.reset()
 
     found_planted = None
-    if rank == 0 and last_final[0] is not None:
+    if rank == 0 and last_final[0] is not None and (args.full or args.dump_hits or args.dump_outputs):
         torch.cuda.synchronize()
         lf = last_final[0]
         fin = (lf.numpy().view(sat_amd.HIT_DTYPE) if isinstance(lf, torch.Tensor) else lf).copy()
         fin = fin[np.lexsort((fin["k"], fin["pid"], fin["end"]))]
         if args.dump_hits:
             np.save(args.dump_hits, fin)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, fin)
         if scan_hits_arr is not None:
             # the same hits, already in (end, pid, k) order, through pm_scan as through the timed step
             same = scan_hits_arr.size == fin.size and bool((scan_hits_arr["end"] == fin["end"]).all() and (scan_hits_arr["pid"] == fin["pid"]).all()
@@ -758,7 +784,7 @@ def main():
         # id i+1) with at most its planted distance, at the site's end -- filter_bitvec reports one hit
         # per chain of candidates and exact_halves drops hits within 2k of the last kept one, so the
         # reported end may sit up to 2k+1 from the planted one
-        if planted and not args.odd and not args.no_check:
+        if args.full and planted and not args.odd and not args.no_check:
             tol = 2 * args.k + 1
             key = fin["pid"].astype(np.int64) << 40 | fin["end"]
             order = np.argsort(key)
@@ -795,7 +821,7 @@ def main():
         for kx in ("blocks", "rounds", "key_hits"):
             scan_stats.pop(kx, None)
     if rank == 0:
-        traffic, traffic_source, traffic_entry = measured_traffic(args, shard)
+        traffic, traffic_source, traffic_entry = measured_traffic(args, shard) if args.full else (None, None, None)
         ms_per_step = dt / args.steps * 1e3
         value = n_bases_total / (dt / args.steps) / 1e9
         kms = float(np.mean(kernel_ms[args.warmup:])) if len(kernel_ms) > args.warmup else float("nan")
@@ -840,19 +866,19 @@ def main():
             res["exchange_ms"] = float(np.mean(exch_host_ms[args.warmup:])) if len(exch_host_ms) > args.warmup else None
             res["exchange_device_ms"] = exch_dev_ms
             res["kernel_ms_per_rank"] = kms_all
-        if pm.selected()[1] == sat_amd.KERNEL_SEED:
+        if args.full and pm.selected()[1] == sat_amd.KERNEL_SEED:
             ir = issue_roofline(args, shard, kms)
             if ir:
                 res["issue_roofline"] = ir
         # the streaming-read rate this box sustains (same 16-byte loads, nothing else to do)
         try:
             mb = min(stream.numel(), 1 << 31) // 16 * 16
-            if mb >= (1 << 29):                                      # well past the 256 MiB Infinity Cache
+            if args.full and mb >= (1 << 29):                        # well past the 256 MiB Infinity Cache
                 res["roofline"]["measured_read_peak"] = sat_amd.measure_stream_read(stream.data_ptr(), mb, reps=5)
                 res["roofline"]["frac_of_measured"] = achieved / res["roofline"]["measured_read_peak"]
         except Exception as e:                                       # measurement only: never fails the bench
             log("measure_stream_read: %s" % e)
-        if pm.selected()[1] == sat_amd.KERNEL_BITPAR:
+        if args.full and pm.selected()[1] == sat_amd.KERNEL_BITPAR:
             # the bit-parallel family is integer-ALU bound.  One 32-bit state word per lane,
             # tile and row is updated per stream byte with ~c vector ops (4 exact; 6 per row with edits,
             # 4 with mismatches only); peak = 256 CUs x 128 lanes x ~2.4 GHz 32-bit integer ops.
@@ -866,7 +892,7 @@ def main():
                 res["alu_roofline"] = {"achieved": ops / (kms * 1e-3) / 1e12, "peak": peak, "unit": "T u32-op/s",
                                        "frac": ops / (kms * 1e-3) / 1e12 / peak,
                                        "model": "%d state words x %.0f ops per stream byte" % (words, c)}
-        if not args.no_cpu and args.cpu_sample >= 0 and world == 1:
+        if args.full and not args.no_cpu and args.cpu_sample >= 0 and world == 1:
             cb = cpu_baseline(args, stream, primers, log)
             if cb:
                 res["cpu_baseline"] = cb

@@ -11,7 +11,7 @@ for style in uniform skew vocab tandem; do
     for stats in "" "--pair-stats"; do
       [ -n "$stats" ] && [ "$name" != "K2" ] && continue
       out=gpurun_out/hard_$tag/bench_hard_${style}_${name}${stats:+_stats}
-      timeout -k 10 600 python bench.py --steps 3 --warmup 1 --no-cpu --scan-passes 0 --db-bases $db --primers $primers --landing $((1<<27)) \
+      timeout -k 10 600 python bench.py --full --steps 3 --warmup 1 --no-cpu --scan-passes 0 --db-bases $db --primers $primers --landing $((1<<27)) \
         --stream-style $style "$@" $stats > $out.json 2> $out.err
       echo "$style $name $stats rc=$? $(python -c "
 import json,sys

@@ -8,7 +8,7 @@ tag=${1:-r02}
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 out=gpurun_out/lines_$tag
 mkdir -p $out
-python bench.py --steps 3 --warmup 1 --k 2 --indels 1 > $out/bench_k2_edits.json 2> $out/bench_k2_edits.err && echo "k2 edits line done"
+python bench.py --full --steps 3 --warmup 1 --k 2 --indels 1 > $out/bench_k2_edits.json 2> $out/bench_k2_edits.err && echo "k2 edits line done"
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt_k2e -- python bench.py --steps 2 --warmup 1 --k 2 --indels 1 --no-cpu > $out/kt_k2e.log 2>&1 && echo "trace done"
 rm -f gpurun_out/edits_stages.txt
 bash scripts/edits_stages.sh > /dev/null 2>&1

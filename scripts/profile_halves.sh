@@ -7,7 +7,7 @@ tag=${1:-r02}
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 out=gpurun_out/lines_$tag
 mkdir -p $out
-python bench.py --steps 5 --warmup 1 --k 1 --indels 1 > $out/bench_k1_edits.json 2> $out/bench_k1_edits.err && echo "k1 edits line done"
+python bench.py --full --steps 5 --warmup 1 --k 1 --indels 1 > $out/bench_k1_edits.json 2> $out/bench_k1_edits.err && echo "k1 edits line done"
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt_k1e -- python bench.py --steps 3 --warmup 1 --k 1 --indels 1 --no-cpu > $out/kt_k1e.log 2>&1 && echo "trace done"
 f=gpurun_out/${tag}_stages_k1_edits.txt
 rm -f $f

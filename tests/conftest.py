@@ -20,11 +20,8 @@ def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
 
 
-REF_HARNESS = os.path.join(ROOT, "oracle", "_ref", "ref_harness")
-
-
 @pytest.fixture(scope="session")
 def ref_harness():
-    if not os.path.exists(REF_HARNESS):
-        pytest.skip("oracle/_ref/ref_harness not built (needs /root/reference)")
-    return REF_HARNESS
+    """the reference engines' harness, by its name in oracle/_ref: run where it is built, replayed from the recording
+    (tests/refrec.py) where it is not"""
+    return "ref_harness"

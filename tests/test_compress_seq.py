@@ -1,8 +1,8 @@
 """pm_compress_seq (host C++) against the files the reference's compress_seq wrote for the same
 FASTA input (tests/golden/cli_*.json, made by tests/golden/make_cli_golden.py), byte for byte;
-and, where the reference binary is present (oracle/_ref), against a fresh run of it on FASTA
-files with awkward layouts (CR LF, blank lines, lower case, no final newline, control characters),
-incl. the bit-packed form (-z true: <db>.sqz + <db>.tbz, compress_seq.cc:741-905)."""
+and against the reference binary (oracle/_ref where it is built, its recorded runs where it is not:
+tests/refrec.py) on FASTA files with awkward layouts (CR LF, blank lines, lower case, no final
+newline, control characters), incl. the bit-packed form (-z true: <db>.sqz + <db>.tbz, compress_seq.cc:741-905)."""
 import base64
 import json
 import os
@@ -11,9 +11,10 @@ import tempfile
 
 import pytest
 
+import refrec
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CS = os.path.join(ROOT, "sequence-alignment-tools_amd", "host", "pm_compress_seq")
-REF_CS = os.path.join(ROOT, "oracle", "_ref", "compress_seq")
 EXTS = ("seq", "sqn", "tbl", "sqz", "tbz", "hdr", "idb")
 
 
@@ -55,21 +56,25 @@ AWKWARD = [
 ]
 
 
-@pytest.mark.skipif(not os.path.exists(REF_CS), reason="reference compress_seq not built (oracle/_ref)")
+def ref_compress_seq(fasta, args):
+    """the reference's compress_seq on `fasta` (bytes): (exit status, {extension: bytes} of the files it wrote)"""
+    status, _, files = refrec.run("compress_seq", ["-i", "{d}/db.fa"] + args, {"db.fa": fasta}, collect=["db.fa." + e for e in EXTS])
+    return status, {n[len("db.fa."):]: b for n, b in files.items()}
+
+
 @pytest.mark.parametrize("idx", range(len(AWKWARD)))
 @pytest.mark.parametrize("args", [[], ["-n", "true"], ["-n", "true", "-u", "false"], ["-S", "false"], ["-e", "false", "-S", "false"],
                                   ["-E", "36", "-n", "true"], ["-n", "true", "-D", "false"], ["-n", "true", "-C", "false"],
                                   ["-z", "true"], ["-z", "true", "-n", "true", "-C", "false"], ["-z", "true", "-D", "false", "-u", "false"],
                                   ["-z", "true", "-E", "36"]])
 def test_against_reference_binary(idx, args):
-    res = []
-    for exe in (REF_CS, CS):
-        with tempfile.TemporaryDirectory() as d:
-            fa = os.path.join(d, "db.fa")
-            with open(fa, "wb") as f:
-                f.write(AWKWARD[idx])
-            r = subprocess.run([exe, "-i", fa] + args, capture_output=True)
-            res.append((r.returncode, files_of(fa)))
+    res = [ref_compress_seq(AWKWARD[idx], args)]
+    with tempfile.TemporaryDirectory() as d:
+        fa = os.path.join(d, "db.fa")
+        with open(fa, "wb") as f:
+            f.write(AWKWARD[idx])
+        r = subprocess.run([CS, "-i", fa] + args, capture_output=True)
+        res.append((r.returncode, files_of(fa)))
     if res[0][0] != 0:
         pytest.skip("reference refuses this input")
     assert res[1][0] == 0
@@ -78,7 +83,6 @@ def test_against_reference_binary(idx, args):
         assert res[0][1][k] == res[1][1][k], (idx, args, k)
 
 
-@pytest.mark.skipif(not os.path.exists(REF_CS), reason="reference compress_seq not built (oracle/_ref)")
 @pytest.mark.parametrize("nsym", [2, 3, 5, 9, 17, 40])
 def test_compressed_form_at_every_code_width(nsym):
     """.sqz packs ceil(log2(table size)) bits per character, most significant bit first, and fills the last
@@ -89,15 +93,17 @@ def test_compressed_form_at_every_code_width(nsym):
     alphabet = "ACGTNRYKMSWBDHVXUQEFILPZJO0123456789abcd"[:nsym - 1]          # + the end-of-sequence character
     for length in (1, 7, 8, 23, 24, 25, 119, 120, 121, 1000):
         fasta = ">a\n" + "".join(rnd.choice(alphabet) for _ in range(length)) + "\n>b\n" + "".join(rnd.choice(alphabet) for _ in range(5)) + "\n"
-        res = []
-        for exe in (REF_CS, CS):
-            with tempfile.TemporaryDirectory() as d:
-                fa = os.path.join(d, "db.fa")
-                with open(fa, "w") as f:
-                    f.write(fasta)
-                r = subprocess.run([exe, "-i", fa, "-z", "true", "-u", "false", "-D", "false"], capture_output=True)
-                assert r.returncode == 0, (exe, r.stderr)
-                res.append(files_of(fa))
+        args = ["-z", "true", "-u", "false", "-D", "false"]
+        status, ref = ref_compress_seq(fasta.encode(), args)
+        assert status == 0, ("reference", nsym, length)
+        res = [ref]
+        with tempfile.TemporaryDirectory() as d:
+            fa = os.path.join(d, "db.fa")
+            with open(fa, "w") as f:
+                f.write(fasta)
+            r = subprocess.run([CS, "-i", fa] + args, capture_output=True)
+            assert r.returncode == 0, (CS, r.stderr)
+            res.append(files_of(fa))
         assert sorted(res[0]) == sorted(res[1]) and "sqz" in res[0]
         for k in res[0]:
             assert res[0][k] == res[1][k], (nsym, length, k)

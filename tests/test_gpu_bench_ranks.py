@@ -32,7 +32,7 @@ def free_port():
 
 def run_bench(ranks, k, indels, dump, extra=()):
     common = ["bench.py", "--gpus", str(ranks), "--steps", "2", "--warmup", "1", "--db-bases", str(DB), "--primers", str(PRIMERS),
-              "--k", str(k), "--indels", str(indels), "--no-cpu", "--dump-hits", dump, *extra]     # default scaling: strong
+              "--k", str(k), "--indels", str(indels), "--no-cpu", "--full", "--dump-hits", dump, *extra]     # default scaling: strong
     env = dict(os.environ, PM_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     if ranks == 1:
         cmd = [sys.executable] + common

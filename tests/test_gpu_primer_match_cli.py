@@ -107,14 +107,12 @@ def test_compressed_and_raw_databases(fixture):
         assert sorted(run_case(g, d, "k1_oneline_fwd_only", "normalized", ["-D", "1"]).splitlines()) == sorted(g["cases"]["k1_oneline_fwd_only"]["raw"].splitlines())
 
 
-REF_PM = os.path.join(ROOT, "oracle", "_ref", "primer_match")
-
-
-@pytest.mark.skipif(not os.path.exists(REF_PM), reason="reference primer_match not built (oracle/_ref)")
 def test_raw_fasta_layouts_against_the_reference_binary():
     """The FASTA file itself as database (-D 1) in layouts the reference reads without a warning: CR LF line ends,
     lower-case bases (matched only with -u), no newline behind the last line, a header with tabs, a one-line entry;
-    same lines as the real primer_match prints."""
+    same lines as the real primer_match prints (oracle/_ref where it is built, its recorded runs where it is not:
+    tests/refrec.py)."""
+    import refrec
     import numpy as np
     rng = np.random.default_rng(5)
     seqs = ["".join(rng.choice(list("ACGT"), size=n).tolist()) for n in (300, 240, 60, 180)]
@@ -123,20 +121,28 @@ def test_raw_fasta_layouts_against_the_reference_binary():
         "crlf": "".join(">e%d some text\r\n%s" % (i, "".join(s[j:j + 60] + "\r\n" for j in range(0, len(s), 60))) for i, s in enumerate(seqs)),
         "lower_no_final_newline": "".join(">e%d\ttabbed\n%s" % (i, "".join(s[j:j + 60].lower() + "\n" for j in range(0, len(s), 60))) for i, s in enumerate(seqs))[:-1],
     }
+    optsets = (["-k", "1", "-r"], ["-k", "1", "-r", "-u"], ["-K", "2", "-r", "-u", "-A", "%i %r %s %e %d [%h|%H]\\n"])
+    pbytes = ("\n".join(primers) + "\n").encode()
+    want = {}
+    for name, text in layouts.items():
+        for i, opts in enumerate(optsets):
+            status, out, _ = refrec.run("primer_match", ["-i", "{d}/%s.fa" % name, "-P", "{d}/p.txt", "-D", "1"] + opts,
+                                        {name + ".fa": text.encode(), "p.txt": pbytes}, timeout=120)
+            assert status == 0, (name, opts)
+            want[name, i] = out
+        assert want[name, len(optsets) - 1].strip(), name
     with tempfile.TemporaryDirectory() as d:
         pf = os.path.join(d, "p.txt")
-        with open(pf, "w") as f:
-            f.write("\n".join(primers) + "\n")
+        with open(pf, "wb") as f:
+            f.write(pbytes)
         for name, text in layouts.items():
             fa = os.path.join(d, name + ".fa")
             with open(fa, "wb") as f:
                 f.write(text.encode())
-            for opts in (["-k", "1", "-r"], ["-k", "1", "-r", "-u"], ["-K", "2", "-r", "-u", "-A", "%i %r %s %e %d [%h|%H]\\n"]):
-                want = subprocess.run([REF_PM, "-i", fa, "-P", pf, "-D", "1"] + opts, capture_output=True, timeout=120)
+            for i, opts in enumerate(optsets):
                 got = subprocess.run([PM, "-i", fa, "-P", pf, "-D", "1"] + opts, capture_output=True, timeout=120)
-                assert want.returncode == 0 and got.returncode == 0, (name, opts, got.stderr[-300:])
-                assert sorted(got.stdout.splitlines()) == sorted(want.stdout.splitlines()), (name, opts)
-            assert want.stdout.strip(), name
+                assert got.returncode == 0, (name, opts, got.stderr[-300:])
+                assert sorted(got.stdout.splitlines()) == sorted(want[name, i].splitlines()), (name, opts)
 
 
 def test_refusals():

@@ -27,7 +27,7 @@ def test_bench_nccl_backend_world_one_equals_plain_run(tmp_path, opts):
     wrapped straight out of HBM, dist.gather, side-stream landing) with world == 1; the final hits must
     equal the plain single-process run's."""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
-    common = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--db-bases", "50000000", "--primers", "20000", "--no-cpu"] + opts
+    common = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--db-bases", "50000000", "--primers", "20000", "--no-cpu", "--full"] + opts
     a, b = str(tmp_path / "plain.npy"), str(tmp_path / "dist.npy")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + common + ["--dump-hits", a], capture_output=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr.decode("latin1")[-1500:]

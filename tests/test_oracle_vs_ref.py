@@ -1,8 +1,9 @@
-"""CPU, build container only: fuzz the oracle against the real reference engines (oracle/_ref).
-Skipped where oracle/_ref/ref_harness does not exist."""
+"""CPU: fuzz the oracle against the real reference engines (oracle/_ref/ref_harness where it is built, its recorded
+runs where it is not: tests/refrec.py)."""
 import numpy as np
 import pytest
 
+import refrec
 import refrun
 import synth
 from oracle import pmoracle as O
@@ -36,7 +37,6 @@ def test_fuzz_against_reference(ref_harness, seed):
 @pytest.mark.parametrize("seed", range(2))
 def test_fuzz_constraints_against_reference(ref_harness, seed):
     """exact_start_bases / exact_end_bases (-s/-e): exact_bases and the constrained verifies."""
-    import os, subprocess, tempfile
     rng = np.random.default_rng(500 + seed)
     ents = synth.make_entries(rng, 3, int(rng.integers(200, 1200)), n_runs=2, repeats=(seed % 2 == 0))
     L = int(rng.integers(16, 24))
@@ -45,27 +45,23 @@ def test_fuzz_constraints_against_reference(ref_harness, seed):
     codes = synth.normalize(synth.stream(ents), table)
     allp = pats + [synth.revcomp(p) for p in pats]
     text = O.Text(codes, table)
-    with tempfile.TemporaryDirectory() as d:
-        open(os.path.join(d, "db.sqn"), "wb").write(codes.tobytes())
-        open(os.path.join(d, "db.tbl"), "wb").write(table)
-        open(os.path.join(d, "pat.txt"), "w").write("\n".join(pats) + "\n")
-        for esb, eeb in [(8, 0), (0, 7), (6, 9), (3, 0)]:
-            for sel, k, ind in [(0, 1, 1), (0, 2, 1), (0, 2, 0), (8, 1, 1), (10, 2, 0), (5, 2, 1), (12, 1, 1)]:
-                cmd = [ref_harness, "-N", str(sel), "-n", "-r", "-i", os.path.join(d, "db"), "-P", os.path.join(d, "pat.txt"),
-                       "-s", str(esb), "-e", str(eeb), "-k" if ind else "-K", str(k)]
-                out = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-                assert out.returncode == 0, out.stderr[-300:]
-                ref = sorted(tuple(int(x) for x in l.split()) for l in out.stdout.splitlines() if not l.startswith("#"))
-                E, F = [esb] * len(allp), [eeb] * len(allp)
-                eng = sel if sel else O.pick_engine(text, allp, k, bool(ind), E, F)
-                got = O.sorted_tuples(O.find_all(text, allp, engine=eng, k=k, indels=bool(ind), esb=E, eeb=F))
-                assert got == ref, (seed, esb, eeb, sel, k, ind)
+    inputs = {"db.sqn": codes.tobytes(), "db.tbl": table, "pat.txt": ("\n".join(pats) + "\n").encode()}
+    for esb, eeb in [(8, 0), (0, 7), (6, 9), (3, 0)]:
+        for sel, k, ind in [(0, 1, 1), (0, 2, 1), (0, 2, 0), (8, 1, 1), (10, 2, 0), (5, 2, 1), (12, 1, 1)]:
+            cmd = ["-N", str(sel), "-n", "-r", "-i", "{d}/db", "-P", "{d}/pat.txt",
+                   "-s", str(esb), "-e", str(eeb), "-k" if ind else "-K", str(k)]
+            status, out, _ = refrec.run(ref_harness, cmd, inputs, timeout=300)
+            assert status == 0, cmd
+            ref = refrec.hits(out)
+            E, F = [esb] * len(allp), [eeb] * len(allp)
+            eng = sel if sel else O.pick_engine(text, allp, k, bool(ind), E, F)
+            got = O.sorted_tuples(O.find_all(text, allp, engine=eng, k=k, indels=bool(ind), esb=E, eeb=F))
+            assert got == ref, (seed, esb, eeb, sel, k, ind)
 
 
 @pytest.mark.parametrize("seed", range(2))
 def test_fuzz_wildcards_against_reference(ref_harness, seed):
     """-w / -W: shift_and with IUPAC pattern classes (shift_and.cc:108-117)."""
-    import os, subprocess, tempfile
     rng = np.random.default_rng(700 + seed)
     ents = synth.make_entries(rng, 3, int(rng.integers(300, 2000)), n_runs=4, repeats=(seed % 2 == 0))
     L = int(rng.integers(8, 14))
@@ -78,17 +74,13 @@ def test_fuzz_wildcards_against_reference(ref_harness, seed):
     table = synth.table_for(ents)
     codes = synth.normalize(synth.stream(ents), table)
     text = O.Text(codes, table)
-    with tempfile.TemporaryDirectory() as d:
-        open(os.path.join(d, "db.sqn"), "wb").write(codes.tobytes())
-        open(os.path.join(d, "db.tbl"), "wb").write(table)
-        open(os.path.join(d, "pat.txt"), "w").write("\n".join(pats) + "\n")
-        for flag, tn in (("-w", False), ("-W", True)):
-            out = subprocess.run([ref_harness, "-N", "4", flag, "-n", "-i", os.path.join(d, "db"), "-P", os.path.join(d, "pat.txt")],
-                                 capture_output=True, text=True, timeout=300)
-            assert out.returncode == 0, out.stderr[-300:]
-            ref = sorted(tuple(int(x) for x in l.split()) for l in out.stdout.splitlines() if not l.startswith("#"))
-            got = O.sorted_tuples(O.find_all(text, pats, engine=4, k=0, wildcards=True, text_n=tn))
-            assert got == ref, (seed, flag)
+    inputs = {"db.sqn": codes.tobytes(), "db.tbl": table, "pat.txt": ("\n".join(pats) + "\n").encode()}
+    for flag, tn in (("-w", False), ("-W", True)):
+        status, out, _ = refrec.run(ref_harness, ["-N", "4", flag, "-n", "-i", "{d}/db", "-P", "{d}/pat.txt"], inputs, timeout=300)
+        assert status == 0, flag
+        ref = refrec.hits(out)
+        got = O.sorted_tuples(O.find_all(text, pats, engine=4, k=0, wildcards=True, text_n=tn))
+        assert got == ref, (seed, flag)
 
 
 @pytest.mark.parametrize("seed", range(3))
@@ -97,7 +89,6 @@ def test_fuzz_wildcards_inexact_against_reference(ref_harness, seed):
     461-475, 514-590) and global_align (primer_alignment.cc:151-154, 253-280); engines as
     pick_pattern_index chooses them (exact_halves over shift_and for k = 1, filter_bitvec for k = 2)
     and forced."""
-    import os, subprocess, tempfile
     rng = np.random.default_rng(900 + seed)
     ents = synth.make_entries(rng, 3, int(rng.integers(400, 2500)), n_runs=4, repeats=(seed % 2 == 0))
     L = int(rng.integers(14, 22))
@@ -111,22 +102,18 @@ def test_fuzz_wildcards_inexact_against_reference(ref_harness, seed):
     codes = synth.normalize(synth.stream(ents), table)
     text = O.Text(codes, table)
     total = 0
-    with tempfile.TemporaryDirectory() as d:
-        open(os.path.join(d, "db.sqn"), "wb").write(codes.tobytes())
-        open(os.path.join(d, "db.tbl"), "wb").write(table)
-        open(os.path.join(d, "pat.txt"), "w").write("\n".join(pats) + "\n")
-        for flag, tn in (("-w", False), ("-W", True)):
-            for k in (1, 2):
-                for indels in (True, False):
-                    for sel in (0, 5, 14, 100):
-                        cmd = [ref_harness, "-N", str(sel), flag, "-k" if indels else "-K", str(k), "-n", "-i", os.path.join(d, "db"),
-                               "-P", os.path.join(d, "pat.txt")]
-                        out = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-                        assert out.returncode == 0, (cmd, out.stderr[-300:])
-                        ref = sorted(tuple(int(x) for x in l.split()) for l in out.stdout.splitlines() if not l.startswith("#"))
-                        got = O.sorted_tuples(O.find_all(text, pats, engine=sel, k=k, indels=indels, wildcards=True, text_n=tn))
-                        assert got == ref, (seed, flag, k, indels, sel, len(got), len(ref))
-                        total += len(ref)
+    inputs = {"db.sqn": codes.tobytes(), "db.tbl": table, "pat.txt": ("\n".join(pats) + "\n").encode()}
+    for flag, tn in (("-w", False), ("-W", True)):
+        for k in (1, 2):
+            for indels in (True, False):
+                for sel in (0, 5, 14, 100):
+                    cmd = ["-N", str(sel), flag, "-k" if indels else "-K", str(k), "-n", "-i", "{d}/db", "-P", "{d}/pat.txt"]
+                    status, out, _ = refrec.run(ref_harness, cmd, inputs, timeout=300)
+                    assert status == 0, cmd
+                    ref = refrec.hits(out)
+                    got = O.sorted_tuples(O.find_all(text, pats, engine=sel, k=k, indels=indels, wildcards=True, text_n=tn))
+                    assert got == ref, (seed, flag, k, indels, sel, len(got), len(ref))
+                    total += len(ref)
     assert total > 0
 
 
@@ -137,7 +124,6 @@ def test_stream_edges_against_reference(ref_harness, norm):
     test_edit_plan_matches_that_end_with_the_stream): the reference's extensions read the mapped file's zero padding
     past the last character (mapFile.h:49-57) and report hits that end beyond the stream; a pattern whose first
     characters are deleted matches at the very start.  The oracle must say what the REAL reference says there."""
-    import os, subprocess, tempfile
     table = b"ACGT\n"
     rng = np.random.default_rng(90)
     rnd = lambda n: "".join("ACGT"[c] for c in rng.integers(0, 4, n))
@@ -169,20 +155,15 @@ def test_stream_edges_against_reference(ref_harness, norm):
     assert beyond > (100 if norm else 20)                      # (on a raw stream every character past the end is a substitution)
     # exact_bases (-s / -e), prefix and suffix blocks
     use = [p for p in pats if len(p) >= 20]
-    with tempfile.TemporaryDirectory() as d:
-        if norm:
-            open(os.path.join(d, "db.sqn"), "wb").write(data.tobytes())
-            open(os.path.join(d, "db.tbl"), "wb").write(table)
-        else:
-            open(os.path.join(d, "db"), "wb").write(raw)
-        open(os.path.join(d, "pat.txt"), "w").write("\n".join(use) + "\n")
-        for esb, eeb in [(8, 0), (6, 3), (0, 7)]:
-            for k, ind in [(1, 0), (2, 0), (1, 1), (2, 1)]:
-                cmd = [ref_harness, "-N", "8", "-i", os.path.join(d, "db"), "-P", os.path.join(d, "pat.txt"), "-s", str(esb), "-e", str(eeb),
-                       "-k" if ind else "-K", str(k)] + (["-n"] if norm else [])
-                out = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-                assert out.returncode == 0, out.stderr[-300:]
-                ref = sorted(tuple(int(x) for x in l.split()) for l in out.stdout.splitlines() if not l.startswith("#"))
-                E, F = [esb] * len(use), [eeb] * len(use)
-                got = O.sorted_tuples(O.find_all(text, use, engine=8, k=k, indels=bool(ind), esb=E, eeb=F))
-                assert got == ref, (norm, esb, eeb, k, ind, sorted(set(ref) - set(got))[:4], sorted(set(got) - set(ref))[:4])
+    inputs = {"db.sqn": data.tobytes(), "db.tbl": table} if norm else {"db": raw}
+    inputs["pat.txt"] = ("\n".join(use) + "\n").encode()
+    for esb, eeb in [(8, 0), (6, 3), (0, 7)]:
+        for k, ind in [(1, 0), (2, 0), (1, 1), (2, 1)]:
+            cmd = ["-N", "8", "-i", "{d}/db", "-P", "{d}/pat.txt", "-s", str(esb), "-e", str(eeb),
+                   "-k" if ind else "-K", str(k)] + (["-n"] if norm else [])
+            status, out, _ = refrec.run(ref_harness, cmd, inputs, timeout=300)
+            assert status == 0, cmd
+            ref = refrec.hits(out)
+            E, F = [esb] * len(use), [eeb] * len(use)
+            got = O.sorted_tuples(O.find_all(text, use, engine=8, k=k, indels=bool(ind), esb=E, eeb=F))
+            assert got == ref, (norm, esb, eeb, k, ind, sorted(set(ref) - set(got))[:4], sorted(set(got) - set(ref))[:4])

@@ -2,12 +2,15 @@
 <db>.seq, <db>.sqn + .tbl, <db>.sqz + .tbz (written here by pm_compress_seq and, where present, by the reference's
 compress_seq) and the FASTA file itself.  The streams must be the same characters position by position (the
 compressed form may add end-of-sequence characters at the end, char_io.t:18-214), the entries must start at the same
-positions with the same headers."""
+positions with the same headers.  The reference's files come from its recorded runs where oracle/_ref is not built
+(tests/refrec.py)."""
 import os
 import subprocess
 import tempfile
 
 import pytest
+
+import refrec
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST = os.path.join(ROOT, "sequence-alignment-tools_amd", "host")
@@ -38,7 +41,10 @@ def dump(db, fmt, uc=0):
     return out
 
 
-@pytest.mark.parametrize("writer", [CS] + ([REF_CS] if os.path.exists(REF_CS) else []))
+EXTS = ("seq", "sqn", "tbl", "sqz", "tbz", "hdr", "idb")
+
+
+@pytest.mark.parametrize("writer", [CS, REF_CS])
 def test_all_forms_give_one_stream(writer):
     assert os.path.exists(DUMP) and os.path.exists(CS), "run __graft_entry__.build()"
     with tempfile.TemporaryDirectory() as d:
@@ -48,7 +54,14 @@ def test_all_forms_give_one_stream(writer):
             fa = os.path.join(d, name, "db.fa")
             with open(fa, "w") as f:
                 f.write(FASTA)
-            if args is not None:
+            if args is not None and writer == REF_CS:
+                status, _, files = refrec.run("compress_seq", ["-i", "{d}/db.fa"] + args, {"db.fa": FASTA.encode()},
+                                              collect=["db.fa." + e for e in EXTS])
+                assert status == 0 and files, name
+                for n, b in files.items():
+                    with open(os.path.join(d, name, n), "wb") as f:
+                        f.write(b)
+            elif args is not None:
                 r = subprocess.run([writer, "-i", fa] + args, capture_output=True)
                 assert r.returncode == 0, r.stderr
             forms[name] = dump(fa, fmt)
