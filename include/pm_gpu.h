@@ -105,6 +105,29 @@ int pm_init(pm_handle *h, const uint8_t *text, int64_t n, const uint8_t *table, 
 int pm_init_device(pm_handle *h, const void *d_text, int64_t n, const uint8_t *table, int32_t table_len,
                    void *hip_stream);
 
+/* pm_init for a stream larger than HBM: `text` (borrowed, as for pm_init) stays in host memory
+ * and the GPU holds only a ring of two windows of it, each window_bytes (rounded up to a multiple of 64 and to the
+ * option set's minimum, four times the halo of its device stages) plus guard margins.  pm_scan / pm_scan_view give
+ * exactly the hits of pm_init for any sequence of ranges: a range longer than a window is scanned in pieces, the next
+ * window is uploaded while the current one is scanned, and a piece whose carried clusters reach further back than a
+ * window (a long tandem-repeat chain) gets a larger window of its own.  exact_halves' one-call device rule needs the
+ * whole stream in one piece, so on a stream longer than a window its hits take the host route pieces already use.
+ * The lower-level calls -- pm_scan_candidates[_async], pm_finalize_device[_owned], pm_final_hits_device -- work on a
+ * range whose text, with the halo and what carried clusters need, fits one window (it is uploaded first; the records
+ * given to pm_finalize_device must be those of the last scan); a larger range is PM_E_INVALID, and so is
+ * pm_measure_pair_edit_floor.  pm_align_hits[_text] read `text`. */
+int pm_init_windowed(pm_handle *h, const uint8_t *text, int64_t n, const uint8_t *table, int32_t table_len,
+                     int64_t window_bytes);
+
+/* Introspection for tests and measurement: out[0] the window size in use (0: the whole stream is resident), out[1] the
+ * HBM bytes held now for stream text plus its 2-bit words, out[2] the peak of out[1] since init, out[3] stream bytes
+ * uploaded since init, out[4] window loads since init (pm_init: 1, pm_init_device: 0).  n <= 5 values are written. */
+int pm_stream_residency(const pm_handle *h, int64_t *out, int n);
+
+/* Free and total HBM of `device` (hipMemGetInfo), for a caller that picks between pm_init and pm_init_windowed: the
+ * resident form holds 1.25 bytes per stream base (text + 2-bit words) before any record list exists. */
+int pm_device_memory(int device, int64_t *free_bytes, int64_t *total_bytes);
+
 /* PatternMatch::find_patterns (pattern_match.h:131) over the stream range [begin,end):
  * appends to out[0..cap) every final hit with begin < hit.end <= end whose cluster/dedup fate is
  * decided (filter_bitvec.cc:118-121 defers the rest to the next call), sorted by (end,pid).
@@ -253,7 +276,8 @@ int pm_scan_stats(pm_handle *h, uint64_t *out, int n);
 
 /* Measurement helper (no reference counterpart; DESIGN.md 4.6 "pair geometry for edits"): on a -K 2 handle of the pair plan,
  * time the 14-test pair geometry as the first stage of an edit-distance plan over the whole stream.  mode 1: substitution
- * compare (lower bound), mode 2: five-shift edit test on two patterns per slot.  No hits are produced. */
+ * compare (lower bound), mode 2: five-shift edit test on two patterns per slot.  No hits are produced.  Not on a windowed
+ * handle (pm_init_windowed): PM_E_INVALID. */
 int pm_measure_pair_edit_floor(pm_handle *h, int mode, float *ms, uint64_t *suspects);
 
 /* Duration of the one-off re-encoding of the stream to 2 bits per base that pm_init[_device] runs

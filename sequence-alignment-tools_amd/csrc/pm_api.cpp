@@ -37,6 +37,22 @@ void Alphabet::set_table(const uint8_t *table, int len) {      // char_io.t:222-
 }
 }  // namespace pm
 
+// windowed stream (pm_init_windowed): host -> HBM in chunks through pinned staging buffers, one HIP stream per thread
+constexpr int WIN_UP_THREADS = 4;
+constexpr int64_t WIN_UP_CHUNK = (int64_t)4 << 20;
+
+// One slot of the window ring: stream text [lo, hi) at bytes + guard (and its 2-bit words at words + guard / 16), with
+// guard margins of unused memory on both sides: a stage that reads beyond its computed reach gets wrong characters, never
+// memory outside an allocation.
+struct WinSlot {
+  uint8_t *bytes = nullptr;
+  uint32_t *words = nullptr;
+  int64_t cap = 0, lo = 0, hi = 0;
+  bool loaded = false, used_rec = false;
+  hipEvent_t ready = nullptr;         // upload + packing done (recorded on the upload stream)
+  hipEvent_t used = nullptr;          // the last kernel that reads the slot (recorded on the handle's stream when it is unbound)
+};
+
 struct pm_handle {
   pm_config cfg{};
   Knobs knobs;                        // the environment's test / measurement knobs as pm_create found them
@@ -162,6 +178,20 @@ struct pm_handle {
   size_t nrest = 0;
   bool halves_fresh = true;           // no host-side exact_halves state (lasthit, carried seeds) since init / pm_reset
 
+  // windowed stream (pm_init_windowed): d_text / d_packed point at the bound slot, rebased so that absolute stream
+  // positions index it; the scan and finalize kernels need no change
+  int64_t win = 0;                    // window bytes (0: the whole stream is resident)
+  int64_t win_back = 0, win_fwd = 0;  // halo of the device stages (stream_halo)
+  int64_t win_guard = 0;              // guard margin of every slot, each side
+  WinSlot slot[2];
+  int bound = -1;
+  hipStream_t up_stream = nullptr;    // packing of uploaded windows
+  uint8_t *stage[WIN_UP_THREADS][2] = {};
+  hipStream_t stage_st[WIN_UP_THREADS] = {};
+  hipEvent_t stage_ev[WIN_UP_THREADS][2] = {};
+  hipEvent_t stage_done[WIN_UP_THREADS] = {};
+  int64_t win_held = 0, win_peak = 0, win_uploaded = 0, win_loads = 0;
+
   std::string err;
 };
 
@@ -253,9 +283,11 @@ extern "C" int pm_add_pattern(pm_handle *h, const char *pat, size_t len, uint64_
 static void drain_spec(pm_handle *h);
 static int ensure_landing(pm_handle *h, size_t need_more);
 static void device_sort_plan(pm_handle *h);
+static void win_release(pm_handle *h);
 
 static void free_device(pm_handle *h) {
   drain_spec(h);
+  win_release(h);
   if (h->land) (void)hipHostFree(h->land);
   h->land = nullptr; h->land_cap = h->land_n = h->land_pos = 0;
   if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
@@ -480,7 +512,7 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
   // -w/-W on a raw stream: IUPAC classes name up to 16 letters each, the kernels keep 6 character
   // classes in registers -- only the letters that occur in the stream need one
   if (!table && h->cfg.wildcards) {
-    if (h->host_only) {                                             // no device copy: look at the host bytes
+    if (h->host_only || h->win) {                                   // no device copy of the whole stream: look at the host bytes
       for (int i = 0; i < 256; ++i) h->alpha.present[i] = false;
       for (int64_t i = 0; i < h->n; ++i) h->alpha.present[h->h_text[i]] = true;
     } else HIP_TRY(h, stream_presence(h->d_text, h->n, h->alpha.present, h->stream));
@@ -722,7 +754,8 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
   }
   if (!h->d_cands) { rc = ensure_capacity(h, (size_t)1 << 20); if (rc) return rc; }
   if (h->edits_dev && !h->host_only) {                              // every candidate is reported by several seeds before the dedup
-    const size_t want = std::min<size_t>(std::max<size_t>((size_t)(h->n / 24), (size_t)1 << 22), (size_t)1 << 28);
+    const int64_t span = h->win ? std::min(h->n, h->win) : h->n;    // (a windowed handle scans at most a window at a time)
+    const size_t want = std::min<size_t>(std::max<size_t>((size_t)(span / 24), (size_t)1 << 22), (size_t)1 << 28);
     if (h->cap < want) { rc = ensure_capacity(h, want); if (rc) return rc; }
   }
   device_sort_plan(h);
@@ -799,10 +832,221 @@ static int ensure_packed(pm_handle *h) {
   return PM_OK;
 }
 
+// ---- windowed stream (pm_init_windowed) -------------------------------------
+
+// How far the device stages of this handle read stream text behind and ahead of a scanned range (begin, end]:
+//  - scan kernels: a hit that ends at e reads [e - L - k, e) (bit-parallel rows, seed and pair windows); the pair
+//    geometry of the edit plan scans begin - 3 .. end + 2; exact_bases -k widens its range by L + 2k + 4 on both sides
+//    (pm_scan_candidates_async) and then reads L + k behind that; exact_halves reads the zero bytes past n (overhang);
+//  - finalize stages: extend_seeds reads L + k on either side of a seed, cluster_dp_device [first - L - k, last] of a
+//    cluster (carried clusters: carry_reach), gather_windows is not used (the handle has the host copy);
+//  - the seed family's kernels carry 16 bases from one block of 1024 into the next.
+// L = the longest pattern; 64 bases of slack on top.  The kernels also READ text whose characters cannot reach a hit in
+// (begin, end]: the bit-parallel kernel runs its automaton from the start of the aligned segment that holds `begin` (up to
+// 4 Mi positions in front of it), a wave of the seed and pair kernels walks its whole sub-range of an aligned chunk and
+// prefetches four blocks of 1024 bases ahead -- the guard margins of a slot (pm_init_windowed) cover those reads.
+static void stream_halo(const pm_handle *h, int64_t *back, int64_t *fwd) {
+  int64_t L = 0;
+  for (const Pattern &p : h->pats) L = std::max<int64_t>(L, (int64_t)p.s.size());
+  const int64_t k = h->cfg.k;
+  const int64_t r = 2 * L + 3 * k + 4 + 16 + 64;
+  *back = (r + 63) / 64 * 64;
+  *fwd = *back;
+}
+
+// the records pm_scan carries into the next piece: the earliest text the device cluster DP will read for them
+static bool dp_on_device(const pm_handle *h) {
+  return h->sem == PM_SEM_FILTER_BITVEC && h->edits_dev && !h->cfg.wildcards && h->pats.size() < ((size_t)1 << 22);
+}
+static int64_t carry_reach(const pm_handle *h) {
+  int64_t lo = INT64_MAX, L = 0;
+  for (const pm_hit &c : h->carry) lo = std::min(lo, c.end);
+  for (const Pattern &p : h->pats) L = std::max<int64_t>(L, (int64_t)p.s.size());
+  return lo == INT64_MAX ? lo : lo - L - h->cfg.k - 64;
+}
+
+// longest piece pm_scan hands to one window: the piece plus its halo (and the 64-byte alignment of a window start) fit
+static int64_t win_piece_cap(const pm_handle *h) { return h->win - h->win_back - h->win_fwd - 64; }
+
+static size_t slot_bytes(const pm_handle *h, int64_t cap) { return (size_t)(cap + 2 * h->win_guard); }
+static size_t slot_words(const pm_handle *h, int64_t cap) { return (size_t)((cap + 2 * h->win_guard) / 16 + 128); }
+
+static void win_account(pm_handle *h) {
+  int64_t held = 0;
+  for (const WinSlot &s : h->slot) {
+    if (s.bytes) held += (int64_t)slot_bytes(h, s.cap);
+    if (s.words) held += (int64_t)slot_words(h, s.cap) * 4;
+  }
+  h->win_held = held;
+  h->win_peak = std::max(h->win_peak, held);
+}
+
+static void win_release(pm_handle *h) {
+  if (!h->win && !h->up_stream && !h->stage_st[0] && !h->slot[0].bytes && !h->slot[1].bytes) return;
+  (void)hipStreamSynchronize(h->stream);
+  if (h->up_stream) (void)hipStreamSynchronize(h->up_stream);
+  for (int t = 0; t < WIN_UP_THREADS; ++t) if (h->stage_st[t]) (void)hipStreamSynchronize(h->stage_st[t]);
+  for (WinSlot &s : h->slot) {
+    if (s.bytes) (void)hipFree(s.bytes);
+    if (s.words) (void)hipFree(s.words);
+    if (s.ready) (void)hipEventDestroy(s.ready);
+    if (s.used) (void)hipEventDestroy(s.used);
+    s = WinSlot();
+  }
+  for (int t = 0; t < WIN_UP_THREADS; ++t) {
+    for (int q = 0; q < 2; ++q) {
+      if (h->stage[t][q]) (void)hipHostFree(h->stage[t][q]);
+      if (h->stage_ev[t][q]) (void)hipEventDestroy(h->stage_ev[t][q]);
+      h->stage[t][q] = nullptr; h->stage_ev[t][q] = nullptr;
+    }
+    if (h->stage_done[t]) (void)hipEventDestroy(h->stage_done[t]);
+    if (h->stage_st[t]) (void)hipStreamDestroy(h->stage_st[t]);
+    h->stage_done[t] = nullptr; h->stage_st[t] = nullptr;
+  }
+  if (h->up_stream) (void)hipStreamDestroy(h->up_stream);
+  h->up_stream = nullptr;
+  if (h->win) { h->d_text = nullptr; h->d_packed = nullptr; h->packed_cap = 0; }   // (pointers into the slots, not allocations)
+  h->win = 0; h->bound = -1;
+  h->win_held = h->win_peak = h->win_uploaded = h->win_loads = 0;
+}
+
+// Upload stream text [lo, hi) into slot si (not the bound one) and pack it.  The host copies chunks into pinned staging
+// buffers, up to WIN_UP_THREADS threads on streams of their own (upload_stream's pattern); the copies wait for the last
+// kernel that read the slot (its `used` event), the packing runs on the upload stream behind them and `ready` marks the
+// end.  Returns once the last chunk is staged: the copies of the last chunks still run while the caller goes on.
+static int win_load(pm_handle *h, int si, int64_t lo, int64_t hi) {
+  WinSlot &s = h->slot[si];
+  const int64_t len = hi - lo;
+  const int64_t G = h->win_guard;
+  const bool packed = h->kern == PM_KERNEL_SEED;
+  if (!s.ready) HIP_TRY(h, hipEventCreateWithFlags(&s.ready, hipEventDisableTiming));
+  if (!s.used) HIP_TRY(h, hipEventCreateWithFlags(&s.used, hipEventDisableTiming));
+  if (!h->up_stream) HIP_TRY(h, hipStreamCreateWithFlags(&h->up_stream, hipStreamNonBlocking));
+  if (!h->stage_st[0]) {
+    for (int t = 0; t < WIN_UP_THREADS; ++t) {
+      HIP_TRY(h, hipStreamCreateWithFlags(&h->stage_st[t], hipStreamNonBlocking));
+      HIP_TRY(h, hipEventCreateWithFlags(&h->stage_done[t], hipEventDisableTiming));
+      for (int q = 0; q < 2; ++q) HIP_TRY(h, hipEventCreateWithFlags(&h->stage_ev[t][q], hipEventDisableTiming));
+    }
+  }
+  if (!s.bytes || s.cap < len || (packed && !s.words)) {           // first use, or a carried chain that needs more than a window
+    if (s.used_rec) HIP_TRY(h, hipEventSynchronize(s.used));
+    for (int t = 0; t < WIN_UP_THREADS; ++t) if (h->stage_st[t]) HIP_TRY(h, hipStreamSynchronize(h->stage_st[t]));   // (an earlier upload into it)
+    HIP_TRY(h, hipStreamSynchronize(h->up_stream));
+    if (s.bytes) (void)hipFree(s.bytes);
+    if (s.words) (void)hipFree(s.words);
+    s.bytes = nullptr; s.words = nullptr;
+    s.cap = std::max(h->win, (len + 63) / 64 * 64);
+    HIP_TRY(h, hipMalloc((void **)&s.bytes, slot_bytes(h, s.cap)));
+    HIP_TRY(h, hipMemsetAsync(s.bytes, 0, slot_bytes(h, s.cap), h->up_stream));
+    if (packed) {
+      HIP_TRY(h, hipMalloc((void **)&s.words, slot_words(h, s.cap) * 4));
+      HIP_TRY(h, hipMemsetAsync(s.words, 0, slot_words(h, s.cap) * 4, h->up_stream));
+    }
+    win_account(h);
+    HIP_TRY(h, hipStreamSynchronize(h->up_stream));
+  }
+  s.loaded = false;
+  uint8_t *dst = s.bytes + G;
+  const uint8_t *src = h->h_text + lo;
+  const int T = (int)std::min<int64_t>(WIN_UP_THREADS, std::max<int64_t>(1, len / (4 * WIN_UP_CHUNK)));
+  for (int t = 0; t < T; ++t)
+    for (int q = 0; q < 2; ++q)
+      if (!h->stage[t][q]) HIP_TRY(h, hipHostMalloc((void **)&h->stage[t][q], (size_t)WIN_UP_CHUNK, hipHostMallocDefault));
+  const int64_t per = ((len + T - 1) / T + WIN_UP_CHUNK - 1) / WIN_UP_CHUNK * WIN_UP_CHUNK;
+  std::vector<hipError_t> errs((size_t)T, hipSuccess);
+  const bool wait_used = s.used_rec;
+  auto work = [&](int t) {
+    hipError_t e = hipSetDevice(h->cfg.device);
+    const int64_t a = std::min(len, (int64_t)t * per), b = std::min(len, a + per);
+    if (e == hipSuccess && wait_used) e = hipStreamWaitEvent(h->stage_st[t], s.used, 0);
+    int q = 0;
+    for (int64_t off = a; off < b && e == hipSuccess; off += WIN_UP_CHUNK, q ^= 1) {
+      const size_t m = (size_t)std::min<int64_t>(WIN_UP_CHUNK, b - off);
+      e = hipEventSynchronize(h->stage_ev[t][q]);                   // the copy that last used this buffer is done
+      if (e != hipSuccess) break;
+      memcpy(h->stage[t][q], src + off, m);
+      e = hipMemcpyAsync(dst + off, h->stage[t][q], m, hipMemcpyHostToDevice, h->stage_st[t]);
+      if (e == hipSuccess) e = hipEventRecord(h->stage_ev[t][q], h->stage_st[t]);
+    }
+    if (e == hipSuccess) e = hipEventRecord(h->stage_done[t], h->stage_st[t]);
+    errs[(size_t)t] = e;
+  };
+  if (T == 1) work(0);
+  else {
+    std::vector<std::thread> th;
+    for (int t = 0; t < T; ++t) th.emplace_back(work, t);
+    for (std::thread &x : th) x.join();
+  }
+  for (hipError_t e : errs) if (e != hipSuccess) return hipfail(h, e, "window upload");
+  for (int t = 0; t < T; ++t) HIP_TRY(h, hipStreamWaitEvent(h->up_stream, h->stage_done[t], 0));
+  if (hi == h->n) HIP_TRY(h, hipMemsetAsync(dst + len, 0, 64, h->up_stream));     // the zero bytes past the end of the stream
+  if (packed) {
+    const int64_t nw = (len + 15) / 16;
+    uint32_t *wdst = s.words + G / 16;
+    HIP_TRY(h, pack_stream(dst, len, h->sd.ascii, wdst, nw, h->up_stream));       // (lo is a multiple of 64: words rebase like bytes)
+    if (hi == h->n) HIP_TRY(h, hipMemsetAsync(wdst + nw, 0, 128 * sizeof(uint32_t), h->up_stream));
+  }
+  HIP_TRY(h, hipEventRecord(s.ready, h->up_stream));
+  s.lo = lo; s.hi = hi; s.loaded = true;
+  h->win_uploaded += len; ++h->win_loads;
+  return PM_OK;
+}
+
+// Point d_text / d_packed at slot si; the handle's stream waits for its upload.  The slot given up is marked used up to
+// here: everything that reads it was enqueued on the handle's stream before.
+static int win_bind(pm_handle *h, int si) {
+  if (h->bound != si) {
+    if (h->bound >= 0) {
+      HIP_TRY(h, hipEventRecord(h->slot[h->bound].used, h->stream));
+      h->slot[h->bound].used_rec = true;
+    }
+    h->bound = si;
+  }
+  const WinSlot &s = h->slot[si];
+  const uintptr_t G = (uintptr_t)h->win_guard;
+  h->d_text = (const uint8_t *)((uintptr_t)s.bytes + G - (uintptr_t)s.lo);
+  h->d_packed = s.words ? (uint32_t *)((uintptr_t)s.words + (G / 16) * 4 - (uintptr_t)(s.lo / 16) * 4) : nullptr;
+  HIP_TRY(h, hipStreamWaitEvent(h->stream, s.ready, 0));
+  return PM_OK;
+}
+
+// Make stream text [lo, hi) (clipped to the stream) resident and bound.  A slot that holds it is bound as it is; else the
+// other slot takes the window [lo, lo + win).  A span longer than a window: `grow` (pm_scan, a carried chain) enlarges
+// the slot, otherwise PM_E_INVALID.
+static int win_need(pm_handle *h, int64_t lo, int64_t hi, bool grow, const char *who) {
+  lo = std::max<int64_t>(0, lo) / 64 * 64;
+  hi = std::max(lo, std::min(h->n, hi));
+  for (int si = 0; si < 2; ++si) {
+    const WinSlot &s = h->slot[si];
+    if (s.loaded && s.lo <= lo && s.hi >= hi) return win_bind(h, si);
+  }
+  if (hi - lo > h->win && !grow)
+    return fail(h, PM_E_INVALID, std::string(who) + ": the range needs " + std::to_string(hi - lo) + " bytes of stream text with its halo, more than the window of " +
+                                 std::to_string(h->win) + " bytes (pm_init_windowed)");
+  const int si = h->bound == 0 ? 1 : 0;
+  const int64_t top = std::min(h->n, std::max((hi + 63) / 64 * 64, lo + h->win));
+  int rc = win_load(h, si, lo, top);
+  if (rc) return rc;
+  return win_bind(h, si);
+}
+
+// pm_scan's look-ahead: when the range that follows (end, end + len] would not fit the bound window, the window it needs
+// goes into the other slot now, while the GPU scans the current one.
+static void win_prefetch(pm_handle *h, int64_t end, int64_t len) {
+  if (!h->win || h->bound < 0 || end >= h->n) return;
+  if (std::min(h->n, end + len + h->win_fwd) <= h->slot[h->bound].hi) return;
+  const int64_t nlo = std::max<int64_t>(0, end - h->win_back) / 64 * 64;
+  const int o = 1 - h->bound;
+  if (h->slot[o].loaded && h->slot[o].lo == nlo) return;
+  (void)win_load(h, o, nlo, std::min(h->n, nlo + h->win));          // (a failure leaves the slot unloaded: the next range loads it itself)
+}
+
 extern "C" int pm_init(pm_handle *h, const uint8_t *text, int64_t n, const uint8_t *table, int32_t table_len) {
   if (!h || (!text && n > 0) || n < 0) return fail(h, PM_E_INVALID, "pm_init: bad arguments");
   const double ti0 = now_ms();
   HIP_TRY(h, hipSetDevice(h->cfg.device));
+  win_release(h);
   if (h->own_d_text && h->d_text) { (void)hipFree((void *)h->d_text); h->d_text = nullptr; }
   void *d = nullptr;
   HIP_TRY(h, hipMalloc(&d, (size_t)(n > 0 ? n : 1) + 16));
@@ -836,6 +1080,7 @@ extern "C" int pm_init(pm_handle *h, const uint8_t *text, int64_t n, const uint8
 extern "C" int pm_init_host(pm_handle *h, const uint8_t *text, int64_t n, const uint8_t *table, int32_t table_len) {
   if (!h || (!text && n > 0) || n < 0) return fail(h, PM_E_INVALID, "pm_init_host: bad arguments");
   HIP_TRY(h, hipSetDevice(h->cfg.device));
+  win_release(h);
   if (h->own_d_text && h->d_text) (void)hipFree((void *)h->d_text);
   h->d_text = nullptr; h->own_d_text = false; h->h_text = text; h->n = n; h->stream = nullptr;
   h->host_only = true;
@@ -847,12 +1092,57 @@ extern "C" int pm_init_device(pm_handle *h, const void *d_text, int64_t n, const
   if (!h || (!d_text && n > 0) || n < 0) return fail(h, PM_E_INVALID, "pm_init_device: bad arguments");
   if (((uintptr_t)d_text) & 3) return fail(h, PM_E_INVALID, "pm_init_device: stream must be 4-byte aligned");
   HIP_TRY(h, hipSetDevice(h->cfg.device));
+  win_release(h);
   if (h->own_d_text && h->d_text) (void)hipFree((void *)h->d_text);
   h->d_text = (const uint8_t *)d_text; h->own_d_text = false; h->h_text = nullptr; h->n = n; h->host_only = false;
   h->stream = (hipStream_t)hip_stream;
   const int rc = init_common(h, table, table_len);
   if (rc) return rc;
   return ensure_packed(h);
+}
+
+extern "C" int pm_init_windowed(pm_handle *h, const uint8_t *text, int64_t n, const uint8_t *table, int32_t table_len,
+                                int64_t window_bytes) {
+  if (!h || (!text && n > 0) || n < 0 || window_bytes <= 0) return fail(h, PM_E_INVALID, "pm_init_windowed: bad arguments");
+  HIP_TRY(h, hipSetDevice(h->cfg.device));
+  win_release(h);
+  if (h->own_d_text && h->d_text) (void)hipFree((void *)h->d_text);
+  if (h->d_packed) (void)hipFree(h->d_packed);                      // (a resident init's 2-bit copy)
+  h->d_packed = nullptr; h->packed_cap = 0;
+  h->d_text = nullptr; h->own_d_text = false; h->h_text = text; h->n = n; h->stream = nullptr; h->host_only = false;
+  stream_halo(h, &h->win_back, &h->win_fwd);
+  // guard: the halo plus the longest aligned run a kernel starts in front of `begin` (bit-parallel segment: 4 Mi positions,
+  // seed / pair chunk: 2 Mi, or what the test knobs set) and the seed kernels' prefetch of four blocks of 1024 bases ahead
+  const int64_t run = std::max<int64_t>({(int64_t)1 << 22, h->knobs.seed_chunk, 64 * h->knobs.bitpar_seglen});
+  h->win_guard = (std::max(h->win_back, h->win_fwd) + run + 512 + 16384 + 63) / 64 * 64;
+  const int64_t minimum = 4 * (h->win_back + h->win_fwd);
+  h->win = std::max(minimum, (window_bytes + 63) / 64 * 64);
+  h->bound = -1;
+  return init_common(h, table, table_len);
+}
+
+extern "C" int pm_stream_residency(const pm_handle *h, int64_t *out, int n) {
+  if (!h || !h->inited || !out || n < 0) return PM_E_INVALID;
+  int64_t v[5] = {0, 0, 0, 0, 0};
+  if (h->win) {
+    v[0] = h->win; v[1] = h->win_held; v[2] = h->win_peak; v[3] = h->win_uploaded; v[4] = h->win_loads;
+  } else if (!h->host_only) {                                       // the whole stream (pm_init: uploaded once; pm_init_device: the caller's)
+    v[1] = (h->d_text ? (h->own_d_text ? h->n + 16 : h->n) : 0) + (h->d_packed ? (int64_t)(h->packed_cap + 128) * 4 : 0);
+    v[2] = v[1];
+    v[3] = h->own_d_text ? h->n : 0;
+    v[4] = h->own_d_text ? 1 : 0;
+  }
+  for (int i = 0; i < n && i < 5; ++i) out[i] = v[i];
+  return PM_OK;
+}
+
+extern "C" int pm_device_memory(int device, int64_t *free_bytes, int64_t *total_bytes) {
+  if (!free_bytes || !total_bytes) return PM_E_INVALID;
+  if (hipSetDevice(device) != hipSuccess) return PM_E_HIP;
+  size_t fr = 0, tot = 0;
+  if (hipMemGetInfo(&fr, &tot) != hipSuccess) return PM_E_HIP;
+  *free_bytes = (int64_t)fr; *total_bytes = (int64_t)tot;
+  return PM_OK;
 }
 
 extern "C" int pm_set_capacity(pm_handle *h, size_t max_candidates) {
@@ -929,6 +1219,12 @@ extern "C" int pm_scan_candidates_async(pm_handle *h, int64_t begin, int64_t end
   if (end > h->n) end = h->n;
   HIP_TRY(h, hipSetDevice(h->cfg.device));
   drain_spec(h);
+  if (h->win) {                                                     // windowed handle: the range's text, its halo and what carried clusters need
+    int64_t lo = begin - h->win_back;
+    if (dp_on_device(h) && !h->carry.empty()) lo = std::min(lo, carry_reach(h));
+    const int rcw = win_need(h, lo, end + h->win_fwd, h->bound_on, "pm_scan_candidates");
+    if (rcw) return rcw;
+  }
   HIP_TRY(h, hipMemsetAsync(h->d_counter, 0, sizeof(unsigned long long), h->stream));
   HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
   h->own_begin = begin; h->own_end = end;
@@ -1014,6 +1310,7 @@ extern "C" int pm_scan_candidates_async(pm_handle *h, int64_t begin, int64_t end
   HIP_TRY(h, hipMemcpyAsync(h->h_counter, h->d_counter, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
   if (h->kern != PM_KERNEL_SEED) h->last_launches = 1;
   h->scan_pending = true;
+  if (h->win && h->bound_on) win_prefetch(h, h->own_end, h->own_end - h->own_begin);   // (the upload overlaps this scan)
   return PM_OK;
 }
 
@@ -1535,6 +1832,7 @@ extern "C" int pm_scan_stats(pm_handle *h, uint64_t *out, int n) {
 // Produces no hits: *ms is the kernel's duration, *suspects the records it would hand to a verify kernel.
 extern "C" int pm_measure_pair_edit_floor(pm_handle *h, int mode, float *ms, uint64_t *suspects) {
   if (!h || !h->inited || !ms || !suspects || (mode != 1 && mode != 2)) return fail(h, PM_E_INVALID, "pm_measure_pair_edit_floor: bad arguments");
+  if (h->win) return fail(h, PM_E_INVALID, "pm_measure_pair_edit_floor: needs the whole stream resident (not pm_init_windowed)");
   if (h->kern != PM_KERNEL_SEED || h->pair.size() != 1 || h->cfg.k != 2 || h->cfg.indels)
     return fail(h, PM_E_UNSUPPORTED, "pm_measure_pair_edit_floor: needs a -K 2 handle on the pair plan (one pattern tile)");
   HIP_TRY(h, hipSetDevice(h->cfg.device));
@@ -2206,6 +2504,10 @@ static int finalize_device_impl(pm_handle *h, const void *d_cands, size_t n, int
   // candidates an earlier range left undecided (clusters that could still grow) join this batch on
   // the device: their chains continue here
   std::vector<pm_hit> hostpart;
+  if (cluster_dp && h->win && !h->carry.empty()) {                 // the cluster DPs of carried records read text behind the scanned range
+    const int rcw = win_need(h, carry_reach(h), h->own_end + h->win_fwd, h->bound_on, "pm_finalize_device");
+    if (rcw) return rcw;
+  }
   const size_t ncarry = h->carry.size();
   if (ncarry) {
     if (h->d_carry_cap < ncarry) {
@@ -2426,7 +2728,8 @@ static int scan_range(pm_handle *h, int64_t begin, int64_t end) {
   const size_t before = h->land_n - h->land_pos;                    // (ensure_landing may move the live hits to the front of the buffer)
   int pieces = 0;
   for (int64_t pos = begin; pos < end;) {
-    const int64_t len = h->piece_len ? std::min<int64_t>(h->piece_len, end - pos) : end - pos;
+    int64_t len = h->piece_len ? std::min<int64_t>(h->piece_len, end - pos) : end - pos;
+    if (h->win) len = std::min(len, win_piece_cap(h));             // windowed: a piece and its halo fit one window
     h->dense_mode = len < end - begin;                              // (no guess of the next range while in pieces: they are not the caller's ranges)
     h->bound_on = true;
     const int rc = scan_piece(h, pos, pos + len);

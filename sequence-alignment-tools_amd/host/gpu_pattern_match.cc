@@ -30,6 +30,19 @@ void BufferChars::build_inverse() {
 // halo of text the windows / seed extensions of the outermost candidates read
 static const int64_t SHARD_GUARD = 1 << 16, SHARD_HALO = 256;
 
+// The stream stays in host memory and the GPU holds a ring of windows of it (pm_init_windowed) when PM_GPU_WINDOW=<bytes>
+// asks for it, or when the resident form -- 1.25 bytes of HBM per base, text + 2-bit words -- plus a reserve for record
+// lists, sort workspace and pattern tables does not fit the free HBM.  0: resident (pm_init), as every database that fits.
+// Default window 1 GiB: measured passes over 3 Gbp took the same time in 256 MiB and 1 GiB windows, while larger windows
+// only add HBM (2.7 GB for the stream at 1 GiB) and a longer first upload (profiles/windowed_pass.json).
+static const int64_t RESIDENT_RESERVE = (int64_t)16 << 30, DEFAULT_WINDOW = (int64_t)1 << 30;
+static int64_t window_for(int device, int64_t n) {
+  if (const char *w = getenv("PM_GPU_WINDOW")) { const long long v = atoll(w); if (v > 0) return v; }
+  int64_t fr = 0, tot = 0;
+  if (pm_device_memory(device, &fr, &tot) != PM_OK) return 0;
+  return n + n / 4 + RESIDENT_RESERVE > fr ? DEFAULT_WINDOW : 0;
+}
+
 GpuPatternMatch::GpuPatternMatch(int kernel, unsigned int k, char eos, bool wc, bool tn, bool indels,
                                  bool dna_mut, int semantics, int device, RankGroup *group) {
   if (dna_mut) { fprintf(stderr, "Fatal error: DNA mutation scoring is not available in the GPU engine.\n"); exit(1); }
@@ -39,6 +52,7 @@ GpuPatternMatch::GpuPatternMatch(int kernel, unsigned int k, char eos, bool wc, 
   cfg.semantics = semantics; cfg.kernel = kernel; cfg.k = (int32_t)k; cfg.indels = indels ? 1 : 0;
   cfg.wildcards = wc ? 1 : 0; cfg.text_n = tn ? 1 : 0; cfg.eos = (unsigned char)eos;
   cfg.device = group_ ? group_->device() : device;
+  device_ = cfg.device;
   if (pm_create(&cfg, &h_) != PM_OK) { fprintf(stderr, "Fatal error: %s\n", pm_last_error(nullptr)); exit(1); }
   if (group_ && group_->rank() == 0 && pm_create(&cfg, &merge_) != PM_OK) { fprintf(stderr, "Fatal error: %s\n", pm_last_error(nullptr)); exit(1); }
 }
@@ -80,7 +94,15 @@ void GpuPatternMatch::init(CharacterProducer &cp) {
   }
   const uint8_t *tb = table.empty() ? nullptr : reinterpret_cast<const uint8_t *>(table.data());
   if (!group_) {
-    if (pm_init(h_, bytes, n_, tb, (int32_t)table.size()) != PM_OK) fatal("init");
+    const int64_t win = window_for(device_, n_);
+    if (win > 0 ? pm_init_windowed(h_, bytes, n_, tb, (int32_t)table.size(), win) != PM_OK
+                : pm_init(h_, bytes, n_, tb, (int32_t)table.size()) != PM_OK) fatal("init");
+    if (verbose_) {
+      int64_t res[5] = {0, 0, 0, 0, 0};
+      (void)pm_stream_residency(h_, res, 5);
+      if (res[0] > 0) fprintf(stderr, "stream: windowed, window %lld bytes (%lld-byte stream stays in host memory)\n", (long long)res[0], (long long)n_);
+      else fprintf(stderr, "stream: resident, %lld bytes in HBM\n", (long long)n_);
+    }
     return;
   }
   // position shard of this rank: its GPU holds stream bytes [glo_, ghi_) only, and

@@ -84,6 +84,7 @@ class GpuPatternMatch {
   int selected_semantics() const;
   int selected_kernel() const;
   void chunk_bytes(int64_t c) { chunk_ = c; }
+  void verbose(bool v) { verbose_ = v; }                                      // -v: init names the stream's residency mode
   // for the caller's per-hit re-alignment (pm_align_hits_text): the handle that knows the whole stream
   pm_handle *handle() const { return merge_ ? merge_ : h_; }
  private:
@@ -99,6 +100,8 @@ class GpuPatternMatch {
   int64_t n_ = 0;
   int64_t chunk_ = (int64_t)1 << 30;
   unsigned long next_id_ = 0;
+  int device_ = 0;
+  bool verbose_ = false;
 };
 
 }  // namespace pmgpu

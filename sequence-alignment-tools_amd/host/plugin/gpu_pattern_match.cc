@@ -6,6 +6,16 @@
 
 #include "util.h"            // reference: timestamp()
 
+// The stream stays in host memory and the GPU holds a ring of windows of it (pm_init_windowed) when PM_GPU_WINDOW=<bytes>
+// asks for it, or when the resident form -- 1.25 bytes of HBM per base -- plus a reserve for record lists, sort workspace
+// and pattern tables does not fit the free HBM (the rule and the 1 GiB default of host/gpu_pattern_match.cc).
+static int64_t window_for(int device, int64_t n) {
+  if (const char *w = getenv("PM_GPU_WINDOW")) { const long long v = atoll(w); if (v > 0) return v; }
+  int64_t fr = 0, tot = 0;
+  if (pm_device_memory(device, &fr, &tot) != PM_OK) return 0;
+  return n + n / 4 + ((int64_t)16 << 30) > fr ? ((int64_t)1 << 30) : 0;
+}
+
 gpu_pattern_match::gpu_pattern_match(int kernel, unsigned int k, char eos, bool wc, bool tn, bool indels, bool dna_mut)
     : h_(0), n_(0), base_(0), chunk_((FILE_POSITION_TYPE)1 << 30) {
   if (dna_mut) {
@@ -22,6 +32,7 @@ gpu_pattern_match::gpu_pattern_match(int kernel, unsigned int k, char eos, bool 
   cfg.text_n = tn ? 1 : 0;
   cfg.eos = (unsigned char)eos;
   if (const char *dev = getenv("PM_GPU_DEVICE")) cfg.device = atoi(dev);
+  device_ = cfg.device;
   if (pm_create(&cfg, &h_) != PM_OK) {
     std::string msg = std::string("Fatal error: ") + pm_last_error(0);
     timestamp(msg.c_str());
@@ -64,8 +75,10 @@ void gpu_pattern_match::init(CharacterProducer &cp) {
     n_ = (FILE_POSITION_TYPE)drained_.size();
   }
   cp.pos(save);
-  if (pm_init(h_, bytes, (int64_t)n_, table.empty() ? 0 : reinterpret_cast<const uint8_t *>(table.data()),
-              (int32_t)table.size()) != PM_OK)
+  const uint8_t *tb = table.empty() ? 0 : reinterpret_cast<const uint8_t *>(table.data());
+  const int64_t win = window_for(device_, (int64_t)n_);
+  if (win > 0 ? pm_init_windowed(h_, bytes, (int64_t)n_, tb, (int32_t)table.size(), win) != PM_OK
+              : pm_init(h_, bytes, (int64_t)n_, tb, (int32_t)table.size()) != PM_OK)
     fatal("init");
 }
 

@@ -37,6 +37,7 @@ class gpu_pattern_match : public PatternMatch {
   FILE_POSITION_TYPE n_;                              // stream bytes
   FILE_POSITION_TYPE base_;                           // cp.pos() of stream byte 0 (fasta_io.t:234-235 offset_)
   FILE_POSITION_TYPE chunk_;
+  int device_ = 0;
 };
 
 #endif

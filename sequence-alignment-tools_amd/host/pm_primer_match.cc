@@ -379,6 +379,7 @@ int main(int argc, char **argv) {
     maxlen = std::max(maxlen, patarray[i].size());
   }
   BufferChars &ff = db.chars();
+  kt.verbose(opt.chatty);
   kt.init(ff);
   if (!ranks.single() && ranks.rank() != 0) {                        // this rank scans its shard, hands its records to rank 0 and is done
     pattern_hit_vector none;

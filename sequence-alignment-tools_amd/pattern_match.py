@@ -24,6 +24,7 @@ ABI_SYMBOLS = [
     "pm_reset", "pm_destroy", "pm_last_error", "pm_selected_semantics", "pm_selected_kernel", "pm_describe",
     "pm_last_kernel_time", "pm_pick_semantics", "pm_measure_stream_read",
     "pm_final_hits_device", "pm_copy_records", "pm_pack_time", "pm_init_host", "pm_scan_stats", "pm_measure_pair_edit_floor", "pm_prepare_device",
+    "pm_init_windowed", "pm_stream_residency", "pm_device_memory",
     "pm_comm_unique_id", "pm_comm_create", "pm_comm_gather", "pm_comm_destroy", "pm_comm_last_error",
 ]
 
@@ -86,6 +87,9 @@ def load_library():
         L.pm_init.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32]
         L.pm_init_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32]
         L.pm_init_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]
+        L.pm_init_windowed.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int64]
+        L.pm_stream_residency.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_int]
+        L.pm_device_memory.argtypes = [C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.pm_scan.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
         L.pm_scan_view.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
         L.pm_scan_candidates.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
@@ -188,13 +192,19 @@ class PatternMatch:
         return id
 
     # -- PatternMatch::init (pattern_match.h:130) -----------------------------------------------
-    def init(self, text, table=None):
+    def init(self, text, table=None, window=None):
         """`text`: uint8 numpy array (host stream bytes as getnch() returns them).
-        `table`: cp.ch(0..size-1) for a normalized stream, None for a raw one."""
+        `table`: cp.ch(0..size-1) for a normalized stream, None for a raw one.
+        `window`: bytes per window of pm_init_windowed -- the stream stays in host memory and the GPU holds a ring of
+        windows of it; None uploads the whole stream (pm_init)."""
         arr = np.ascontiguousarray(text, dtype=np.uint8)
         self._keep = arr                      # pm_init borrows the host pointer
         tb = None if table is None else (C.c_uint8 * len(table)).from_buffer_copy(bytes(table))
-        self._check(self._L.pm_init(self._h, arr.ctypes.data_as(C.c_void_p), arr.size, tb, 0 if table is None else len(table)))
+        tl = 0 if table is None else len(table)
+        if window is None:
+            self._check(self._L.pm_init(self._h, arr.ctypes.data_as(C.c_void_p), arr.size, tb, tl))
+        else:
+            self._check(self._L.pm_init_windowed(self._h, arr.ctypes.data_as(C.c_void_p), arr.size, tb, tl, int(window)))
         self._n, self._pos = arr.size, 0
 
     def init_host(self, text, table=None):
@@ -376,6 +386,14 @@ class PatternMatch:
         v = (C.c_uint64 * 8)()
         self._check(self._L.pm_scan_stats(self._h, v, 8))
         names = ("candidates", "between_stages", "internal_rescans", "blocks", "rounds", "key_hits", "range_splits")
+        return {k: int(v[i]) for i, k in enumerate(names)}
+
+    def residency(self):
+        """pm_stream_residency: the window size in use (0 = whole stream resident), HBM bytes held for the stream now and
+        at peak, stream bytes uploaded and window loads since init"""
+        v = (C.c_int64 * 5)()
+        self._check(self._L.pm_stream_residency(self._h, v, 5))
+        names = ("window", "held", "peak", "uploaded", "loads")
         return {k: int(v[i]) for i, k in enumerate(names)}
 
     def measure_pair_edit_floor(self, mode):
