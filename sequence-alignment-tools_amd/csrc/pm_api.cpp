@@ -244,6 +244,7 @@ static void read_knobs(Knobs *k) {
   k->seed_tile = (long)num("PM_SEED_TILE");
   if (const char *v = getenv("PM_PAIR")) k->pair = atoi(v);
   k->pair_row = (int)num("PM_PAIR_ROW");
+  k->pair_map = is("PM_PAIR_MAP", "superchunk") ? PAIR_MAP_SUPERCHUNK : is("PM_PAIR_MAP", "xcd") ? PAIR_MAP_XCD : is("PM_PAIR_MAP", "xcd-superchunk") ? PAIR_MAP_XCD_SUPERCHUNK : -1;
   k->half_bloom = is("PM_HALF_SCAN", "bloom"); k->edit_bloom = is("PM_EDIT_SCAN", "bloom"); k->edit_hash = is("PM_EDIT_SCAN", "hash");
   k->edit_table_log = (int)num("PM_EDIT_TABLE_LOG");
   if (const char *v = getenv("PM_BITPAR_TP")) k->bitpar_tp = atoi(v) != 0;
@@ -1174,19 +1175,26 @@ extern "C" const char *pm_last_error(const pm_handle *h) { return h ? h->err.c_s
 extern "C" int pm_selected_semantics(const pm_handle *h) { return h && h->inited ? h->sem : PM_E_INVALID; }
 extern "C" int pm_selected_kernel(const pm_handle *h) { return h && h->inited ? h->kern : PM_E_INVALID; }
 
+// workgroup -> (field pair, chunk) of the pair kernels (pm_workmap.h): "xcd" = every XCD walks its share of the chunks one
+// field pair after the other; "superchunk" = runs of 256 chunks per field pair over the whole grid
+static const char *pair_schedule_name(const ScanGeometry &g) {
+  return g.work_map == PAIR_MAP_XCD_SUPERCHUNK ? "xcd-superchunk" : g.work_map == PAIR_MAP_XCD ? "xcd" : "superchunk";
+}
+
 extern "C" int pm_describe(const pm_handle *h, char *buf, size_t buflen) {
   if (!h || !buf || !h->inited) return PM_E_INVALID;
   if (h->kern == PM_KERNEL_SEED && !h->pair.empty()) {
-    snprintf(buf, buflen, "kernel=pm_pair_scan tiles=%d combos=%d fields=2-of-4 x 5 bases window=20 row_slots=%d chunk=%lld nchunks=%d grid=%d block=%d lds=%d",
-             (int)h->pair.size(), h->pair[0].ncombos, h->pair[0].stride, (long long)h->geo.seg_len, h->geo.nseg, h->geo.blocks, h->geo.threads, PAIR_LDS_BYTES);
+    snprintf(buf, buflen, "kernel=pm_pair_scan tiles=%d combos=%d fields=2-of-4 x 5 bases window=20 row_slots=%d chunk=%lld nchunks=%d grid=%d block=%d lds=%d schedule=%s",
+             (int)h->pair.size(), h->pair[0].ncombos, h->pair[0].stride, (long long)h->geo.seg_len, h->geo.nseg, h->geo.blocks, h->geo.threads, PAIR_LDS_BYTES,
+             pair_schedule_name(h->geo));
     if (h->nrest) {
       const size_t at = strlen(buf);
       if (at < buflen) snprintf(buf + at, buflen - at, " + %s for %zu patterns the seed plan does not take", bitpar_kernel_name(h->scan_k, h->scan_indels), h->nrest);
     }
   }
   else if (h->kern == PM_KERNEL_SEED && h->edits_dev && h->epair_on) {
-    snprintf(buf, buflen, "kernel=pm_pair_edit_scan+pm_pair_edit_resolve+pm_edits_verify tiles=1 tests=14 fields=2-of-4 x 5 bases, displaced by |d| <= 2 window=20 row_slots=%d slot_patterns=2 chunk=%lld nchunks=%d grid=%d block=%d lds=%d",
-             h->epair.stride, (long long)h->geo.seg_len, h->geo.nseg, h->geo.blocks, h->geo.threads, PAIR_LDS_BYTES);
+    snprintf(buf, buflen, "kernel=pm_pair_edit_scan+pm_pair_edit_resolve+pm_edits_verify tiles=1 tests=14 fields=2-of-4 x 5 bases, displaced by |d| <= 2 window=20 row_slots=%d slot_patterns=2 chunk=%lld nchunks=%d grid=%d block=%d lds=%d schedule=%s",
+             h->epair.stride, (long long)h->geo.seg_len, h->geo.nseg, h->geo.blocks, h->geo.threads, PAIR_LDS_BYTES, pair_schedule_name(h->geo));
     if (h->nrest) {
       const size_t at = strlen(buf);
       if (at < buflen) snprintf(buf + at, buflen - at, " + %s for %zu patterns the seed plan does not take", bitpar_kernel_name(h->scan_k, h->scan_indels), h->nrest);

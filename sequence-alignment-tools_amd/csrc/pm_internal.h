@@ -27,7 +27,7 @@ struct Alphabet {
   void set_table(const uint8_t *table, int len);
 };
 
-// Test and measurement knobs (PM_SEED_CHUNK, PM_SEED_GROUP, PM_SEED_DEBUG, PM_SEED_TILE, PM_PAIR, PM_HALF_SCAN,
+// Test and measurement knobs (PM_SEED_CHUNK, PM_SEED_GROUP, PM_SEED_DEBUG, PM_SEED_TILE, PM_PAIR, PM_PAIR_ROW, PM_PAIR_MAP, PM_HALF_SCAN,
 // PM_EDIT_SCAN, PM_EDIT_TABLE_LOG, PM_BITPAR_TP, PM_BITPAR_SEGLEN, PM_DEBUG).  The environment is read ONCE, by
 // pm_create (pm_api.cpp read_knobs), into the handle: nothing on the init or launch path calls getenv, and a
 // handle's behaviour does not change when its caller's environment does.  Every field's 0 / -1 / false = unset.
@@ -38,6 +38,7 @@ struct Knobs {
   long seed_tile = 0;                // keys per pattern tile
   int pair = -1;                     // 0: keep -K 1 / -K 2 off the pair plan
   int pair_row = 0;                  // PM_PAIR_ROW: slots per row of the pair plan's slot table (measurement)
+  int pair_map = -1;                 // PM_PAIR_MAP: workgroup -> (field pair, chunk) of the pair kernels (pm_workmap.h PAIR_MAP_*; -1: by range size)
   bool half_bloom = false;           // exact_halves -k on the round-1 form (PM_HALF_SCAN=bloom)
   bool edit_bloom = false;           // edits: first stage = the round-1 pm_seed_scan instance (PM_EDIT_SCAN=bloom)
   bool edit_hash = false;            // edits: first stage = round 2's pm_edit_scan (PM_EDIT_SCAN=hash) where the pair geometry would run (-k 2, one tile)
@@ -83,7 +84,7 @@ std::string bitpar_build(const std::vector<Pattern> &pats, const std::vector<uin
 hipError_t bitpar_upload(const BitparTables &t, bool indels, BitparDevice *d, hipStream_t st);
 void bitpar_free(BitparDevice *d);
 
-struct ScanGeometry { int64_t seg_len; int nseg; int blocks; int threads; };
+struct ScanGeometry { int64_t seg_len; int nseg; int blocks; int threads; int work_map = 0; };   // work_map: pair kernels, pm_workmap.h
 ScanGeometry bitpar_geometry(const BitparDevice &d, int64_t begin, int64_t end);
 
 // Enqueue the scan of stream range (begin,end] (hit end positions) on `st`.

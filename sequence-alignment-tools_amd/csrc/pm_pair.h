@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "pm_internal.h"
+#include "pm_workmap.h"
 
 namespace pm {
 
@@ -24,6 +25,7 @@ constexpr int PAIR_BITMAP_WORDS = 32768;            // 2^20 key bits: key bits 0
 constexpr int PAIR_QUEUE = 128;                     // per wave: suspect records (16 bytes) waiting to leave in a batch
 constexpr int PAIR_LDS_BYTES = PAIR_BITMAP_WORDS * 4 + PAIR_WAVES * PAIR_QUEUE * 16;   // key bitmap + the waves' suspect queues
 static_assert(PAIR_LDS_BYTES <= 163840, "160 KiB of LDS per workgroup");
+constexpr int PAIR_XCD_MIN_CHUNKS = 5 * 256;        // chunks from which pair_geometry takes the XCD map (pm_workmap.h): 5 workgroups per CU and combo
 
 struct PairTables {                                 // one pattern tile
   int k = 0, maxlen = 0, ncombos = 0, eos_code = -1, stride = 0;

@@ -44,6 +44,7 @@
 // direct table could not settle, and did the rank / address / compare work branch-free for all windows.
 #include "pm_internal.h"
 #include "pm_pair.h"
+#include "pm_workmap.h"
 
 #include <algorithm>
 #include <cstring>
@@ -76,6 +77,7 @@ struct PairArgs {
   int64_t npacked;
   int64_t chunk0, chunk_len;            // first chunk index (absolute), positions per workgroup
   int nchunks, ncombos, group;
+  int work_map;                         // blockIdx -> (combo, chunk), pm_workmap.h: PAIR_MAP_SUPERCHUNK, PAIR_MAP_XCD, PAIR_MAP_XCD_SUPERCHUNK
   int k, eos_code, debug;
   int stride;                           // slots per row of the slot table (the last one is the row's overflow marker)
   int fa[PAIR_MAX_COMBOS], fb[PAIR_MAX_COMBOS];
@@ -807,23 +809,18 @@ __device__ __forceinline__ void pair_scan_body(const PairArgs &a, const int comb
   }
 }
 
+// blockIdx -> (combo, chunk) of this workgroup (pm_workmap.h); false: none
+__device__ __forceinline__ bool pair_block_item(const PairArgs &a, int *combo, int *cj) {
+  if (a.work_map == PAIR_MAP_XCD_SUPERCHUNK) pair_xcd_superchunk_item((int)blockIdx.x, a.nchunks, a.ncombos, a.group, combo, cj);
+  else if (a.work_map == PAIR_MAP_XCD) pair_xcd_item((int)blockIdx.x, a.nchunks, a.ncombos, combo, cj);
+  else pair_superchunk_item((int)blockIdx.x, a.nchunks, a.ncombos, a.group, combo, cj);
+  return *cj < a.nchunks && *combo < a.ncombos;
+}
+
 __global__ __launch_bounds__(PAIR_THREADS) void pm_pair_scan(PairArgs a) {
   extern __shared__ uint32_t lds[];
-  // blockIdx -> (combo, chunk): runs of `group` chunks share a combo, all combos of a superchunk
-  // follow each other (the superchunk's stream is re-read from MALL, a combo's table stays in L2)
-  const int per_super = a.group * a.ncombos;
-  const int sc = blockIdx.x / per_super;
-  const int rem = blockIdx.x - sc * per_super;
-  int combo = rem / a.group;
-  int cj = sc * a.group + (rem - combo * a.group);
-  const int full = (a.nchunks / a.group) * a.group;               // last, shorter superchunk
-  if (sc * a.group >= full) {
-    const int tail = a.nchunks - full;
-    const int r2 = blockIdx.x - (full / a.group) * per_super;
-    combo = r2 / tail;
-    cj = full + (r2 - combo * tail);
-  }
-  if (cj >= a.nchunks || combo >= a.ncombos) return;
+  int combo, cj;
+  if (!pair_block_item(a, &combo, &cj)) return;
   {
     const u32x4 *src = reinterpret_cast<const u32x4 *>(a.image + (size_t)combo * PAIR_BITMAP_WORDS);
     u32x4 *dst = reinterpret_cast<u32x4 *>(lds);
@@ -850,19 +847,8 @@ __global__ __launch_bounds__(PAIR_THREADS) void pm_pair_scan(PairArgs a) {
 template <int FLOOR>
 __global__ __launch_bounds__(PAIR_THREADS) void pm_pair_edit_scan(PairArgs a) {
   extern __shared__ uint32_t lds[];
-  const int per_super = a.group * a.ncombos;
-  const int sc = blockIdx.x / per_super;
-  const int rem = blockIdx.x - sc * per_super;
-  int var = rem / a.group;
-  int cj = sc * a.group + (rem - var * a.group);
-  const int full = (a.nchunks / a.group) * a.group;
-  if (sc * a.group >= full) {
-    const int tail = a.nchunks - full;
-    const int r2 = blockIdx.x - (full / a.group) * per_super;
-    var = r2 / tail;
-    cj = full + (r2 - var * tail);
-  }
-  if (cj >= a.nchunks || var >= a.ncombos) return;
+  int var, cj;
+  if (!pair_block_item(a, &var, &cj)) return;
   // variants in table order: (0,1,0); (0,2,-1..1); (0,3,-2..2); (1,2,0); (1,3,-1..1); (2,3,0)
   const int table = edit_variant_table(var);
   {
@@ -1171,6 +1157,11 @@ ScanGeometry pair_geometry(const PairDevice &d, int64_t begin, int64_t end) {
   g.nseg = (int)(c_hi - c_lo + 1);
   g.threads = PAIR_THREADS;
   g.blocks = g.nseg * d.ncombos;
+  // blockIdx -> (combo, chunk), pm_workmap.h.  The XCD superchunk map keeps each XCD's 32 CUs on one combo for several
+  // workgroups each (3 Gbp: 1431 chunks of 2 Mi at -K 2, 2862 of 1 Mi at -K 1: 14.7 -> 13.5 ms, 5.03 -> 4.82 ms; DESIGN
+  // §4.0).  Smaller ranges (pm_scan pieces, windowed pieces, position shards) keep the superchunk map.
+  g.work_map = g.nseg >= PAIR_XCD_MIN_CHUNKS ? PAIR_MAP_XCD_SUPERCHUNK : PAIR_MAP_SUPERCHUNK;
+  if (d.knobs.pair_map >= 0) g.work_map = d.knobs.pair_map;        // PM_PAIR_MAP (A/B runs, tests)
   return g;
 }
 
@@ -1183,7 +1174,12 @@ hipError_t pair_launch(const PairDevice &d, const uint8_t *d_text, const uint32_
   if (floor_mode && (d.k != 2 || d.ncombos != 6)) return hipErrorInvalidValue;
   if (floor_mode == 3 && (!seed_out || !seed_count)) return hipErrorInvalidValue;
   ScanGeometry g = pair_geometry(d, begin, end);
-  if (floor_mode) g.blocks = g.nseg * 14;
+  if (floor_mode) {
+    g.blocks = g.nseg * 14;
+    // the edit plan keeps the superchunk map: its 14 tests share 6 tables in runs of 1 - 5 tests, so an XCD mostly holds one
+    // table already, and the XCD superchunk map's pieces of tests of unequal cost took 4 % longer
+    if (d.knobs.pair_map < 0) g.work_map = PAIR_MAP_SUPERCHUNK;
+  }
   if (geo_out) *geo_out = g;
   if (g.blocks <= 0 || d.np == 0) return hipSuccess;
   PairArgs a;
@@ -1193,6 +1189,7 @@ hipError_t pair_launch(const PairDevice &d, const uint8_t *d_text, const uint32_
   a.chunk_len = g.seg_len; a.chunk0 = begin / g.seg_len; a.nchunks = g.nseg; a.ncombos = d.ncombos;
   a.group = 256;
   if (d.knobs.seed_group > 0) a.group = d.knobs.seed_group;
+  a.work_map = g.work_map;
   a.k = d.k; a.eos_code = d.eos_code;
   a.debug = d.knobs.seed_debug;
   for (int c = 0; c < PAIR_MAX_COMBOS; ++c) { a.fa[c] = d.fa[c]; a.fb[c] = d.fb[c]; a.first_off[c] = (uint32_t)d.first_off[c]; }
