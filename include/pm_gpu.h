@@ -7,7 +7,7 @@
  * All functions return PM_OK (0) or a negative pm_status; pm_last_error() has the text.
  * A handle is owned by one host thread (the reference is single-threaded).
  *
- * Data flow:  pm_create -> pm_add_pattern xN -> pm_init[_device] -> pm_scan ... -> pm_destroy
+ * Data flow:  pm_create -> pm_add_pattern xN -> pm_init[_device|_windowed|_packed] -> pm_scan ... -> pm_destroy
  * Multi-GPU:  each rank pm_scan_candidates() on its shard of the stream; filter_bitvec option sets
  *             then pm_finalize_device_owned() on the same rank and the final hits are gathered
  *             (RCCL) in rank order; for the others the candidate records are gathered and one
@@ -119,9 +119,38 @@ int pm_init_device(pm_handle *h, const void *d_text, int64_t n, const uint8_t *t
 int pm_init_windowed(pm_handle *h, const uint8_t *text, int64_t n, const uint8_t *table, int32_t table_len,
                      int64_t window_bytes);
 
+/* PatternMatch::init for a stream held bit-packed in host memory (<db>.sqz, char_io.t:18-214): n codes of `bits` bits,
+ * MSB first (code c in bits [c*bits, (c+1)*bits) of the packed bytes, bit 0 being the MSB of byte 0); `table` as for
+ * pm_init and mandatory (a packed stream is always a normalized one), table_len <= 2^bits.  window_bytes == 0: the
+ * packed bytes are uploaded as they are and unpacked in HBM (then exactly a pm_init handle, except that it keeps no host
+ * text: the host stage decodes the windows it verifies from the packed bytes).  window_bytes > 0: as pm_init_windowed
+ * (window_bytes counts stream positions, as there), but every window crosses PCIe packed and is unpacked into its slot;
+ * the HBM held for the stream is at most 2*(1.25 + bits/8)*(W + 2G) + 2 KiB for a window of W bytes with guard margins
+ * of G (three buffers per slot: text, 2-bit words, packed bytes).  `packed` is borrowed until pm_destroy in both forms. */
+int pm_init_packed(pm_handle *h, const uint8_t *packed, int64_t packed_bytes, int32_t bits, int64_t n,
+                   const uint8_t *table, int32_t table_len, int64_t window_bytes);
+
+/* Unpack the n codes that start at bit 0 of d_packed (8-byte aligned; a window that starts at code `first`, a multiple
+ * of 64, passes base + first*bits/8) into d_text and, when d_words != NULL, the 2-bit words d_words[0..ceil(n/16))
+ * that the seed family reads (dword i = bases 16i..16i+15, base j in bits 2j, value code & 3, zero past n).  d_text is
+ * 16-byte aligned and holds n rounded up to a multiple of 16 bytes: the bytes from n up to there are written zero,
+ * nothing beyond.  Loads stay inside packed_bytes.  Enqueued on hip_stream (a hipStream_t, NULL = default stream).
+ * The reference's reader is Compressed<>::getnch (char_io.t:104-160). */
+int pm_unpack_device(const void *d_packed, int64_t packed_bytes, int32_t bits, int64_t n,
+                     void *d_text, void *d_words, void *hip_stream);
+
+/* GPU-free helpers (the host stage's own reader, and its inverse for callers and tests), eight codes at a time:
+ * pm_unpack_codes writes codes first .. first+n-1 of the packed bytes to out[0..n); pm_pack_codes writes n codes to
+ * out[0..ceil(n*bits/8)), zero fill bits in the last byte and zero bytes up to out_bytes (PM_E_INVALID when a code does
+ * not fit `bits` bits or out_bytes is too small). */
+int pm_unpack_codes(const uint8_t *packed, int64_t packed_bytes, int32_t bits, int64_t first, int64_t n, uint8_t *out);
+int pm_pack_codes(const uint8_t *codes, int64_t n, int32_t bits, uint8_t *out, int64_t out_bytes);
+
 /* Introspection for tests and measurement: out[0] the window size in use (0: the whole stream is resident), out[1] the
- * HBM bytes held now for stream text plus its 2-bit words, out[2] the peak of out[1] since init, out[3] stream bytes
- * uploaded since init, out[4] window loads since init (pm_init: 1, pm_init_device: 0).  n <= 5 values are written. */
+ * HBM bytes held now for stream text plus its 2-bit words (and, on a pm_init_packed handle, the packed bytes in HBM while
+ * they exist), out[2] the peak of out[1] since init, out[3] stream bytes that crossed PCIe since init (packed bytes for
+ * a packed handle), out[4] window loads since init (pm_init: 1, pm_init_device: 0), out[5] bits per code of the host form
+ * (0: one byte per code).  n <= 6 values are written. */
 int pm_stream_residency(const pm_handle *h, int64_t *out, int n);
 
 /* Free and total HBM of `device` (hipMemGetInfo), for a caller that picks between pm_init and pm_init_windowed: the
@@ -167,7 +196,8 @@ int pm_set_capacity(pm_handle *h, size_t max_candidates);
  * exact_halves.cc:140-190).  flags: PM_FINALIZE_LAST flushes deferred clusters (no more input),
  * PM_FINALIZE_SORTED orders the output by (end,pid) (otherwise unspecified, like the emission
  * order of the reference engines).  Text, where the verify needs it, comes from the host pointer
- * given to pm_init or, for pm_init_device, from windows fetched out of HBM. */
+ * given to pm_init, decoded from the packed bytes given to pm_init_packed or, for pm_init_device, from
+ * windows fetched out of HBM. */
 #define PM_FINALIZE_LAST 1
 #define PM_FINALIZE_SORTED 2
 int pm_finalize(pm_handle *h, const pm_hit *cands, size_t n, int64_t scanned_to, int flags,
@@ -282,7 +312,8 @@ int pm_measure_pair_edit_floor(pm_handle *h, int mode, float *ms, uint64_t *susp
 
 /* Duration of the one-off re-encoding of the stream to 2 bits per base that pm_init[_device] runs
  * for the seed kernel family (0 for the bit-parallel family): not part of a scan, reported so that a
- * reader can add it to a single cold pass. */
+ * reader can add it to a single cold pass.  On a resident pm_init_packed handle: the unpack kernel, which
+ * writes the bytes and the 2-bit words in one pass (either kernel family). */
 int pm_pack_time(pm_handle *h, float *ms);
 
 /* pick_pattern_index's automatic choice (select.cc:101-141) without a handle. */

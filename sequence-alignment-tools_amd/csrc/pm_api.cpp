@@ -47,6 +47,7 @@ constexpr int64_t WIN_UP_CHUNK = (int64_t)4 << 20;
 struct WinSlot {
   uint8_t *bytes = nullptr;
   uint32_t *words = nullptr;
+  uint8_t *pk = nullptr;              // pm_init_packed: the window's bit-packed bytes as they crossed PCIe (unpacked into bytes / words)
   int64_t cap = 0, lo = 0, hi = 0;
   bool loaded = false, used_rec = false;
   hipEvent_t ready = nullptr;         // upload + packing done (recorded on the upload stream)
@@ -65,6 +66,11 @@ struct pm_handle {
   bool host_only = false;             // pm_init_host: host stage only, no stream on the device
 
   const uint8_t *h_text = nullptr;
+  // pm_init_packed: the host form of the stream is bit-packed (pk_bits bits per code, MSB first) and h_text is NULL
+  const uint8_t *h_packed = nullptr;
+  int64_t h_packed_bytes = 0;
+  int pk_bits = 0;
+  int64_t pk_peak_extra = 0;          // resident form: HBM the packed staging buffer held during init
   const uint8_t *d_text = nullptr;
   bool own_d_text = false;
   int64_t n = 0;
@@ -208,6 +214,102 @@ static int hipfail(pm_handle *h, hipError_t e, const char *what) {
   return fail(h, PM_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
 #define HIP_TRY(h, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return hipfail((h), e_, #expr); } while (0)
+
+// ---- bit-packed codes on the host (<db>.sqz: char_io.t:18-214) ---------------------------------
+// Code c sits in bits [c*bits, (c+1)*bits) of the packed bytes, bit 0 being the MSB of byte 0.  Eight codes are exactly
+// `bits` bytes, so both directions move eight codes through one 64-bit word with constant shifts.
+namespace {
+
+template <int BITS> void unpack8(const uint8_t *p, uint8_t *out) {
+  uint64_t w = 0;
+  for (int i = 0; i < BITS; ++i) w = (w << 8) | p[i];
+  for (int j = 0; j < 8; ++j) out[j] = (uint8_t)((w >> (BITS * (7 - j))) & ((1u << BITS) - 1u));
+}
+template <int BITS> uint32_t pack8(const uint8_t *c, uint8_t *p) {
+  uint64_t w = 0;
+  uint32_t seen = 0;
+  for (int j = 0; j < 8; ++j) { w = (w << BITS) | c[j]; seen |= c[j]; }
+  for (int i = 0; i < BITS; ++i) p[i] = (uint8_t)(w >> (8 * (BITS - 1 - i)));
+  return seen;
+}
+template <int BITS> void unpack_run(const uint8_t *p, int64_t groups, uint8_t *out) {
+  for (int64_t g = 0; g < groups; ++g) unpack8<BITS>(p + g * BITS, out + 8 * g);
+}
+template <int BITS> uint32_t pack_run(const uint8_t *c, int64_t groups, uint8_t *p) {
+  uint32_t seen = 0;
+  for (int64_t g = 0; g < groups; ++g) seen |= pack8<BITS>(c + 8 * g, p + g * BITS);
+  return seen;
+}
+// one code at any position: the two bytes that hold it (bits <= 8: a code spans at most two)
+inline uint8_t code_at(const uint8_t *p, int64_t packed_bytes, int bits, int64_t c) {
+  const int64_t bit = c * bits, b = bit >> 3;
+  const uint32_t w = ((uint32_t)p[b] << 8) | (b + 1 < packed_bytes ? p[b + 1] : 0u);
+  return (uint8_t)((w >> (16 - bits - (int)(bit & 7))) & ((1u << bits) - 1u));
+}
+
+}  // namespace
+
+extern "C" int pm_unpack_codes(const uint8_t *packed, int64_t packed_bytes, int32_t bits, int64_t first, int64_t n, uint8_t *out) {
+  if (bits < 1 || bits > 8 || first < 0 || n < 0 || packed_bytes < 0 || packed_bytes > ((int64_t)1 << 59)) return PM_E_INVALID;
+  if (n == 0) return PM_OK;
+  if (!packed || !out || first > packed_bytes * 8 / bits - n) return PM_E_INVALID;
+  int64_t i = 0;
+  for (; i < n && ((first + i) & 7); ++i) out[i] = code_at(packed, packed_bytes, bits, first + i);
+  const int64_t groups = (n - i) / 8;
+  const uint8_t *p = packed + (first + i) / 8 * bits;
+  switch (bits) {
+    case 1: unpack_run<1>(p, groups, out + i); break;
+    case 2: unpack_run<2>(p, groups, out + i); break;
+    case 3: unpack_run<3>(p, groups, out + i); break;
+    case 4: unpack_run<4>(p, groups, out + i); break;
+    case 5: unpack_run<5>(p, groups, out + i); break;
+    case 6: unpack_run<6>(p, groups, out + i); break;
+    case 7: unpack_run<7>(p, groups, out + i); break;
+    case 8: unpack_run<8>(p, groups, out + i); break;
+  }
+  for (i += 8 * groups; i < n; ++i) out[i] = code_at(packed, packed_bytes, bits, first + i);
+  return PM_OK;
+}
+
+extern "C" int pm_pack_codes(const uint8_t *codes, int64_t n, int32_t bits, uint8_t *out, int64_t out_bytes) {
+  if (bits < 1 || bits > 8 || n < 0 || out_bytes < 0 || n > ((int64_t)1 << 59)) return PM_E_INVALID;
+  const int64_t need = (n * bits + 7) / 8;
+  if (out_bytes < need || (n > 0 && (!codes || !out))) return PM_E_INVALID;
+  const int64_t groups = n / 8;
+  uint32_t seen = 0;
+  switch (bits) {
+    case 1: seen = pack_run<1>(codes, groups, out); break;
+    case 2: seen = pack_run<2>(codes, groups, out); break;
+    case 3: seen = pack_run<3>(codes, groups, out); break;
+    case 4: seen = pack_run<4>(codes, groups, out); break;
+    case 5: seen = pack_run<5>(codes, groups, out); break;
+    case 6: seen = pack_run<6>(codes, groups, out); break;
+    case 7: seen = pack_run<7>(codes, groups, out); break;
+    case 8: seen = pack_run<8>(codes, groups, out); break;
+  }
+  if (n > 8 * groups) {                                             // the last, partial group: fill bits are zero
+    uint8_t last[8] = {0, 0, 0, 0, 0, 0, 0, 0}, bytes[8];
+    for (int64_t i = 8 * groups; i < n; ++i) { last[i - 8 * groups] = codes[i]; seen |= codes[i]; }
+    uint64_t w = 0;
+    for (int j = 0; j < 8; ++j) w = (w << bits) | (last[j] & ((1u << bits) - 1u));
+    for (int i = 0; i < bits; ++i) bytes[i] = (uint8_t)(w >> (8 * (bits - 1 - i)));
+    memcpy(out + groups * bits, bytes, (size_t)(need - groups * bits));
+  }
+  if (out_bytes > need) memset(out + need, 0, (size_t)(out_bytes - need));
+  return (seen >> bits) ? PM_E_INVALID : PM_OK;                     // a code that does not fit `bits` bits
+}
+
+// Where the host stage reads stream codes from: the caller's bytes (pm_init, pm_init_windowed, pm_init_host), the caller's
+// packed bytes (pm_init_packed), or -- no host form: pm_init_device -- the resident text in HBM.
+static bool has_host_form(const pm_handle *h) { return h->h_text || h->h_packed; }
+static int host_codes(pm_handle *h, int64_t pos, int64_t len, uint8_t *dst) {
+  if (len <= 0) return PM_OK;
+  if (h->h_text) memcpy(dst, h->h_text + pos, (size_t)len);
+  else if (h->h_packed) {
+    if (pm_unpack_codes(h->h_packed, h->h_packed_bytes, h->pk_bits, pos, len, dst) != PM_OK) return fail(h, PM_E_INVALID, "packed stream: read outside the packed bytes");
+  } else HIP_TRY(h, hipMemcpy(dst, h->d_text + pos, (size_t)len, hipMemcpyDeviceToHost));
+  return PM_OK;
+}
 
 // ---- pick_pattern_index, automatic branch (reference select.cc:31-141, NOPRIMEGEN, -x 0) -----
 extern "C" int pm_pick_semantics(int32_t alphabet_size, int32_t acgt_normalized, int32_t k, int32_t wildcards,
@@ -813,15 +915,20 @@ static hipError_t upload_stream(int device, void *d, const uint8_t *text, size_t
 
 // The seed family's first stage reads the stream at 2 bits per base (pm_seed.hip pack_stream): one
 // pass over the stream per pm_init, on the handle's stream, after the bytes are in HBM.
-static int ensure_packed(pm_handle *h) {
-  if (h->kern != PM_KERNEL_SEED) return PM_OK;
+static int ensure_words(pm_handle *h) {
   const size_t words = (size_t)((h->n + 15) / 16);
   if (!h->d_packed || h->packed_cap < words) {
     if (h->d_packed) (void)hipFree(h->d_packed);
     h->d_packed = nullptr;
     h->packed_cap = words;
-    HIP_TRY(h, hipMalloc((void **)&h->d_packed, (words + 128) * sizeof(uint32_t)));   // + padding the scan kernels' block prefetch may read (zeroed below)
+    HIP_TRY(h, hipMalloc((void **)&h->d_packed, (words + 128) * sizeof(uint32_t)));   // + padding the scan kernels' block prefetch may read (zeroed by the caller)
   }
+  return PM_OK;
+}
+static int ensure_packed(pm_handle *h) {
+  if (h->kern != PM_KERNEL_SEED) return PM_OK;
+  const size_t words = (size_t)((h->n + 15) / 16);
+  { const int rc = ensure_words(h); if (rc) return rc; }
   if (h->n >= 16) HIP_TRY(h, pack_stream(h->d_text, 16, h->sd.ascii, h->d_packed + words + 64, 1, h->stream));   // the kernel's code is resident before the timed pass
   HIP_TRY(h, hipStreamSynchronize(h->stream));                      // table uploads of this init are not part of the figure
   HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
@@ -872,11 +979,15 @@ static int64_t win_piece_cap(const pm_handle *h) { return h->win - h->win_back -
 static size_t slot_bytes(const pm_handle *h, int64_t cap) { return (size_t)(cap + 2 * h->win_guard); }
 static size_t slot_words(const pm_handle *h, int64_t cap) { return (size_t)((cap + 2 * h->win_guard) / 16 + 128); }
 
+// bytes of a slot's packed buffer: `cap` codes (cap is a multiple of 64: whole bytes) and one 8-byte word of slack
+static size_t slot_packed(const pm_handle *h, int64_t cap) { return (size_t)(cap / 8 * h->pk_bits + 8); }
+
 static void win_account(pm_handle *h) {
   int64_t held = 0;
   for (const WinSlot &s : h->slot) {
     if (s.bytes) held += (int64_t)slot_bytes(h, s.cap);
     if (s.words) held += (int64_t)slot_words(h, s.cap) * 4;
+    if (s.pk) held += (int64_t)slot_packed(h, s.cap);
   }
   h->win_held = held;
   h->win_peak = std::max(h->win_peak, held);
@@ -890,6 +1001,7 @@ static void win_release(pm_handle *h) {
   for (WinSlot &s : h->slot) {
     if (s.bytes) (void)hipFree(s.bytes);
     if (s.words) (void)hipFree(s.words);
+    if (s.pk) (void)hipFree(s.pk);
     if (s.ready) (void)hipEventDestroy(s.ready);
     if (s.used) (void)hipEventDestroy(s.used);
     s = WinSlot();
@@ -911,7 +1023,9 @@ static void win_release(pm_handle *h) {
   h->win_held = h->win_peak = h->win_uploaded = h->win_loads = 0;
 }
 
-// Upload stream text [lo, hi) into slot si (not the bound one) and pack it.  The host copies chunks into pinned staging
+// Upload stream text [lo, hi) into slot si (not the bound one) and pack it.  On a pm_init_packed handle the bytes that cross
+// PCIe are the window's slice of the packed stream (lo is a multiple of 64 codes, so the slice starts on a whole byte, 8-byte
+// aligned): they go into the slot's packed buffer and one kernel on the upload stream unpacks them into text and words.  The host copies chunks into pinned staging
 // buffers, up to WIN_UP_THREADS threads on streams of their own (upload_stream's pattern); the copies wait for the last
 // kernel that read the slot (its `used` event), the packing runs on the upload stream behind them and `ready` marks the
 // end.  Returns once the last chunk is staged: the copies of the last chunks still run while the caller goes on.
@@ -920,6 +1034,7 @@ static int win_load(pm_handle *h, int si, int64_t lo, int64_t hi) {
   const int64_t len = hi - lo;
   const int64_t G = h->win_guard;
   const bool packed = h->kern == PM_KERNEL_SEED;
+  const int pkb = h->pk_bits;                                       // > 0: the host form is bit-packed
   if (!s.ready) HIP_TRY(h, hipEventCreateWithFlags(&s.ready, hipEventDisableTiming));
   if (!s.used) HIP_TRY(h, hipEventCreateWithFlags(&s.used, hipEventDisableTiming));
   if (!h->up_stream) HIP_TRY(h, hipStreamCreateWithFlags(&h->up_stream, hipStreamNonBlocking));
@@ -930,13 +1045,14 @@ static int win_load(pm_handle *h, int si, int64_t lo, int64_t hi) {
       for (int q = 0; q < 2; ++q) HIP_TRY(h, hipEventCreateWithFlags(&h->stage_ev[t][q], hipEventDisableTiming));
     }
   }
-  if (!s.bytes || s.cap < len || (packed && !s.words)) {           // first use, or a carried chain that needs more than a window
+  if (!s.bytes || s.cap < len || (packed && !s.words) || (pkb && !s.pk)) {           // first use, or a carried chain that needs more than a window
     if (s.used_rec) HIP_TRY(h, hipEventSynchronize(s.used));
     for (int t = 0; t < WIN_UP_THREADS; ++t) if (h->stage_st[t]) HIP_TRY(h, hipStreamSynchronize(h->stage_st[t]));   // (an earlier upload into it)
     HIP_TRY(h, hipStreamSynchronize(h->up_stream));
     if (s.bytes) (void)hipFree(s.bytes);
     if (s.words) (void)hipFree(s.words);
-    s.bytes = nullptr; s.words = nullptr;
+    if (s.pk) (void)hipFree(s.pk);
+    s.bytes = nullptr; s.words = nullptr; s.pk = nullptr;
     s.cap = std::max(h->win, (len + 63) / 64 * 64);
     HIP_TRY(h, hipMalloc((void **)&s.bytes, slot_bytes(h, s.cap)));
     HIP_TRY(h, hipMemsetAsync(s.bytes, 0, slot_bytes(h, s.cap), h->up_stream));
@@ -944,30 +1060,37 @@ static int win_load(pm_handle *h, int si, int64_t lo, int64_t hi) {
       HIP_TRY(h, hipMalloc((void **)&s.words, slot_words(h, s.cap) * 4));
       HIP_TRY(h, hipMemsetAsync(s.words, 0, slot_words(h, s.cap) * 4, h->up_stream));
     }
+    if (pkb) HIP_TRY(h, hipMalloc((void **)&s.pk, slot_packed(h, s.cap)));
     win_account(h);
     HIP_TRY(h, hipStreamSynchronize(h->up_stream));
   }
   s.loaded = false;
   uint8_t *dst = s.bytes + G;
-  const uint8_t *src = h->h_text + lo;
-  const int T = (int)std::min<int64_t>(WIN_UP_THREADS, std::max<int64_t>(1, len / (4 * WIN_UP_CHUNK)));
+  // what the staging threads copy, and where to: the text itself into the slot, or its packed slice into the packed buffer
+  const int64_t plo = pkb ? lo / 8 * pkb : 0;
+  const int64_t up_len = pkb ? std::min(h->h_packed_bytes, (hi * pkb + 7) / 8) - plo : len;
+  const uint8_t *src = pkb ? h->h_packed + plo : h->h_text + lo;
+  uint8_t *up_dst = pkb ? s.pk : dst;
+  const int T = (int)std::min<int64_t>(WIN_UP_THREADS, std::max<int64_t>(1, up_len / (4 * WIN_UP_CHUNK)));
   for (int t = 0; t < T; ++t)
     for (int q = 0; q < 2; ++q)
       if (!h->stage[t][q]) HIP_TRY(h, hipHostMalloc((void **)&h->stage[t][q], (size_t)WIN_UP_CHUNK, hipHostMallocDefault));
-  const int64_t per = ((len + T - 1) / T + WIN_UP_CHUNK - 1) / WIN_UP_CHUNK * WIN_UP_CHUNK;
+  const int64_t per = ((up_len + T - 1) / T + WIN_UP_CHUNK - 1) / WIN_UP_CHUNK * WIN_UP_CHUNK;
   std::vector<hipError_t> errs((size_t)T, hipSuccess);
   const bool wait_used = s.used_rec;
   auto work = [&](int t) {
     hipError_t e = hipSetDevice(h->cfg.device);
-    const int64_t a = std::min(len, (int64_t)t * per), b = std::min(len, a + per);
-    if (e == hipSuccess && wait_used) e = hipStreamWaitEvent(h->stage_st[t], s.used, 0);
+    const int64_t a = std::min(up_len, (int64_t)t * per), b = std::min(up_len, a + per);
+    // the text is overwritten once its last reader is done; the packed buffer once the unpack of the slot's last load is
+    if (e == hipSuccess && pkb) e = hipStreamWaitEvent(h->stage_st[t], s.ready, 0);
+    else if (e == hipSuccess && wait_used) e = hipStreamWaitEvent(h->stage_st[t], s.used, 0);
     int q = 0;
     for (int64_t off = a; off < b && e == hipSuccess; off += WIN_UP_CHUNK, q ^= 1) {
       const size_t m = (size_t)std::min<int64_t>(WIN_UP_CHUNK, b - off);
       e = hipEventSynchronize(h->stage_ev[t][q]);                   // the copy that last used this buffer is done
       if (e != hipSuccess) break;
       memcpy(h->stage[t][q], src + off, m);
-      e = hipMemcpyAsync(dst + off, h->stage[t][q], m, hipMemcpyHostToDevice, h->stage_st[t]);
+      e = hipMemcpyAsync(up_dst + off, h->stage[t][q], m, hipMemcpyHostToDevice, h->stage_st[t]);
       if (e == hipSuccess) e = hipEventRecord(h->stage_ev[t][q], h->stage_st[t]);
     }
     if (e == hipSuccess) e = hipEventRecord(h->stage_done[t], h->stage_st[t]);
@@ -981,8 +1104,14 @@ static int win_load(pm_handle *h, int si, int64_t lo, int64_t hi) {
   }
   for (hipError_t e : errs) if (e != hipSuccess) return hipfail(h, e, "window upload");
   for (int t = 0; t < T; ++t) HIP_TRY(h, hipStreamWaitEvent(h->up_stream, h->stage_done[t], 0));
+  if (pkb) {
+    if (wait_used) HIP_TRY(h, hipStreamWaitEvent(h->up_stream, s.used, 0));
+    HIP_TRY(h, unpack_stream(s.pk, up_len, pkb, len, h->sd.ascii, dst, packed ? s.words + G / 16 : nullptr, h->up_stream));
+  }
   if (hi == h->n) HIP_TRY(h, hipMemsetAsync(dst + len, 0, 64, h->up_stream));     // the zero bytes past the end of the stream
-  if (packed) {
+  if (packed && pkb) {
+    if (hi == h->n) HIP_TRY(h, hipMemsetAsync(s.words + G / 16 + (len + 15) / 16, 0, 128 * sizeof(uint32_t), h->up_stream));
+  } else if (packed) {
     const int64_t nw = (len + 15) / 16;
     uint32_t *wdst = s.words + G / 16;
     HIP_TRY(h, pack_stream(dst, len, h->sd.ascii, wdst, nw, h->up_stream));       // (lo is a multiple of 64: words rebase like bytes)
@@ -990,7 +1119,7 @@ static int win_load(pm_handle *h, int si, int64_t lo, int64_t hi) {
   }
   HIP_TRY(h, hipEventRecord(s.ready, h->up_stream));
   s.lo = lo; s.hi = hi; s.loaded = true;
-  h->win_uploaded += len; ++h->win_loads;
+  h->win_uploaded += up_len; ++h->win_loads;
   return PM_OK;
 }
 
@@ -1052,7 +1181,7 @@ extern "C" int pm_init(pm_handle *h, const uint8_t *text, int64_t n, const uint8
   void *d = nullptr;
   HIP_TRY(h, hipMalloc(&d, (size_t)(n > 0 ? n : 1) + 16));
   const double ti1 = now_ms();
-  h->d_text = (const uint8_t *)d; h->own_d_text = true; h->h_text = text; h->n = n; h->stream = nullptr; h->host_only = false;
+  h->d_text = (const uint8_t *)d; h->own_d_text = true; h->h_text = text; h->n = n; h->stream = nullptr; h->host_only = false; h->h_packed = nullptr; h->h_packed_bytes = 0; h->pk_bits = 0; h->pk_peak_extra = 0;
   // the stream crosses PCIe (≈0.3 s for 3 GB of pageable memory) while this thread builds the
   // pattern tables; raw streams with wildcards look at the stream on the device first, so they wait
   const bool overlap = n > ((int64_t)1 << 24) && !(!table && h->cfg.wildcards);
@@ -1083,7 +1212,7 @@ extern "C" int pm_init_host(pm_handle *h, const uint8_t *text, int64_t n, const 
   HIP_TRY(h, hipSetDevice(h->cfg.device));
   win_release(h);
   if (h->own_d_text && h->d_text) (void)hipFree((void *)h->d_text);
-  h->d_text = nullptr; h->own_d_text = false; h->h_text = text; h->n = n; h->stream = nullptr;
+  h->d_text = nullptr; h->own_d_text = false; h->h_text = text; h->n = n; h->stream = nullptr; h->h_packed = nullptr; h->h_packed_bytes = 0; h->pk_bits = 0; h->pk_peak_extra = 0;
   h->host_only = true;
   return init_common(h, table, table_len);
 }
@@ -1095,22 +1224,30 @@ extern "C" int pm_init_device(pm_handle *h, const void *d_text, int64_t n, const
   HIP_TRY(h, hipSetDevice(h->cfg.device));
   win_release(h);
   if (h->own_d_text && h->d_text) (void)hipFree((void *)h->d_text);
-  h->d_text = (const uint8_t *)d_text; h->own_d_text = false; h->h_text = nullptr; h->n = n; h->host_only = false;
+  h->d_text = (const uint8_t *)d_text; h->own_d_text = false; h->h_text = nullptr; h->n = n; h->host_only = false; h->h_packed = nullptr; h->h_packed_bytes = 0; h->pk_bits = 0; h->pk_peak_extra = 0;
   h->stream = (hipStream_t)hip_stream;
   const int rc = init_common(h, table, table_len);
   if (rc) return rc;
   return ensure_packed(h);
 }
 
+// the part pm_init_windowed and the windowed form of pm_init_packed share: the host form is set by the caller
+static int init_window_ring(pm_handle *h, int64_t n, const uint8_t *table, int32_t table_len, int64_t window_bytes);
+
 extern "C" int pm_init_windowed(pm_handle *h, const uint8_t *text, int64_t n, const uint8_t *table, int32_t table_len,
                                 int64_t window_bytes) {
   if (!h || (!text && n > 0) || n < 0 || window_bytes <= 0) return fail(h, PM_E_INVALID, "pm_init_windowed: bad arguments");
   HIP_TRY(h, hipSetDevice(h->cfg.device));
+  h->h_text = text; h->h_packed = nullptr; h->h_packed_bytes = 0; h->pk_bits = 0; h->pk_peak_extra = 0;
+  return init_window_ring(h, n, table, table_len, window_bytes);
+}
+
+static int init_window_ring(pm_handle *h, int64_t n, const uint8_t *table, int32_t table_len, int64_t window_bytes) {
   win_release(h);
   if (h->own_d_text && h->d_text) (void)hipFree((void *)h->d_text);
   if (h->d_packed) (void)hipFree(h->d_packed);                      // (a resident init's 2-bit copy)
   h->d_packed = nullptr; h->packed_cap = 0;
-  h->d_text = nullptr; h->own_d_text = false; h->h_text = text; h->n = n; h->stream = nullptr; h->host_only = false;
+  h->d_text = nullptr; h->own_d_text = false; h->n = n; h->stream = nullptr; h->host_only = false;
   stream_halo(h, &h->win_back, &h->win_fwd);
   // guard: the halo plus the longest aligned run a kernel starts in front of `begin` (bit-parallel segment: 4 Mi positions,
   // seed / pair chunk: 2 Mi, or what the test knobs set) and the seed kernels' prefetch of four blocks of 1024 bases ahead
@@ -1122,18 +1259,82 @@ extern "C" int pm_init_windowed(pm_handle *h, const uint8_t *text, int64_t n, co
   return init_common(h, table, table_len);
 }
 
+extern "C" int pm_init_packed(pm_handle *h, const uint8_t *packed, int64_t packed_bytes, int32_t bits, int64_t n,
+                              const uint8_t *table, int32_t table_len, int64_t window_bytes) {
+  if (!h) return PM_E_INVALID;
+  if (bits < 1 || bits > 8) return fail(h, PM_E_INVALID, "pm_init_packed: bits per code must be 1..8");
+  if (n < 0 || packed_bytes < 0 || window_bytes < 0 || packed_bytes > ((int64_t)1 << 59)) return fail(h, PM_E_INVALID, "pm_init_packed: negative size");
+  if (n > packed_bytes * 8 / bits) return fail(h, PM_E_INVALID, "pm_init_packed: n codes do not fit packed_bytes");
+  if (!packed && n > 0) return fail(h, PM_E_INVALID, "pm_init_packed: no packed bytes");
+  if (!table || table_len <= 0) return fail(h, PM_E_INVALID, "pm_init_packed: a packed stream is a normalized one and needs its table");
+  if (table_len > (1 << bits)) return fail(h, PM_E_INVALID, "pm_init_packed: the table has more symbols than codes of this width");
+  const double ti0 = now_ms();
+  HIP_TRY(h, hipSetDevice(h->cfg.device));
+  win_release(h);
+  if (window_bytes > 0) {
+    h->h_text = nullptr; h->h_packed = packed; h->h_packed_bytes = packed_bytes; h->pk_bits = bits; h->pk_peak_extra = 0;
+    return init_window_ring(h, n, table, table_len, window_bytes);
+  }
+  // resident: the packed bytes cross PCIe as they are (upload_stream, beside the pattern-table build) into a staging buffer
+  // in HBM; one kernel on the handle's stream unpacks them into the owned text and, for the seed family, its 2-bit words
+  if (h->own_d_text && h->d_text) { (void)hipFree((void *)h->d_text); h->d_text = nullptr; }
+  const int64_t up = (n * bits + 7) / 8;
+  void *d = nullptr, *d_pk = nullptr;
+  HIP_TRY(h, hipMalloc(&d, (size_t)(n > 0 ? n : 1) + 16));
+  h->d_text = (const uint8_t *)d; h->own_d_text = true; h->h_text = nullptr; h->n = n; h->stream = nullptr; h->host_only = false;
+  h->h_packed = packed; h->h_packed_bytes = packed_bytes; h->pk_bits = bits; h->pk_peak_extra = 0;
+  HIP_TRY(h, hipMalloc(&d_pk, (size_t)up + 8));
+  const double ti1 = now_ms();
+  const bool overlap = up > ((int64_t)1 << 24);
+  hipError_t copy_err = hipSuccess;
+  std::thread copier;
+  if (up > 0) {
+    if (overlap) {
+      const int dev = h->cfg.device;
+      copier = std::thread([=, &copy_err]() {
+        copy_err = hipSetDevice(dev);
+        if (copy_err == hipSuccess) copy_err = upload_stream(dev, d_pk, packed, (size_t)up);
+      });
+    } else copy_err = hipMemcpy(d_pk, packed, (size_t)up, hipMemcpyHostToDevice);
+  }
+  int rc = init_common(h, table, table_len);
+  const double ti2 = now_ms();
+  if (copier.joinable()) copier.join();
+  if (h->knobs.debug) fprintf(stderr, "[pm] init (packed, %d bits): runtime + stream buffers %.0f ms, tables %.0f ms, then %.0f ms more for the upload of %lld bytes\n", bits, ti1 - ti0, ti2 - ti1, now_ms() - ti2, (long long)up);
+  if (copy_err != hipSuccess) { (void)hipFree(d_pk); return fail(h, PM_E_HIP, std::string("pm_init_packed: stream upload: ") + hipGetErrorString(copy_err)); }
+  const bool words = h->kern == PM_KERNEL_SEED;
+  if (!rc && words) rc = ensure_words(h);
+  if (rc) { (void)hipFree(d_pk); return rc; }
+  h->pk_peak_extra = up + 8;
+  auto unpack = [&]() -> int {
+    const size_t nw = (size_t)((n + 15) / 16);
+    if (n >= 16) HIP_TRY(h, unpack_stream(d_pk, up, bits, 16, h->sd.ascii, d, words ? h->d_packed + nw + 64 : nullptr, h->stream));   // the kernel's code is resident before the timed pass
+    HIP_TRY(h, hipStreamSynchronize(h->stream));                    // table uploads of this init are not part of the figure
+    HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
+    if (words) HIP_TRY(h, hipMemsetAsync(h->d_packed + nw, 0, 128 * sizeof(uint32_t), h->stream));
+    HIP_TRY(h, unpack_stream(d_pk, up, bits, n, h->sd.ascii, d, words ? h->d_packed : nullptr, h->stream));
+    HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
+    HIP_TRY(h, hipEventSynchronize(h->ev1));
+    (void)hipEventElapsedTime(&h->pack_ms, h->ev0, h->ev1);
+    return PM_OK;
+  };
+  rc = unpack();
+  (void)hipFree(d_pk);
+  return rc;
+}
+
 extern "C" int pm_stream_residency(const pm_handle *h, int64_t *out, int n) {
   if (!h || !h->inited || !out || n < 0) return PM_E_INVALID;
-  int64_t v[5] = {0, 0, 0, 0, 0};
+  int64_t v[6] = {0, 0, 0, 0, 0, h->pk_bits};
   if (h->win) {
     v[0] = h->win; v[1] = h->win_held; v[2] = h->win_peak; v[3] = h->win_uploaded; v[4] = h->win_loads;
   } else if (!h->host_only) {                                       // the whole stream (pm_init: uploaded once; pm_init_device: the caller's)
     v[1] = (h->d_text ? (h->own_d_text ? h->n + 16 : h->n) : 0) + (h->d_packed ? (int64_t)(h->packed_cap + 128) * 4 : 0);
-    v[2] = v[1];
-    v[3] = h->own_d_text ? h->n : 0;
+    v[2] = v[1] + h->pk_peak_extra;
+    v[3] = !h->own_d_text ? 0 : h->pk_bits ? (h->n * h->pk_bits + 7) / 8 : h->n;
     v[4] = h->own_d_text ? 1 : 0;
   }
-  for (int i = 0; i < n && i < 5; ++i) out[i] = v[i];
+  for (int i = 0; i < n && i < 6; ++i) out[i] = v[i];
   return PM_OK;
 }
 
@@ -1363,8 +1564,7 @@ static int edits_start_candidates(pm_handle *h, std::vector<pm_hit> *out) {
   }
   std::vector<pm_hit> all, *extra = &all;
   uint8_t head[64] = {0};
-  if (h->h_text) memcpy(head, h->h_text, (size_t)T);
-  else HIP_TRY(h, hipMemcpy(head, h->d_text, (size_t)T, hipMemcpyDeviceToHost));
+  { const int rc = host_codes(h, 0, T, head); if (rc) return rc; }
   for (size_t j = 0; j < h->inner.size(); ++j) {
     if (j < h->in_rest.size() && h->in_rest[j]) continue;           // the residue engine reports its own
     const std::string &s = h->inner[j].s;
@@ -1413,8 +1613,7 @@ static int edits_end_candidates(pm_handle *h, std::vector<pm_hit> *extra) {
   }
   const int64_t T = std::min<int64_t>(n, 32 + k + 8);
   uint8_t tail[64] = {0};
-  if (h->h_text) memcpy(tail, h->h_text + (n - T), (size_t)T);
-  else HIP_TRY(h, hipMemcpy(tail, h->d_text + (n - T), (size_t)T, hipMemcpyDeviceToHost));
+  { const int rc = host_codes(h, n - T, T, tail); if (rc) return rc; }
   std::vector<pm_hit> all;
   for (size_t j = 0; j < h->inner.size(); ++j) {
     if (j < h->in_rest.size() && h->in_rest[j]) continue;           // the residue engine reports its own
@@ -1459,10 +1658,7 @@ static int stream_start_candidates(pm_handle *h) {
   if (!h->head_cached) {                                            // same stream, same patterns: computed once (0.3 ms per scan at 200k patterns)
   const int64_t need = std::min<int64_t>(h->n, 32);
   uint8_t head[32] = {0};
-  if (need > 0) {
-    if (h->h_text) memcpy(head, h->h_text, (size_t)need);
-    else HIP_TRY(h, hipMemcpy(head, h->d_text, (size_t)need, hipMemcpyDeviceToHost));
-  }
+  { const int rc = host_codes(h, 0, need, head); if (rc) return rc; }
   std::vector<pm_hit> &extra = h->head_cache;
   extra.clear();
   for (size_t j = 0; j < h->inner.size(); ++j) {
@@ -1519,10 +1715,7 @@ static int stream_end_overhang_candidates(pm_handle *h, bool bases) {
     all.clear();
     const int64_t need = std::min<int64_t>(n, 32);
     uint8_t tail[32] = {0};                                         // tail[32 - need .. 32) = the last `need` characters
-    if (need > 0) {
-      if (h->h_text) memcpy(tail + 32 - need, h->h_text + (n - need), (size_t)need);
-      else HIP_TRY(h, hipMemcpy(tail + 32 - need, h->d_text + (n - need), (size_t)need, hipMemcpyDeviceToHost));
-    }
+    { const int rc = host_codes(h, n - need, need, tail + 32 - need); if (rc) return rc; }
     auto differs = [&](unsigned char pc, int code) -> bool {
       if (h->cfg.wildcards) return acgt_of(pc).find((char)h->alpha.ch[code]) == std::string::npos;
       return code != h->alpha.nch[pc];
@@ -1701,13 +1894,7 @@ static int scan_wait_once(pm_handle *h, size_t *n_out) {
       const int64_t n = h->n, E = std::min<int64_t>(n, 56);
       if (!h->edge_cached) {                                        // same stream, same patterns: computed once
         uint8_t edge[2][64] = {{0}, {0}};
-        if (E > 0) {
-          if (h->h_text) { memcpy(edge[0], h->h_text, (size_t)E); memcpy(edge[1], h->h_text + (n - E), (size_t)E); }
-          else {
-            HIP_TRY(h, hipMemcpy(edge[0], h->d_text, (size_t)E, hipMemcpyDeviceToHost));
-            HIP_TRY(h, hipMemcpy(edge[1], h->d_text + (n - E), (size_t)E, hipMemcpyDeviceToHost));
-          }
-        }
+        { int rc = host_codes(h, 0, E, edge[0]); if (!rc) rc = host_codes(h, n - E, E, edge[1]); if (rc) return rc; }
         h->edge_cache.clear();
         for (size_t j = 0; j < h->pats.size(); ++j) {
           const Pattern &p = h->pats[j];
@@ -1867,7 +2054,7 @@ extern "C" int pm_measure_pair_edit_floor(pm_handle *h, int mode, float *ms, uin
 
 extern "C" int pm_pack_time(pm_handle *h, float *ms) {
   if (!h || !h->inited || !ms) return PM_E_INVALID;
-  *ms = h->kern == PM_KERNEL_SEED ? h->pack_ms : 0.f;
+  *ms = (h->kern == PM_KERNEL_SEED || (h->pk_bits && !h->win)) ? h->pack_ms : 0.f;   // (a resident packed handle: its unpack kernel)
   return PM_OK;
 }
 
@@ -1906,14 +2093,22 @@ int fetch_windows(pm_handle *h, std::vector<Window> &wins) {
   for (Window &w : wins) { w.off = total; total += w.len; }
   h->winbuf.resize((size_t)total + 1);
   if (wins.empty()) return PM_OK;
-  if (h->h_text) {
-    // host copy of the stream: copy + code -> character in one pass, slices of windows per thread
+  if (has_host_form(h)) {
+    // host copy of the stream: copy (or decode, from the packed form) + code -> character in one pass, slices of windows per thread
     auto copy = [&](size_t lo, size_t hi) {
       for (size_t wi = lo; wi < hi; ++wi) {
         const Window &w = wins[wi];
-        for (int i = 0; i < w.len; ++i) {
-          const int64_t p = w.start + i;
-          h->winbuf[w.off + i] = h->alpha.ch[(p >= 0 && p < h->n) ? h->h_text[p] : 0];
+        uint8_t *dst = h->winbuf.data() + w.off;
+        if (h->h_text) {
+          for (int i = 0; i < w.len; ++i) {
+            const int64_t p = w.start + i;
+            dst[i] = h->alpha.ch[(p >= 0 && p < h->n) ? h->h_text[p] : 0];
+          }
+        } else {
+          const int64_t a = std::min(h->n, std::max<int64_t>(0, w.start)), b = std::max(a, std::min(h->n, w.start + w.len));
+          memset(dst, 0, (size_t)w.len);
+          if (b > a) (void)pm_unpack_codes(h->h_packed, h->h_packed_bytes, h->pk_bits, a, b - a, dst + (a - w.start));
+          for (int i = 0; i < w.len; ++i) dst[i] = h->alpha.ch[dst[i]];
         }
       }
     };

@@ -97,6 +97,11 @@ const char *bitpar_kernel_name(int k, bool indels);
 // which byte values occur in the stream (pm_util.hip); used to bound the character classes of -w/-W on raw streams
 hipError_t stream_presence(const uint8_t *d_text, int64_t n, bool present[256], hipStream_t st);
 
+// ---- bit-packed stream -> bytes + 2-bit words in HBM (pm_unpack.hip) ---------------------------
+// n codes of `bits` bits from bit 0 of d_packed (8-byte aligned) -> d_text[0 .. n rounded up to 16) (16-byte aligned, zero
+// past n) and, when d_words != nullptr, the words of pack_stream(d_text, n, ascii, ...)
+hipError_t unpack_stream(const void *d_packed, int64_t packed_bytes, int bits, int64_t n, bool ascii, void *d_text, uint32_t *d_words, hipStream_t st);
+
 // ---- window gather (verify stage text access when the stream lives only in HBM) -------------
 hipError_t gather_windows(const uint8_t *d_text, int64_t n, const int64_t *d_starts, const int32_t *d_lens,
                           const int64_t *d_offsets, int count, uint8_t *d_out, hipStream_t st);

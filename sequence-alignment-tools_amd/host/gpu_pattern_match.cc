@@ -8,21 +8,32 @@
 
 namespace pmgpu {
 
+StreamChars::StreamChars(std::string table) : table_(std::move(table)) {
+  for (int i = 0; i < 256; ++i) inv_[i] = table_.empty() ? i : -1;
+  for (size_t i = 0; i < table_.size(); ++i) inv_[(unsigned char)table_[i]] = (int)i;
+}
+
 BufferChars::BufferChars(std::vector<unsigned char> bytes, std::string table)
-    : bytes_(std::move(bytes)), table_(std::move(table)) {
+    : StreamChars(std::move(table)), bytes_(std::move(bytes)) {
   data_ = bytes_.data();
   n_ = (int64_t)bytes_.size();
-  build_inverse();
 }
 
 BufferChars::BufferChars(const unsigned char *data, size_t n, std::string table)
-    : data_(data), n_((int64_t)n), table_(std::move(table)) {
-  build_inverse();
+    : StreamChars(std::move(table)), data_(data) {
+  n_ = (int64_t)n;
 }
 
-void BufferChars::build_inverse() {
-  for (int i = 0; i < 256; ++i) inv_[i] = table_.empty() ? i : -1;
-  for (size_t i = 0; i < table_.size(); ++i) inv_[(unsigned char)table_[i]] = (int)i;
+PackedChars::PackedChars(std::vector<unsigned char> packed, int bits, std::string table)
+    : StreamChars(std::move(table)), bytes_(std::move(packed)), bits_(bits) {
+  data_ = bytes_.data();
+  bytes_n_ = (int64_t)bytes_.size();
+  n_ = bytes_n_ * 8 / bits_;
+}
+
+PackedChars::PackedChars(const unsigned char *packed, size_t packed_bytes, int bits, std::string table)
+    : StreamChars(std::move(table)), data_(packed), bytes_n_((int64_t)packed_bytes), bits_(bits) {
+  n_ = bytes_n_ * 8 / bits_;
 }
 
 // a shard holds its own bytes, a guard band either side (filter_bitvec chains of candidates that
@@ -79,8 +90,32 @@ void GpuPatternMatch::init(CharacterProducer &cp) {
   // the engine needs cp only for nch()/ch()/size() and the bytes (SURVEY 8b "Text access")
   std::string table;
   if (cp.size() < 256) for (unsigned i = 0; i < cp.size(); ++i) table.push_back(cp.ch((unsigned char)i));
+  const uint8_t *tb = table.empty() ? nullptr : reinterpret_cast<const uint8_t *>(table.data());
+  // a bit-packed stream (<db>.sqz) crosses PCIe packed and is unpacked on the GPU (pm_init_packed).  PM_GPU_PACKED=0 keeps
+  // the route through one byte per code in host memory (for A/B runs); position shards of a packed stream take it too.
+  PackedChars *pc = dynamic_cast<PackedChars *>(&cp);
+  const char *pk_env = getenv("PM_GPU_PACKED");
+  if (pc && !group_ && !(pk_env && atoi(pk_env) == 0 && *pk_env)) {
+    n_ = pc->length();
+    const int64_t win = window_for(device_, n_);
+    if (pm_init_packed(h_, pc->packed(), pc->packed_bytes(), pc->bits(), n_, tb, (int32_t)table.size(), win) != PM_OK) fatal("init");
+    if (verbose_) {
+      int64_t res[6] = {0, 0, 0, 0, 0, 0};
+      (void)pm_stream_residency(h_, res, 6);
+      if (res[0] > 0) fprintf(stderr, "stream: packed, %lld bits per code, windowed, window %lld positions (%lld packed bytes stay in host memory for %lld positions)\n",
+                              (long long)res[5], (long long)res[0], (long long)pc->packed_bytes(), (long long)n_);
+      else fprintf(stderr, "stream: packed, %lld bits per code, resident: %lld bytes uploaded and unpacked in HBM to %lld positions\n",
+                   (long long)res[5], (long long)res[3], (long long)n_);
+    }
+    return;
+  }
   const unsigned char *bytes;
-  if (cp.has_filename() && cp.c_str()) {                                      // mmap path: char_io.h:167-169
+  if (pc) {                                                                   // the packed bytes, decoded eight codes at a time
+    owned_.assign((size_t)pc->length(), 0);
+    if (pm_unpack_codes(pc->packed(), pc->packed_bytes(), pc->bits(), 0, pc->length(), owned_.data()) != PM_OK) { fprintf(stderr, "Fatal error: init: bad packed stream\n"); exit(1); }
+    bytes = owned_.data();
+    n_ = (int64_t)owned_.size();
+  } else if (cp.has_filename() && cp.c_str()) {                                      // mmap path: char_io.h:167-169
     bytes = reinterpret_cast<const unsigned char *>(cp.c_str());
     n_ = cp.length();
   } else {                                                                    // BufferedFileChars: drain once
@@ -92,7 +127,6 @@ void GpuPatternMatch::init(CharacterProducer &cp) {
     bytes = owned_.data();
     n_ = (int64_t)owned_.size();
   }
-  const uint8_t *tb = table.empty() ? nullptr : reinterpret_cast<const uint8_t *>(table.data());
   if (!group_) {
     const int64_t win = window_for(device_, n_);
     if (win > 0 ? pm_init_windowed(h_, bytes, n_, tb, (int32_t)table.size(), win) != PM_OK

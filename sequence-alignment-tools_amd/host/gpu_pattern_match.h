@@ -32,13 +32,10 @@ class CharacterProducer {                       // reference char_io.h:18-71 (su
   virtual const char *c_str() const { return nullptr; }   // contiguous bytes when has_filename()
 };
 
-// A stream held in memory (what MapFileChars / Normalized<MapFileChars> are to the reference).
-class BufferChars : public CharacterProducer {
+// What the in-memory streams below share: the alphabet table, the position, and random access to one code (the command
+// lines look at single stream positions; a packed stream has no c_str() to index).
+class StreamChars : public CharacterProducer {
  public:
-  BufferChars(std::vector<unsigned char> bytes, std::string table);   // table empty = raw stream
-  // bytes owned by someone else (a file mapping, seq_io.h) who outlives this object
-  BufferChars(const unsigned char *data, size_t n, std::string table);
-  unsigned char getnch() override { return data_[pos_++]; }
   char ch(unsigned char c) override { return table_.empty() ? (char)c : table_[c]; }
   int nch(char c) override { return inv_[(unsigned char)c]; }
   unsigned int size() const override { return table_.empty() ? 256u : (unsigned)table_.size(); }
@@ -46,16 +43,53 @@ class BufferChars : public CharacterProducer {
   bool eof() const override { return pos_ >= n_; }
   int64_t pos() const override { return pos_; }
   void pos(int64_t p) override { pos_ = p; }
-  bool has_filename() const override { return true; }
-  const char *c_str() const override { return reinterpret_cast<const char *>(data_); }
- private:
-  void build_inverse();
-  std::vector<unsigned char> bytes_;
-  const unsigned char *data_ = nullptr;
+  virtual unsigned char code_at(int64_t p) const = 0;   // the code getnch() returns at position p, 0 <= p < length()
+ protected:
+  explicit StreamChars(std::string table);              // table empty = raw stream
   int64_t n_ = 0;
   std::string table_;
   int inv_[256];
   int64_t pos_ = 0;
+};
+
+// A stream held in memory (what MapFileChars / Normalized<MapFileChars> are to the reference).
+class BufferChars : public StreamChars {
+ public:
+  BufferChars(std::vector<unsigned char> bytes, std::string table);   // table empty = raw stream
+  // bytes owned by someone else (a file mapping, seq_io.h) who outlives this object
+  BufferChars(const unsigned char *data, size_t n, std::string table);
+  unsigned char getnch() override { return data_[pos_++]; }
+  unsigned char code_at(int64_t p) const override { return data_[p]; }
+  bool has_filename() const override { return true; }
+  const char *c_str() const override { return reinterpret_cast<const char *>(data_); }
+ private:
+  std::vector<unsigned char> bytes_;
+  const unsigned char *data_ = nullptr;
+};
+
+// A bit-packed stream held in memory (<db>.sqz; what Compressed<> is to the reference, char_io.t:18-214): codes of
+// `bits` bits, most significant bit first.  length() counts every whole code the bytes hold, the end-of-sequence codes
+// that fill up compress_seq's last buffer included.  No c_str(): GpuPatternMatch::init hands the packed bytes to
+// pm_init_packed, which unpacks them on the GPU.
+class PackedChars : public StreamChars {
+ public:
+  PackedChars(std::vector<unsigned char> packed, int bits, std::string table);
+  // packed bytes owned by someone else (a file mapping, seq_io.h) who outlives this object
+  PackedChars(const unsigned char *packed, size_t packed_bytes, int bits, std::string table);
+  unsigned char getnch() override { return code_at(pos_++); }
+  unsigned char code_at(int64_t p) const override {      // a code spans at most two bytes
+    const int64_t bit = p * bits_, b = bit >> 3;
+    const unsigned w = ((unsigned)data_[b] << 8) | (b + 1 < bytes_n_ ? data_[b + 1] : 0u);
+    return (unsigned char)((w >> (16 - bits_ - (int)(bit & 7))) & ((1u << bits_) - 1u));
+  }
+  const unsigned char *packed() const { return data_; }
+  int64_t packed_bytes() const { return bytes_n_; }
+  int bits() const { return bits_; }
+ private:
+  std::vector<unsigned char> bytes_;
+  const unsigned char *data_ = nullptr;
+  int64_t bytes_n_ = 0;
+  int bits_ = 8;
 };
 
 struct pattern_hit {                            // one element of pattern_hit_vector (pattern_match.h:82)

@@ -334,7 +334,7 @@ int main(int argc, char **argv) {
     pm.add_pattern(patarray[i], i, patconst[i].first, patconst[i].second);
     maxlen = std::max(maxlen, patarray[i].size());
   }
-  BufferChars &ff = db.chars();
+  StreamChars &ff = db.chars();
   pm.verbose(opt.chatty);
   pm.init(ff);
   if (!ranks.single() && ranks.rank() != 0) {                        // this rank scans its shard, hands its records to rank 0 and is done
@@ -459,7 +459,7 @@ int main(int argc, char **argv) {
       x.ncount = 0;
       for (long i = 0; i < amplicon_len; ++i) {
         const int64_t q = ps + i;
-        const char ch = q >= 0 && q < db.length() ? ff.ch((unsigned char)ff.c_str()[q]) : '\0';
+        const char ch = q >= 0 && q < db.length() ? ff.ch(ff.code_at(q)) : '\0';
         x.amplicon[(size_t)i] = ch;
         if (ch == 'N' || ch == 'n') ++x.ncount;
       }

@@ -378,7 +378,7 @@ int main(int argc, char **argv) {
     kt.add_pattern(patarray[i], i, patconst[i].first, patconst[i].second);
     maxlen = std::max(maxlen, patarray[i].size());
   }
-  BufferChars &ff = db.chars();
+  StreamChars &ff = db.chars();
   kt.verbose(opt.chatty);
   kt.init(ff);
   if (!ranks.single() && ranks.rank() != 0) {                        // this rank scans its shard, hands its records to rank 0 and is done

@@ -17,8 +17,8 @@ int main(int argc, char **argv) {
   printf("table ");
   for (unsigned char c : db.table()) printf("%02x", c);
   printf("\nstream ");
-  const char *p = db.chars().c_str();
-  for (int64_t i = 0; i < db.length(); ++i) printf("%02x", (unsigned char)p[i]);
+  const pmgpu::StreamChars &cs = db.chars();
+  for (int64_t i = 0; i < db.length(); ++i) printf("%02x", cs.code_at(i));
   printf("\nentries %zu\n", db.entries());
   unsigned long last = 0;
   for (int64_t i = 1; i <= db.length(); ++i) {                     // entry of every position (an end position as the engines report it): index + start

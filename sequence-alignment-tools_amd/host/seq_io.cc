@@ -89,6 +89,7 @@ bool MappedFile::open(const std::string &path) {
 SeqDb::SeqDb(const std::string &database, int format, bool load_headers, bool check, bool upper_case, char eos_char, bool memmap) {
   std::vector<unsigned char> bytes;
   bool mapped = false, raw = false;
+  unsigned packed_bits = 0;                             // > 0: `bytes` / the mapping hold a bit-packed stream
   auto load = [&](const std::string &path) -> bool {
     if (memmap && map_.open(path)) { mapped = true; return true; }
     return read_file(path, &bytes);
@@ -100,24 +101,16 @@ SeqDb::SeqDb(const std::string &database, int format, bool load_headers, bool ch
       die(("Can't open normalized sequence database " + database + ".sqn/.tbl").c_str());
     table_.assign(tb.begin(), tb.end());
   } else if ((format == 0 && file_exists(database + ".sqz")) || format == 4) {   // select.t:74
-    // compressed database (char_io.t:18-214): codes of ceil(log2(table size)) bits, most significant bit first;
-    // unpacked here into one code per byte -- the stream the engines see is the .sqn one plus the end-of-sequence
-    // codes that fill up the last buffer
+    // compressed database (char_io.t:18-214): codes of ceil(log2(table size)) bits, most significant bit first.  The
+    // file is handed on as it is (PackedChars): the stream the engines see is the .sqn one plus the end-of-sequence
+    // codes that fill up the last buffer, and it is unpacked where it is needed -- on the GPU
     normalized_ = true;
-    std::vector<unsigned char> packed, tb;
-    if (!read_file(database + ".sqz", &packed) || !read_file(database + ".tbz", &tb) || tb.empty())
+    std::vector<unsigned char> tb;
+    if (!load(database + ".sqz") || !read_file(database + ".tbz", &tb) || tb.empty() || tb.size() > 256)
       die(("Can't open compressed sequence database " + database + ".sqz/.tbz").c_str());
     table_.assign(tb.begin(), tb.end());
-    unsigned bits = 1;
-    while ((1u << bits) < tb.size()) ++bits;
-    const size_t nchars = packed.size() * 8 / bits;
-    bytes.resize(nchars);
-    size_t bitat = 0;
-    for (size_t i = 0; i < nchars; ++i) {
-      unsigned code = 0;
-      for (unsigned b = 0; b < bits; ++b, ++bitat) code = (code << 1) | ((packed[bitat >> 3] >> (7 - (bitat & 7))) & 1u);
-      bytes[i] = (unsigned char)code;
-    }
+    packed_bits = 1;
+    while ((1u << packed_bits) < tb.size()) ++packed_bits;
   } else if ((format == 0 && file_exists(database + ".seq")) || format == 2) {   // select.t:118
     if (!load(database + ".seq")) die(("Can't open indexed sequence database " + database + ".seq").c_str());
   } else {                                               // none of the files, or -D 1: the FASTA file itself (select.t:152-186)
@@ -167,7 +160,10 @@ SeqDb::SeqDb(const std::string &database, int format, bool load_headers, bool ch
     cache_.resize(keys_.size());
     cached_.assign(keys_.size(), false);
   }
-  if (mapped) {
+  if (packed_bits) {
+    chars_ = mapped ? new PackedChars(map_.data(), map_.size(), (int)packed_bits, table_) : new PackedChars(std::move(bytes), (int)packed_bits, table_);
+    length_ = chars_->length();
+  } else if (mapped) {
     length_ = (int64_t)map_.size();
     chars_ = new BufferChars(map_.data(), map_.size(), table_);
   } else {
@@ -197,7 +193,7 @@ SeqDb::SeqDb(const std::string &database, int format, bool load_headers, bool ch
     if (ikeys[0] == 0)
       die("Bad format for indexed sequence database.", "Parameter indicates EOS as first character, but first sequence starts at 0.");
     if (ikeys[0] > 1) die("Bad format for indexed sequence database.", "First sequence starts at position > 1.");
-    const char c0 = length_ > 0 ? chars_->ch((unsigned char)chars_->c_str()[0]) : 0;
+    const char c0 = length_ > 0 ? chars_->ch(chars_->code_at(0)) : 0;
     if (c0 != eos_char) {
       fprintf(stderr, "Bad format for indexed sequence database.\nEOS character mismatch.\n");
       fprintf(stderr, "From indexed sequence database: %c\nFrom primer_match config: %c\n", c0, eos_char);

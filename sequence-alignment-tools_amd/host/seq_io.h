@@ -56,7 +56,7 @@ class SeqDb {
   // Errors follow the reference: message on stderr, exit(1).
   // memmap: map the sequence file (the reference's default) instead of reading it (-B, BufferedFileChars).
   SeqDb(const std::string &database, int format, bool load_headers, bool check, bool upper_case, char eos_char, bool memmap = true);
-  BufferChars &chars() { return *chars_; }
+  StreamChars &chars() { return *chars_; }             // BufferChars, or PackedChars for a compressed database
   bool normalized() const { return normalized_; }
   const std::string &table() const { return table_; }
   int64_t length() const { return length_; }
@@ -66,7 +66,7 @@ class SeqDb {
   size_t entries() const { return keys_.size(); }
  private:
   bool locate(int64_t pos, size_t *idx) const;       // last entry with key <= pos-1
-  BufferChars *chars_ = nullptr;
+  StreamChars *chars_ = nullptr;
   MappedFile map_;
   bool normalized_ = false;
   std::string table_;

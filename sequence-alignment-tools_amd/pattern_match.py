@@ -25,6 +25,7 @@ ABI_SYMBOLS = [
     "pm_last_kernel_time", "pm_pick_semantics", "pm_measure_stream_read",
     "pm_final_hits_device", "pm_copy_records", "pm_pack_time", "pm_init_host", "pm_scan_stats", "pm_measure_pair_edit_floor", "pm_prepare_device",
     "pm_init_windowed", "pm_stream_residency", "pm_device_memory",
+    "pm_init_packed", "pm_unpack_device", "pm_unpack_codes", "pm_pack_codes",
     "pm_comm_unique_id", "pm_comm_create", "pm_comm_gather", "pm_comm_destroy", "pm_comm_last_error",
 ]
 
@@ -88,6 +89,10 @@ def load_library():
         L.pm_init_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32]
         L.pm_init_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]
         L.pm_init_windowed.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int64]
+        L.pm_init_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_int64]
+        L.pm_unpack_device.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.pm_unpack_codes.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_void_p]
+        L.pm_pack_codes.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64]
         L.pm_stream_residency.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_int]
         L.pm_device_memory.argtypes = [C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.pm_scan.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
@@ -135,6 +140,35 @@ def measure_stream_read(d_ptr, nbytes, reps=5, stream=0):
     if rc:
         raise PmError(rc, "pm_measure_stream_read failed")
     return g.value
+
+
+def pack_codes(codes, bits):
+    """pm_pack_codes: uint8 codes (< 2**bits) -> the bit-packed bytes of a <db>.sqz, MSB first, zero fill bits at the end."""
+    arr = np.ascontiguousarray(codes, dtype=np.uint8)
+    out = np.zeros(max(0, (arr.size * int(bits) + 7) // 8), dtype=np.uint8)
+    rc = load_library().pm_pack_codes(arr.ctypes.data_as(C.c_void_p), arr.size, int(bits), out.ctypes.data_as(C.c_void_p), out.size)
+    if rc:
+        raise PmError(rc, "pm_pack_codes: bits outside 1..8 or a code that does not fit %d bits" % bits)
+    return out
+
+
+def unpack_codes(packed, bits, first, n):
+    """pm_unpack_codes: codes first .. first+n-1 of a bit-packed stream as a uint8 array."""
+    arr = np.ascontiguousarray(packed, dtype=np.uint8)
+    out = np.zeros(max(int(n), 0), dtype=np.uint8)
+    rc = load_library().pm_unpack_codes(arr.ctypes.data_as(C.c_void_p), arr.size, int(bits), int(first), int(n), out.ctypes.data_as(C.c_void_p))
+    if rc:
+        raise PmError(rc, "pm_unpack_codes: bits outside 1..8 or codes outside the packed bytes")
+    return out
+
+
+def unpack_device(d_packed, packed_bytes, bits, n, d_text, d_words=0, stream=0):
+    """pm_unpack_device over raw device pointers (torch tensors' data_ptr()): n codes from bit 0 of d_packed into the bytes
+    at d_text (room for n rounded up to 16) and, when d_words is given, the 2-bit words of the seed family."""
+    rc = load_library().pm_unpack_device(C.c_void_p(d_packed), int(packed_bytes), int(bits), int(n), C.c_void_p(d_text),
+                                         C.c_void_p(d_words or 0), C.c_void_p(stream or 0))
+    if rc:
+        raise PmError(rc, "pm_unpack_device failed (arguments, alignment or launch)")
 
 
 def reverse_comp(p):
@@ -206,6 +240,16 @@ class PatternMatch:
         else:
             self._check(self._L.pm_init_windowed(self._h, arr.ctypes.data_as(C.c_void_p), arr.size, tb, tl, int(window)))
         self._n, self._pos = arr.size, 0
+
+    def init_packed(self, packed, bits, n, table, window=None):
+        """pm_init_packed: `packed` holds n codes of `bits` bits, MSB first (a <db>.sqz); it crosses PCIe packed and is
+        unpacked on the GPU.  `window` as for init(): None keeps the whole stream resident."""
+        arr = np.ascontiguousarray(packed, dtype=np.uint8)
+        self._keep = arr                      # borrowed until close()
+        tb = None if table is None else (C.c_uint8 * len(table)).from_buffer_copy(bytes(table))
+        self._check(self._L.pm_init_packed(self._h, arr.ctypes.data_as(C.c_void_p), arr.size, int(bits), int(n), tb,
+                                           0 if table is None else len(table), 0 if window is None else int(window)))
+        self._n, self._pos = int(n), 0
 
     def init_host(self, text, table=None):
         """pm_init_host: a handle that runs the HOST stage only (finalize, align_hits) over the whole stream -- the merge
@@ -390,10 +434,10 @@ class PatternMatch:
 
     def residency(self):
         """pm_stream_residency: the window size in use (0 = whole stream resident), HBM bytes held for the stream now and
-        at peak, stream bytes uploaded and window loads since init"""
-        v = (C.c_int64 * 5)()
-        self._check(self._L.pm_stream_residency(self._h, v, 5))
-        names = ("window", "held", "peak", "uploaded", "loads")
+        at peak, stream bytes that crossed PCIe and window loads since init, bits per code of the host form (0: bytes)"""
+        v = (C.c_int64 * 6)()
+        self._check(self._L.pm_stream_residency(self._h, v, 6))
+        names = ("window", "held", "peak", "uploaded", "loads", "bits")
         return {k: int(v[i]) for i, k in enumerate(names)}
 
     def measure_pair_edit_floor(self, mode):
