@@ -251,6 +251,35 @@ int pm_align_hits(pm_handle *h, const pm_hit *hits, size_t n, pm_alignment *out)
  * both NUL-terminated at ops + i*stride and text + i*stride.  stride > longest pattern + k. */
 int pm_align_hits_text(pm_handle *h, const pm_hit *hits, size_t n, pm_alignment *out, char *ops, char *text, size_t stride);
 
+/* pm_align_hits / pm_align_hits_text for n 16-byte records that lie in HBM (pm_final_hits_device, a gather buffer, the
+ * caller's own) -- the results stay in HBM too: d_out[n] pm_alignment and, when d_ops / d_text are given (both or
+ * neither; NULL: stride is ignored), the two strings of record i at i * stride.  On a handle whose whole stream is in HBM
+ * (pm_init, pm_init_device, pm_init_packed without windows) one GPU lane re-aligns one record; patterns
+ * longer than 32 characters with k >= 1, and k > 3, are beyond that kernel: those records are aligned by the code behind
+ * pm_align_hits inside the same call, and so is every record of a pm_init_windowed / pm_init_host handle (their text is
+ * not in HBM as a whole) -- the answers are the same, pm_counts' info says how many went which way.  A record that has no
+ * alignment at all (editdist INT32_MAX with start 0: the DP gave up at a row, pattern_alignment.cc:425-436) gets two
+ * empty strings.  Runs on the handle's stream and returns when the results are complete. */
+int pm_align_hits_device(pm_handle *h, const void *d_hits, size_t n, void *d_out, void *d_ops, void *d_text, size_t stride);
+
+/* PatternMatch::find_patterns over (begin, end] plus the caller's tally loop (primer_match.cc:1118-1268, `-c`) with
+ * nothing handed out: the range's final hits are re-aligned and tallied where they are, in HBM.  Ranges as for pm_scan
+ * (consecutive, increasing; end == n flushes; dense ranges are cut into pieces by the library).  The tally, per pattern
+ * (each added pattern is one of its own), over its hits in order of stream end: a hit that comes after the pattern's
+ * total has reached max_count is skipped; the others are re-aligned; one that re-aligns to more than k (the caller's
+ * "Bogus hit", primer_match.cc:1248-1261) is counted in info.bogus and neither tallied nor counted towards max_count;
+ * the rest add one to counts[pattern][editdist].  max_count is primer_match's -M (0: none) and must not change between
+ * two pm_reset()s; pm_scan / pm_scan_view and pm_count_scan cannot be mixed between two pm_reset()s (PM_E_INVALID).
+ * pm_init_windowed handles give the same tallies with the re-alignment on the host; pm_init_host handles cannot scan. */
+int pm_count_scan(pm_handle *h, int64_t begin, int64_t end, uint64_t max_count);
+
+/* The tallies since the last pm_reset: counts[i * (k + 1) + d] for the i-th added pattern (npat = patterns added),
+ * capped[i] = 1 when its total reached max_count (capped and info may be NULL).  info: hits tallied, hits skipped behind
+ * a cap, records re-aligned on the device / on the host (pm_align_hits_device included), bogus hits and the one with the
+ * smallest (end, id) (its k is not recorded: 0), bytes of hit records copied device -> host by these calls. */
+typedef struct { uint64_t tallied, skipped, aligned_device, aligned_host, bogus, record_bytes_to_host; pm_hit first_bogus; } pm_count_info;
+int pm_counts(pm_handle *h, uint64_t *counts, uint8_t *capped, size_t npat, pm_count_info *info);
+
 /* ---- Multi-GPU exchange (the reference has no counterpart: its scan is one serial
  * pass, primer_match.cc:1118).  One rank = one process = one GPU.  The ranks scan position shards
  * (pm_scan_candidates on local stream indices), exchange their record counts by whatever means the

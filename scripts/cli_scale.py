@@ -71,10 +71,10 @@ def mutate(rng, w, nsub):
     return bytes(w)
 
 
-def run_timed(cmd, stdout):
+def run_timed(cmd, stdout, env=None):
     t0 = time.time()
     with open(stdout, "wb") as f:
-        r = subprocess.run(cmd, stdout=f, stderr=subprocess.PIPE)
+        r = subprocess.run(cmd, stdout=f, stderr=subprocess.PIPE, env=env)
     dt = time.time() - t0
     return dt, r.returncode, r.stderr.decode("latin1")
 
@@ -87,6 +87,9 @@ def main():
     ap.add_argument("--pairs", type=int, default=100_000)
     ap.add_argument("--ref-sample", type=int, default=30_000_000, help="bases for the reference binaries (0 = skip)")
     ap.add_argument("--tmp", default=None)
+    ap.add_argument("--gpu-counts", choices=["0", "1", "both"], default="0",
+                    help="the -c cases with PM_GPU_COUNTS=0 (the host loop, pm_primer_match's default), =1 (the device tally), or both (the host loop's runs are named *_host_tally)")
+    ap.add_argument("--counts-only", action="store_true", help="only the two -c cases")
     args = ap.parse_args()
     rng = np.random.default_rng(20260101)
     res = {"bases": args.bases, "entries": args.entries, "primers": args.primers, "pairs": args.pairs, "runs": {}}
@@ -130,24 +133,36 @@ def main():
             ("primer_match_k1_align", [os.path.join(HOST, "pm_primer_match"), "-i", db, "-P", os.path.join(d, "primers.txt"), "-k", "1", "-r", "-A", "%i %r %s %e %d %H\\n", "-v"]),
             ("pcr_match_k1_sts", [os.path.join(HOST, "pm_pcr_match"), "-i", db, "-S", os.path.join(d, "pairs.sts"), "-k", "1", "-M", "1000", "-A", "%I %H %>s %<e %l %>d %<d %r\\n", "-v"]),
         ]
+        if args.counts_only:
+            runs = runs[:2]
+        host_env, dev_env = dict(os.environ, PM_GPU_COUNTS="0"), dict(os.environ, PM_GPU_COUNTS="1")
+        envs = {name: (dev_env if args.gpu_counts in ("1", "both") else host_env) for name, _ in runs[:2]}
+        if args.gpu_counts == "both":
+            extra = [(name + "_host_tally", cmd) for name, cmd in runs[:2]]
+            envs.update({name: host_env for name, _ in extra})
+            runs = runs[:2] + extra + runs[2:]
         for name, cmd in runs:
             # every command twice, each a new process (HIP start, tables, upload, scan, report: nothing survives between them but the
             # page cache, which holds the database either way -- it was written a moment ago); wall_s is the faster one, both are kept:
             # process start and exit on a shared box vary by 0.1 s from run to run
             walls = []
             for _ in range(2):
-                dt_i, rc, err_i = run_timed(cmd, os.path.join(d, name + ".out"))
+                dt_i, rc, err_i = run_timed(cmd, os.path.join(d, name + ".out"), envs.get(name))
                 walls.append(dt_i)
                 if dt_i == min(walls):
                     dt, err = dt_i, err_i
             with open(os.path.join(d, name + ".out"), "rb") as f:
                 nlines = sum(1 for _ in f)
             res["runs"][name] = {"wall_s": dt, "wall_s_runs": walls, "rc": rc, "output_lines": nlines, "gbases_per_s_wall": args.bases / dt / 1e9,
-                                 "phases": [l for l in err.splitlines() if l.startswith("[") or l.startswith("scan")]}
+                                 "phases": [l for l in err.splitlines() if l.startswith("[") or l.startswith("scan") or l.startswith("counts")]}
             print(name, "%.2f s" % dt, file=sys.stderr, flush=True)
 
         # the reference binaries on a bounded sample of the same database (same primer files)
-        if args.ref_sample > 0 and os.path.exists(os.path.join(REF, "pcr_match")):
+        if args.gpu_counts == "both":                                # the two routes print the same lines
+            for name, _ in runs[:2]:
+                with open(os.path.join(d, name + ".out"), "rb") as fa, open(os.path.join(d, name + "_host_tally.out"), "rb") as fb:
+                    res["runs"][name]["same_output_as_host_tally"] = fa.read() == fb.read()
+        if args.ref_sample > 0 and not args.counts_only and os.path.exists(os.path.join(REF, "pcr_match")):
             ns = min(args.ref_sample, args.bases)
             codes = np.fromfile(db + ".sqn", dtype=np.uint8, count=ns + 1)[1:]
             sdb = os.path.join(d, "sample")

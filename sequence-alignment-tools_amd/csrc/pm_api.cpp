@@ -198,6 +198,28 @@ struct pm_handle {
   hipEvent_t stage_done[WIN_UP_THREADS] = {};
   int64_t win_held = 0, win_peak = 0, win_uploaded = 0, win_loads = 0;
 
+  // counts (pm_count_scan / pm_counts) and the device re-alignment (pm_align_hits_device): DESIGN.md 5d
+  AlignDevice ad;                     // tables of pm_align.hip, built on first use after an init (ensure_align_tables)
+  bool ad_ready = false, ad_any_long = false;   // ad_any_long: some pattern is beyond the device limit of the DP
+  void *ad_mem[8] = {};
+  int scan_mode = 0;                  // since pm_reset: 0 nothing scanned, 1 pm_scan / pm_scan_view, 2 pm_count_scan
+  bool counting = false;              // a pm_count_scan is in its scan_range and the finals stay on the device
+  uint64_t cnt_max = 0;               // its max_count
+  bool cnt_dev = false;               // the tallies live on the device (else: cnt_host)
+  uint64_t *d_ck = nullptr, *d_ck_alt = nullptr, *d_ck_scan = nullptr;   // tally keys + the tally's two workspaces
+  size_t ck_cap = 0, cnt_fed = 0;     // cnt_fed: upper bound of the records the range's feed kernel looked at
+  void *d_cktemp = nullptr;
+  size_t cktemp_bytes = 0, cktemp_for = 0;
+  unsigned long long *d_cnt = nullptr, *d_cinfo = nullptr, *d_actr = nullptr, *h_actr = nullptr;   // tallies [npat * (k + 1)], info [4], kernel counters [3] (+ pinned copy)
+  size_t cnt_words = 0;
+  pm_hit *d_hostq = nullptr;          // records the feed kernel leaves to the host (patterns beyond the device limit)
+  size_t hostq_cap = 0;
+  pm_hit *d_extra = nullptr;          // the range's host-decided hits, uploaded for the same kernel
+  size_t d_extra_cap = 0;
+  std::vector<uint64_t> cnt_host;     // host tally (k > 3 or 2^22 patterns and more)
+  pm_count_info cinfo{};              // the host's share of pm_counts' info
+  bool cnt_has_bogus = false;
+
   std::string err;
 };
 
@@ -387,10 +409,15 @@ static void drain_spec(pm_handle *h);
 static int ensure_landing(pm_handle *h, size_t need_more);
 static void device_sort_plan(pm_handle *h);
 static void win_release(pm_handle *h);
+static void count_free(pm_handle *h);
+static int count_clear(pm_handle *h);
+static int count_feed_device(pm_handle *h, const pm_hit *d_hits, const unsigned long long *d_count, size_t n_upper);
+static int count_collect(pm_handle *h, size_t nfin, std::vector<pm_hit> &extra, size_t *n_out);
 
 static void free_device(pm_handle *h) {
   drain_spec(h);
   win_release(h);
+  count_free(h);
   if (h->land) (void)hipHostFree(h->land);
   h->land = nullptr; h->land_cap = h->land_n = h->land_pos = 0;
   if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
@@ -634,6 +661,7 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
   { void *lazy[] = {h->d_dp_codes, h->d_dp_esb, h->d_dp_eeb, h->d_fpat_len, h->d_fpat_id}; for (void *q : lazy) if (q) (void)hipFree(q); }
   h->d_dp_codes = nullptr; h->d_dp_esb = h->d_dp_eeb = nullptr; h->d_fpat_len = nullptr; h->d_fpat_id = nullptr;
   h->d_final = nullptr; h->n_final = 0;
+  count_free(h);
   h->seed_flags = false; h->bases_flags = false; h->bases_edits = false; h->half_ranked_any = false;
   h->zoned = false;
   for (const Pattern &p : h->pats) h->zoned = h->zoned || p.esb || p.eeb;
@@ -1362,7 +1390,8 @@ extern "C" int pm_reset(pm_handle *h) {
   std::fill(h->lasthit.begin(), h->lasthit.end(), 0);
   h->halves_fresh = true;
   h->last_count = 0;
-  return PM_OK;
+  h->scan_mode = 0;
+  return count_clear(h);
 }
 
 extern "C" void pm_destroy(pm_handle *h) {
@@ -2569,6 +2598,7 @@ static int ensure_fpat(pm_handle *h) {
 // kernels in front produce it, else n_upper itself).  Enqueues the sort; *sorted tells whether the device could.
 static int land_enqueue_sort(pm_handle *h, const pm_hit *d_hits, const unsigned long long *d_count, size_t n_upper, bool *sorted) {
   *sorted = false;
+  if (h->counting) return count_feed_device(h, d_hits, d_count, n_upper);   // pm_count_scan: the finals are re-aligned where they are
   if (n_upper == 0 || n_upper > (size_t)INT_MAX / 2 || !h->sort_dev) return PM_OK;
   { int rcw = ensure_sort_workspace(h, n_upper, false); if (rcw) return rcw; }
   { int rcp = ensure_fpat(h); if (rcp) return rcp; }
@@ -2598,6 +2628,7 @@ static int finalize_sync(pm_handle *h, const ScanNext *next) {
 // nfin final hits (sorted on the device: d_sorted, else as they are at d_hits) + the host-decided `extra` -> landing buffer,
 // in (end, pid, k) order.  The copy runs on the copy stream: the handle's stream may hold the next range's scan.
 static int land_collect(pm_handle *h, const pm_hit *d_hits, bool sorted, size_t nfin, std::vector<pm_hit> &extra, size_t *n_out) {
+  if (h->counting) return count_collect(h, nfin, extra, n_out);
   { int rcl = ensure_landing(h, nfin + extra.size()); if (rcl) return rcl; }
   pm_hit *dst = h->land + h->land_n;
   if (nfin) {
@@ -2741,6 +2772,7 @@ static int finalize_device_impl(pm_handle *h, const void *d_cands, size_t n, int
     return fail(h, PM_E_UNSUPPORTED, "pm_finalize_device_owned: a chain of candidates reaches from the guard edge into the owned range (repeat longer than the guard band)");
   const double tfd1 = now_ms();
   if (nleft) {
+    if (h->counting) h->cinfo.record_bytes_to_host += nleft * sizeof(pm_hit);
     const size_t at = hostpart.size();
     hostpart.resize(at + nleft);
     if (land) {                                                     // (the handle's stream may hold the next range's scan)
@@ -2878,6 +2910,384 @@ static int align_hits_impl(pm_handle *h, const pm_hit *hits, size_t n, pm_alignm
   return PM_OK;
 }
 
+static int scan_range(pm_handle *h, int64_t begin, int64_t end);
+
+// ---- counts on the device ----------------------------------------------------------------------
+// pm_align_hits_device re-aligns records that lie in HBM (pm_align.hip); pm_count_scan is pm_scan with the landing
+// replaced: the range's final hits are re-aligned where the finalize stage left them, turned into one 64-bit key each
+// (pattern index | end | re-aligned distance), and the tally kernels add them to the handle's tallies under the rule of
+// primer_match.cc:1123-1247.  What the host decides (clusters at range seams and at the stream start, patterns beyond
+// the device limit of the DP) is aligned by align_hits_impl and joins the same key list before the tally.
+
+static void count_free(pm_handle *h) {
+  for (void *&q : h->ad_mem) { if (q) (void)hipFree(q); q = nullptr; }
+  h->ad = AlignDevice(); h->ad_ready = false; h->ad_any_long = false;
+  void *cw[] = {h->d_ck, h->d_ck_alt, h->d_ck_scan, h->d_cktemp, h->d_cnt, h->d_cinfo, h->d_actr, h->d_hostq, h->d_extra};
+  h->d_extra = nullptr; h->d_extra_cap = 0;
+  for (void *q : cw) if (q) (void)hipFree(q);
+  if (h->h_actr) (void)hipHostFree(h->h_actr);
+  h->d_ck = h->d_ck_alt = h->d_ck_scan = nullptr; h->d_cktemp = nullptr; h->d_cnt = h->d_cinfo = h->d_actr = h->h_actr = nullptr;
+  h->d_hostq = nullptr; h->ck_cap = h->cktemp_bytes = h->cktemp_for = h->cnt_words = h->hostq_cap = 0;
+  h->cnt_host.clear(); h->cnt_dev = false; h->counting = false;
+}
+
+// pm_reset: the tallies start again
+static int count_clear(pm_handle *h) {
+  h->cinfo = pm_count_info(); h->cnt_has_bogus = false; h->cnt_max = 0; h->counting = false; h->cnt_fed = 0;
+  std::fill(h->cnt_host.begin(), h->cnt_host.end(), 0);
+  if (h->d_cnt) {
+    HIP_TRY(h, hipMemsetAsync(h->d_cnt, 0, h->cnt_words * sizeof(unsigned long long), h->stream));
+    HIP_TRY(h, hipMemsetAsync(h->d_cinfo, 0, 3 * sizeof(unsigned long long), h->stream));
+    HIP_TRY(h, hipMemsetAsync(h->d_cinfo + 3, 0xff, sizeof(unsigned long long), h->stream));
+    HIP_TRY(h, stream_wait(h));
+  }
+  return PM_OK;
+}
+
+// is the whole stream in HBM (pm_init, pm_init_device, pm_init_packed resident)?
+static bool stream_resident(const pm_handle *h) { return !h->host_only && h->win == 0 && (h->d_text || h->n == 0); }
+
+static int ensure_align_tables(pm_handle *h) {
+  if (h->ad_ready) return PM_OK;
+  const size_t np = h->pats.size();
+  std::vector<uint8_t> tab(ALIGN_TAB_BYTES), chars;
+  std::vector<uint32_t> off(np + 1, 0), ids(np), perm(np), rank(np);
+  std::vector<int32_t> esb(np), eeb(np);
+  align_tables(h->alpha, tab.data());
+  h->ad_any_long = false;
+  for (size_t i = 0; i < np; ++i) {
+    const Pattern &p = h->pats[i];
+    chars.insert(chars.end(), p.s.begin(), p.s.end());
+    off[i + 1] = (uint32_t)chars.size();
+    esb[i] = p.esb; eeb[i] = p.eeb; perm[i] = (uint32_t)i;
+    if (h->cfg.k > 0 && (p.s.size() > (size_t)AL_MAXL || p.s.empty())) h->ad_any_long = true;
+  }
+  if (h->cfg.k > AL_MAXK) h->ad_any_long = true;
+  // pattern ids in increasing order; of equal ids the pattern added last, as id2idx resolves them
+  std::stable_sort(perm.begin(), perm.end(), [&](uint32_t x, uint32_t y) { return h->pats[x].id < h->pats[y].id; });
+  for (size_t r = 0; r < np; ++r) {
+    ids[r] = (uint32_t)h->pats[perm[r]].id;
+    const auto it = h->id2idx.find(ids[r]);
+    if (it != h->id2idx.end()) perm[r] = it->second;
+  }
+  for (size_t r = 0; r < np; ++r) rank[perm[r]] = (uint32_t)r;
+  const void *src[8] = {tab.data(), chars.data(), off.data(), esb.data(), eeb.data(), ids.data(), perm.data(), rank.data()};
+  const size_t bytes[8] = {tab.size(), chars.size(), off.size() * 4, np * 4, np * 4, np * 4, np * 4, np * 4};
+  for (int i = 0; i < 8; ++i) {
+    HIP_TRY(h, hipMalloc(&h->ad_mem[i], bytes[i] ? bytes[i] : 4));
+    if (bytes[i]) HIP_TRY(h, hipMemcpy(h->ad_mem[i], src[i], bytes[i], hipMemcpyHostToDevice));
+  }
+  AlignDevice &a = h->ad;
+  a.tab = (const uint8_t *)h->ad_mem[0]; a.pchars = (const uint8_t *)h->ad_mem[1]; a.poff = (const uint32_t *)h->ad_mem[2];
+  a.esb = (const int32_t *)h->ad_mem[3]; a.eeb = (const int32_t *)h->ad_mem[4];
+  a.ids_sorted = (const uint32_t *)h->ad_mem[5]; a.perm = (const uint32_t *)h->ad_mem[6]; a.idrank = (const uint32_t *)h->ad_mem[7];
+  a.npat = (uint32_t)np; a.k = h->cfg.k; a.indels = h->cfg.indels != 0; a.eos = (uint8_t)h->cfg.eos;
+  a.wc = h->cfg.wildcards != 0; a.tn = h->cfg.text_n != 0;
+  if (!h->d_actr) HIP_TRY(h, hipMalloc((void **)&h->d_actr, 3 * sizeof(unsigned long long)));
+  if (!h->h_actr) HIP_TRY(h, hipHostMalloc((void **)&h->h_actr, 3 * sizeof(unsigned long long), hipHostMallocDefault));
+  h->ad_ready = true;
+  return PM_OK;
+}
+
+extern "C" int pm_align_hits_device(pm_handle *h, const void *d_hits, size_t n, void *d_out, void *d_ops, void *d_text, size_t stride) {
+  if (!h || !h->inited || (n && (!d_hits || !d_out))) return fail(h, PM_E_INVALID, "pm_align_hits_device: bad arguments");
+  if ((d_ops != nullptr) != (d_text != nullptr) || (d_ops && stride == 0)) return fail(h, PM_E_INVALID, "pm_align_hits_device: d_ops and d_text come together, with a stride");
+  if (n == 0) return PM_OK;
+  if (n >= ((size_t)1 << 31)) return fail(h, PM_E_INVALID, "pm_align_hits_device: 2^31 records or more in one call");
+  HIP_TRY(h, hipSetDevice(h->cfg.device));
+  const bool strings = d_ops != nullptr;
+  if (!stream_resident(h)) {                                        // the stream is not in HBM as a whole: the host aligns every record
+    std::vector<pm_hit> all(n);
+    HIP_TRY(h, hipMemcpy(all.data(), d_hits, n * sizeof(pm_hit), hipMemcpyDeviceToHost));
+    h->cinfo.record_bytes_to_host += n * sizeof(pm_hit);
+    std::vector<pm_alignment> al(n);
+    std::vector<char> ho, ht;
+    if (strings) { ho.assign(n * stride, 0); ht.assign(n * stride, 0); }
+    { int rc = align_hits_impl(h, all.data(), n, al.data(), strings ? ho.data() : nullptr, strings ? ht.data() : nullptr, stride); if (rc) return rc; }
+    h->cinfo.aligned_host += n;
+    HIP_TRY(h, hipMemcpy(d_out, al.data(), n * sizeof(pm_alignment), hipMemcpyHostToDevice));
+    if (strings) {
+      HIP_TRY(h, hipMemcpy(d_ops, ho.data(), n * stride, hipMemcpyHostToDevice));
+      HIP_TRY(h, hipMemcpy(d_text, ht.data(), n * stride, hipMemcpyHostToDevice));
+    }
+    return PM_OK;
+  }
+  { int rc = ensure_align_tables(h); if (rc) return rc; }
+  // records of patterns beyond the device limit: the kernel compacts them and their indices; only they cross to the host
+  // and only their results are written back (pm_align_scatter)
+  uint64_t *d_idx = nullptr;
+  pm_hit *d_rec = nullptr;
+  void *d_back = nullptr;
+  auto release = [&]() { if (d_idx) (void)hipFree(d_idx); if (d_rec) (void)hipFree(d_rec); if (d_back) (void)hipFree(d_back); };
+  if (h->ad_any_long) {
+    hipError_t ea = hipMalloc((void **)&d_idx, n * sizeof(uint64_t));
+    if (ea == hipSuccess) ea = hipMalloc((void **)&d_rec, n * sizeof(pm_hit));
+    if (ea != hipSuccess) { release(); return hipfail(h, ea, "pm_align_hits_device"); }
+  }
+  hipError_t e = align_hits_device(h->ad, h->d_text, h->n, (const pm_hit *)d_hits, nullptr, n, (pm_alignment *)d_out, (char *)d_ops, (char *)d_text, stride,
+                                   nullptr, d_rec, d_idx, h->d_actr, h->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(h->h_actr, h->d_actr, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = stream_wait(h);
+  if (e != hipSuccess) { release(); return hipfail(h, e, "pm_align_hits_device"); }
+  const size_t m = (size_t)h->h_actr[0];
+  int rc = PM_OK;
+  if (h->h_actr[1]) rc = fail(h, PM_E_INVALID, "pm_align_hits_device: unknown pattern id");
+  else if (h->h_actr[2]) rc = fail(h, PM_E_INVALID, "pm_align_hits_device: stride too small");
+  h->cinfo.aligned_device += n - m;
+  if (rc == PM_OK && m) {
+    std::vector<pm_hit> hh(m);
+    std::vector<pm_alignment> al(m);
+    std::vector<char> ho, ht;
+    if (strings) { ho.assign(m * stride, 0); ht.assign(m * stride, 0); }
+    e = hipMemcpy(hh.data(), d_rec, m * sizeof(pm_hit), hipMemcpyDeviceToHost);
+    h->cinfo.record_bytes_to_host += m * sizeof(pm_hit);
+    if (e == hipSuccess) rc = align_hits_impl(h, hh.data(), m, al.data(), strings ? ho.data() : nullptr, strings ? ht.data() : nullptr, stride);
+    if (e == hipSuccess && rc == PM_OK) {
+      h->cinfo.aligned_host += m;
+      const size_t ab = m * sizeof(pm_alignment), sb = strings ? m * stride : 0;
+      e = hipMalloc(&d_back, ab + 2 * sb);
+      char *back = (char *)d_back;
+      if (e == hipSuccess) e = hipMemcpy(back, al.data(), ab, hipMemcpyHostToDevice);
+      if (e == hipSuccess && strings) e = hipMemcpy(back + ab, ho.data(), sb, hipMemcpyHostToDevice);
+      if (e == hipSuccess && strings) e = hipMemcpy(back + ab + sb, ht.data(), sb, hipMemcpyHostToDevice);
+      if (e == hipSuccess) e = align_scatter_device(d_idx, m, (const pm_alignment *)back, strings ? back + ab : nullptr, strings ? back + ab + sb : nullptr, stride,
+                                                    (pm_alignment *)d_out, (char *)d_ops, (char *)d_text, h->stream);
+      if (e == hipSuccess) e = stream_wait(h);
+    }
+    if (e != hipSuccess) rc = hipfail(h, e, "pm_align_hits_device");
+  }
+  release();
+  return rc;
+}
+
+static bool count_tally_on_device(const pm_handle *h) {
+  return !h->host_only && h->cfg.k <= AL_MAXK && h->pats.size() < (size_t)TALLY_MAXPAT && (uint64_t)h->n + 512 < (1ull << 39);
+}
+
+// room for `need` tally keys (the first `keep` stay) and the workspaces of a tally over that many
+static int ensure_count_keys(pm_handle *h, size_t need, size_t keep) {
+  if (h->ck_cap < need) {
+    const size_t cap = std::max<size_t>(need + need / 4, (size_t)1 << 16);
+    uint64_t *nk = nullptr;
+    HIP_TRY(h, hipMalloc((void **)&nk, cap * 8));
+    if (keep) HIP_TRY(h, hipMemcpy(nk, h->d_ck, keep * 8, hipMemcpyDeviceToDevice));
+    void *old[] = {h->d_ck, h->d_ck_alt, h->d_ck_scan};
+    for (void *q : old) if (q) (void)hipFree(q);
+    h->d_ck = nk; h->d_ck_alt = h->d_ck_scan = nullptr; h->ck_cap = cap;
+    HIP_TRY(h, hipMalloc((void **)&h->d_ck_alt, cap * 8));
+    HIP_TRY(h, hipMalloc((void **)&h->d_ck_scan, cap * 8));
+  }
+  if (h->cktemp_for < h->ck_cap) {
+    if (h->d_cktemp) (void)hipFree(h->d_cktemp);
+    h->d_cktemp = nullptr;
+    h->cktemp_bytes = tally_temp_bytes(h->ck_cap);
+    HIP_TRY(h, hipMalloc(&h->d_cktemp, h->cktemp_bytes ? h->cktemp_bytes : 16));
+    h->cktemp_for = h->ck_cap;
+  }
+  return PM_OK;
+}
+
+static int ensure_count_state(pm_handle *h) {
+  const size_t words = std::max<size_t>(h->pats.size() * (size_t)(h->cfg.k + 1), 1);
+  h->cnt_dev = count_tally_on_device(h);
+  if (!h->cnt_dev) { if (h->cnt_host.size() != words) h->cnt_host.assign(words, 0); return PM_OK; }
+  { int rc = ensure_align_tables(h); if (rc) return rc; }
+  if (!h->d_cnt) {
+    HIP_TRY(h, hipMalloc((void **)&h->d_cnt, words * sizeof(unsigned long long)));
+    HIP_TRY(h, hipMalloc((void **)&h->d_cinfo, 4 * sizeof(unsigned long long)));
+    h->cnt_words = words;
+    const pm_count_info keep = h->cinfo;                            // (count_clear also clears the host's share)
+    const uint64_t keep_max = h->cnt_max;
+    const int rc = count_clear(h);
+    h->cinfo = keep; h->cnt_max = keep_max;
+    if (rc) return rc;
+  }
+  return PM_OK;
+}
+
+// the device's finals of one range -> tally keys d_ck[0 .. count), before the host knows their number
+static int count_feed_device(pm_handle *h, const pm_hit *d_hits, const unsigned long long *d_count, size_t n_upper) {
+  h->cnt_fed = 0;
+  if (n_upper == 0) return PM_OK;
+  // (cannot happen: the finalize stage in front refuses 2^31 records before it touches the engine's state; not a reason to cut the range)
+  if (n_upper >= ((size_t)1 << 31)) return fail(h, PM_E_INVALID, "pm_count_scan: internal: 2^31 or more final hits in one range");
+  { int rc = ensure_count_keys(h, n_upper + ((size_t)1 << 12), 0); if (rc) return rc; }
+  if (h->ad_any_long && h->hostq_cap < n_upper) {
+    if (h->d_hostq) (void)hipFree(h->d_hostq);
+    h->d_hostq = nullptr;
+    h->hostq_cap = n_upper + n_upper / 4;
+    HIP_TRY(h, hipMalloc((void **)&h->d_hostq, h->hostq_cap * sizeof(pm_hit)));
+  }
+  HIP_TRY(h, align_hits_device(h->ad, h->d_text, h->n, d_hits, d_count, n_upper, nullptr, nullptr, nullptr, 0, h->d_ck,
+                               h->ad_any_long ? h->d_hostq : nullptr, nullptr, h->d_actr, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(h->h_actr, h->d_actr, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+  h->cnt_fed = n_upper;
+  return PM_OK;
+}
+
+static uint64_t host_tally_key(uint32_t idx, int64_t end, int code) {
+  return ((uint64_t)idx << 42) | (((uint64_t)end & ((1ull << 39) - 1ull)) << 3) | (uint64_t)code;
+}
+
+// The tally of primer_match.cc:1123-1247 on the host, for handles whose tallies do not fit the device keys: hits of one
+// pattern in order of stream end (the list is in (end, pid, k) order)
+static void count_host_tally(pm_handle *h, const pm_hit *hits, const pm_alignment *al, size_t m) {
+  const int k = h->cfg.k;
+  for (size_t j = 0; j < m; ++j) {
+    const size_t idx = h->id2idx.find(hits[j].pid)->second;
+    uint64_t total = 0;
+    for (int d = 0; d <= k; ++d) total += h->cnt_host[idx * (k + 1) + d];
+    if (h->cnt_max && total >= h->cnt_max) { ++h->cinfo.skipped; continue; }
+    if (al[j].editdist < 0 || al[j].editdist > k) {
+      ++h->cinfo.bogus;
+      if (!h->cnt_has_bogus || by_end_pid(hits[j], h->cinfo.first_bogus)) { h->cinfo.first_bogus = make_hit(hits[j].end, hits[j].pid, 0); h->cnt_has_bogus = true; }
+      continue;
+    }
+    ++h->cnt_host[idx * (k + 1) + al[j].editdist];
+    ++h->cinfo.tallied;
+  }
+}
+
+// records the host aligns (in (end, pid, k) order) -> keys behind the `at` keys the device made, or the host tally
+static int count_host_records(pm_handle *h, const pm_hit *hits, size_t m, size_t at) {
+  if (m == 0) return PM_OK;
+  std::vector<pm_alignment> al(m);
+  { int rc = align_hits_impl(h, hits, m, al.data(), nullptr, nullptr, 0); if (rc) return rc; }
+  h->cinfo.aligned_host += m;
+  if (!h->cnt_dev) { count_host_tally(h, hits, al.data(), m); return PM_OK; }
+  std::vector<uint64_t> keys(m);
+  for (size_t j = 0; j < m; ++j)
+    keys[j] = host_tally_key(h->id2idx.find(hits[j].pid)->second, hits[j].end, (al[j].editdist < 0 || al[j].editdist > h->cfg.k) ? TALLY_BOGUS : al[j].editdist);
+  { int rc = ensure_count_keys(h, at + m, at); if (rc) return rc; }
+  HIP_TRY(h, hipMemcpy(h->d_ck + at, keys.data(), m * 8, hipMemcpyHostToDevice));
+  return PM_OK;
+}
+
+// sort + tally of the `n` keys at d_ck on the handle's stream (behind the next range's scan when pm_scan's pipeline has
+// enqueued it: nothing the tally reads or writes is touched by a scan)
+static int count_flush(pm_handle *h, size_t n) {
+  if (n == 0 || !h->cnt_dev) return PM_OK;
+  if (n >= ((size_t)1 << 31)) return fail(h, PM_E_INVALID, "pm_count_scan: internal: 2^31 or more tally keys in one range");
+  HIP_TRY(h, tally_device(h->ad, h->d_ck, h->d_ck_alt, h->d_ck_scan, n, h->d_cktemp, h->cktemp_bytes, h->cnt_max, h->d_cnt, h->d_cinfo, h->stream));
+  return PM_OK;
+}
+
+// pm_count_scan's landing: nfin finals were turned into keys by count_feed_device (the finalize stage is done: its
+// counters are on the host); `extra`, the hits of the range that the host rules decided, are uploaded and go through the
+// same kernel.  Only records of patterns beyond the device limit of the DP are aligned on the host.
+static int count_collect(pm_handle *h, size_t nfin, std::vector<pm_hit> &extra, size_t *n_out) {
+  if (n_out) *n_out = nfin + extra.size();
+  if (h->cnt_fed == 0) nfin = 0;
+  h->cnt_fed = 0;
+  std::vector<pm_hit> rest;
+  auto take_hostq = [&](size_t nq) -> int {                         // (the handle's stream may hold the next range's scan)
+    if (!nq) return PM_OK;
+    const size_t at = rest.size();
+    rest.resize(at + nq);
+    HIP_TRY(h, hipMemcpyAsync(rest.data() + at, h->d_hostq, nq * sizeof(pm_hit), hipMemcpyDeviceToHost, h->copy_stream));
+    HIP_TRY(h, hipStreamSynchronize(h->copy_stream));
+    h->cinfo.record_bytes_to_host += nq * sizeof(pm_hit);
+    return PM_OK;
+  };
+  if (nfin) {
+    if (h->h_actr[1]) return fail(h, PM_E_INVALID, "pm_count_scan: a final hit with an unknown pattern id");
+    const size_t nq = (size_t)h->h_actr[0];
+    { int rc = take_hostq(nq); if (rc) return rc; }
+    h->cinfo.aligned_device += nfin - nq;
+  }
+  const size_t m = extra.size();
+  if (m) {
+    { int rc = ensure_count_keys(h, nfin + 2 * m + ((size_t)1 << 12), nfin); if (rc) return rc; }
+    if (h->d_extra_cap < m) {
+      if (h->d_extra) (void)hipFree(h->d_extra);
+      h->d_extra = nullptr;
+      h->d_extra_cap = std::max<size_t>(2 * m, (size_t)1 << 12);
+      HIP_TRY(h, hipMalloc((void **)&h->d_extra, h->d_extra_cap * sizeof(pm_hit)));
+    }
+    if (h->ad_any_long && h->hostq_cap < m) {
+      if (h->d_hostq) (void)hipFree(h->d_hostq);
+      h->d_hostq = nullptr;
+      h->hostq_cap = std::max<size_t>(2 * m, (size_t)1 << 12);
+      HIP_TRY(h, hipMalloc((void **)&h->d_hostq, h->hostq_cap * sizeof(pm_hit)));
+    }
+    HIP_TRY(h, hipMemcpy(h->d_extra, extra.data(), m * sizeof(pm_hit), hipMemcpyHostToDevice));
+    HIP_TRY(h, align_hits_device(h->ad, h->d_text, h->n, h->d_extra, nullptr, m, nullptr, nullptr, nullptr, 0, h->d_ck + nfin,
+                                 h->ad_any_long ? h->d_hostq : nullptr, nullptr, h->d_actr, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->h_actr, h->d_actr, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, stream_wait(h));
+    if (h->h_actr[1]) return fail(h, PM_E_INVALID, "pm_count_scan: a final hit with an unknown pattern id");
+    const size_t nq = (size_t)h->h_actr[0];
+    { int rc = take_hostq(nq); if (rc) return rc; }
+    h->cinfo.aligned_device += m - nq;
+  }
+  for (pm_hit &x : rest) x.aux[0] = x.aux[1] = x.aux[2] = 0;
+  sort_hits(rest.data(), rest.size());
+  { int rc = count_host_records(h, rest.data(), rest.size(), nfin + m); if (rc) return rc; }
+  return count_flush(h, nfin + m + rest.size());
+}
+
+extern "C" int pm_count_scan(pm_handle *h, int64_t begin, int64_t end, uint64_t max_count) {
+  if (!h || !h->inited) return fail(h, PM_E_INVALID, "pm_count_scan: handle not initialised");
+  if (h->host_only) return fail(h, PM_E_INVALID, "pm_count_scan: this handle runs the host stage only");
+  if (h->scan_mode == 1) return fail(h, PM_E_INVALID, "pm_count_scan after pm_scan (pm_reset first)");
+  if (h->scan_mode == 2 && max_count != h->cnt_max) return fail(h, PM_E_INVALID, "pm_count_scan: max_count changed between two pm_reset()s");
+  HIP_TRY(h, hipSetDevice(h->cfg.device));
+  h->scan_mode = 2; h->cnt_max = max_count;
+  { int rc = ensure_count_state(h); if (rc) return rc; }
+  if (end > h->n) end = h->n;
+  if (end <= begin) return PM_OK;
+  // the finals stay on the device when the whole stream is there for the re-alignment; otherwise the range lands as for
+  // pm_scan and the host aligns its hits (the tally is the same)
+  h->counting = h->cnt_dev && stream_resident(h);
+  const bool on_device = h->counting;
+  const int rc = scan_range(h, begin, end);
+  h->counting = false;
+  if (rc) return rc;
+  if (!on_device) {
+    const pm_hit *hits = h->land + h->land_pos;
+    const size_t m = h->land_n - h->land_pos;
+    h->cinfo.record_bytes_to_host += m * sizeof(pm_hit);
+    { int rc2 = count_host_records(h, hits, m, 0); if (rc2) return rc2; }
+    h->land_pos = h->land_n = 0;
+    { int rc2 = count_flush(h, m); if (rc2) return rc2; }
+  }
+  HIP_TRY(h, stream_wait(h));
+  return PM_OK;
+}
+
+extern "C" int pm_counts(pm_handle *h, uint64_t *counts, uint8_t *capped, size_t npat, pm_count_info *info) {
+  if (!h || !h->inited) return fail(h, PM_E_INVALID, "pm_counts: handle not initialised");
+  if (!counts || npat != h->pats.size()) return fail(h, PM_E_INVALID, "pm_counts: counts must hold (k + 1) values for every added pattern");
+  const int k = h->cfg.k;
+  const size_t words = npat * (size_t)(k + 1);
+  pm_count_info out = h->cinfo;
+  if (!h->cnt_has_bogus) out.first_bogus = make_hit(0, 0, 0);
+  memset(counts, 0, words * sizeof(uint64_t));
+  if (h->d_cnt && h->cnt_dev) {
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    unsigned long long di[4];
+    HIP_TRY(h, stream_wait(h));
+    if (words) HIP_TRY(h, hipMemcpy(counts, h->d_cnt, words * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(di, h->d_cinfo, sizeof(di), hipMemcpyDeviceToHost));
+    out.tallied += di[0]; out.skipped += di[1]; out.bogus += di[2];
+    if (di[3] != ~0ull) {
+      uint32_t pid = 0;
+      HIP_TRY(h, hipMemcpy(&pid, h->ad.ids_sorted + (di[3] & 0x3fffffu), 4, hipMemcpyDeviceToHost));
+      out.first_bogus = make_hit((int64_t)(di[3] >> 22), pid, 0);
+    }
+  } else if (h->cnt_host.size() == words) {
+    for (size_t i = 0; i < words; ++i) counts[i] = h->cnt_host[i];
+  }
+  if (capped)
+    for (size_t i = 0; i < npat; ++i) {
+      uint64_t total = 0;
+      for (int d = 0; d <= k; ++d) total += counts[i * (k + 1) + d];
+      capped[i] = h->cnt_max && total >= h->cnt_max ? 1 : 0;
+    }
+  if (info) *info = out;
+  return PM_OK;
+}
+
 // One range of PatternMatch::find_patterns: scan, finalize, final hits in (end, pid, k) order behind whatever the landing
 // buffer still holds.  With a device finalize stage the scan of the range expected next -- the same number of stream
 // bytes, the way the reference's callers walk a stream chunk by chunk -- is already on the GPU when this returns.
@@ -2912,6 +3322,14 @@ static int scan_piece(pm_handle *h, int64_t begin, int64_t end) {
     rc = finalize_into(h, cands.data(), cnt, end, end >= h->n, outv);
     if (rc) return rc;
     sort_hits(outv.data(), outv.size());
+    if (h->counting) {                                                // (the records were finalized on the host: all of them are `extra`)
+      h->cinfo.record_bytes_to_host += cnt * sizeof(pm_hit);
+      h->cnt_fed = 0;
+      rc = count_collect(h, 0, outv, nullptr);
+      if (rc) return rc;
+      h->next_begin = end;
+      return PM_OK;
+    }
     rc = ensure_landing(h, outv.size());
     if (rc) return rc;
     if (!outv.empty()) memcpy(h->land + h->land_n, outv.data(), outv.size() * sizeof(pm_hit));
@@ -2962,6 +3380,8 @@ extern "C" int pm_scan(pm_handle *h, int64_t begin, int64_t end, pm_hit *out, si
   if (!h || !h->inited) return fail(h, PM_E_INVALID, "pm_scan: handle not initialised");
   if (n_out) *n_out = 0;
   if (more) *more = 0;
+  if (h->scan_mode == 2) return fail(h, PM_E_INVALID, "pm_scan after pm_count_scan (pm_reset first)");
+  h->scan_mode = 1;
   if (end > h->n) end = h->n;
   if (end > begin) { const int rc = scan_range(h, begin, end); if (rc) return rc; }
   const size_t avail = h->land_n - h->land_pos;
@@ -2977,6 +3397,8 @@ extern "C" int pm_scan(pm_handle *h, int64_t begin, int64_t end, pm_hit *out, si
 extern "C" int pm_scan_view(pm_handle *h, int64_t begin, int64_t end, const pm_hit **hits, size_t *n) {
   if (!h || !h->inited || !hits || !n) return fail(h, PM_E_INVALID, "pm_scan_view: bad arguments");
   *hits = nullptr; *n = 0;
+  if (h->scan_mode == 2) return fail(h, PM_E_INVALID, "pm_scan_view after pm_count_scan (pm_reset first)");
+  h->scan_mode = 1;
   if (end > h->n) end = h->n;
   if (h->land_pos == h->land_n) h->land_pos = h->land_n = 0;       // the span of the last call is given up
   if (end > begin) { const int rc = scan_range(h, begin, end); if (rc) return rc; }

@@ -147,6 +147,39 @@ hipError_t halves_rule_device(const pm_hit *d_in, size_t n, bool flags, int slac
                               uint64_t *d_keys, uint64_t *d_keys_alt, uint32_t *d_vals, uint32_t *d_vals_alt, void *d_temp, size_t temp_bytes,
                               pm_hit *d_out, unsigned long long *d_counts, hipStream_t st);
 
+// ---- the caller's re-alignment and tally on the device (pm_align.hip) ----------------------------
+constexpr int AL_MAXL = 32, AL_MAXK = 3;         // device limit of the edit-distance DP; longer patterns are aligned by the host
+constexpr int AL_THREADS = 64;                   // one wave per block: every lane owns a column of the block's LDS
+constexpr uint64_t TALLY_INVALID = ~0ull;        // tally key of a record the device did not align
+constexpr int TALLY_BOGUS = 4;                   // distance code of a hit that re-aligns to more than k (or to a violation)
+constexpr uint32_t TALLY_MAXPAT = (1u << 22) - 1;   // pattern indices fit 22 bits below the invalid key's
+constexpr int ALIGN_TAB_BYTES = 256 + 128 * 4;
+
+struct AlignDevice {                             // uploaded once per init (pm_api.cpp ensure_align_tables)
+  const uint8_t *tab = nullptr;                  // align_tables()
+  const uint8_t *pchars = nullptr;               // the patterns as added, one after the other
+  const uint32_t *poff = nullptr;                // [npat + 1] offsets into pchars
+  const int32_t *esb = nullptr, *eeb = nullptr;
+  const uint32_t *ids_sorted = nullptr, *perm = nullptr;   // pattern ids in increasing order and the pattern index of each
+  const uint32_t *idrank = nullptr;              // pattern index -> rank of its id
+  uint32_t npat = 0;
+  int k = 0, indels = 0, eos = 0, wc = 0, tn = 0;
+};
+void align_tables(const Alphabet &alpha, uint8_t *tab);
+// One lane per record of d_hits[0 .. min(*d_count, n_upper)) (d_count may be NULL).  Any of d_out, d_ops + d_txt (strings
+// at i * stride), d_keys (tally keys) may be NULL.  Records of patterns beyond the device limit go to d_hostq_hits (the
+// records) / d_hostq_idx (their indices), whichever is not NULL, counted in d_ctr[0]; d_ctr[1] counts unknown pattern ids,
+// d_ctr[2] strings that did not fit.
+hipError_t align_hits_device(const AlignDevice &a, const uint8_t *d_text, int64_t ntext, const pm_hit *d_hits, const unsigned long long *d_count,
+                             size_t n_upper, pm_alignment *d_out, char *d_ops, char *d_txt, size_t stride, uint64_t *d_keys,
+                             pm_hit *d_hostq_hits, uint64_t *d_hostq_idx, unsigned long long *d_ctr, hipStream_t st);
+// d_src[j] (and the two strings at j * stride, when d_ops != NULL) -> place d_idx[j] of d_out / d_ops / d_txt, j < m
+hipError_t align_scatter_device(const uint64_t *d_idx, size_t m, const pm_alignment *d_src, const char *d_src_ops, const char *d_src_txt, size_t stride,
+                                pm_alignment *d_out, char *d_ops, char *d_txt, hipStream_t st);
+size_t tally_temp_bytes(size_t n);
+hipError_t tally_device(const AlignDevice &a, uint64_t *d_keys, uint64_t *d_keys_alt, uint64_t *d_scan, size_t n, void *d_temp, size_t temp_bytes,
+                        uint64_t max_count, unsigned long long *d_counts, unsigned long long *d_info, hipStream_t st);
+
 // ---- seed extension DP on the GPU (pm_extend.hip) ---------------------------------------------
 hipError_t extend_seeds(const uint8_t *d_text, int64_t n, const pm_hit *d_seeds, size_t nseeds,
                         const uint8_t *d_half_codes, const uint8_t *d_half_len, const int32_t *d_esb, const int32_t *d_eeb,

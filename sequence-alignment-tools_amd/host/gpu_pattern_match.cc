@@ -64,6 +64,7 @@ GpuPatternMatch::GpuPatternMatch(int kernel, unsigned int k, char eos, bool wc, 
   cfg.wildcards = wc ? 1 : 0; cfg.text_n = tn ? 1 : 0; cfg.eos = (unsigned char)eos;
   cfg.device = group_ ? group_->device() : device;
   device_ = cfg.device;
+  k_ = k;
   if (pm_create(&cfg, &h_) != PM_OK) { fprintf(stderr, "Fatal error: %s\n", pm_last_error(nullptr)); exit(1); }
   if (group_ && group_->rank() == 0 && pm_create(&cfg, &merge_) != PM_OK) { fprintf(stderr, "Fatal error: %s\n", pm_last_error(nullptr)); exit(1); }
 }
@@ -83,6 +84,7 @@ unsigned long GpuPatternMatch::add_pattern(std::string const &pat, unsigned long
   if (id == 0) id = ++next_id_;                                               // pattern_match.h:92-94
   if (pm_add_pattern(h_, pat.data(), pat.size(), id, esb, eeb) != PM_OK) fatal("add_pattern");
   if (merge_ && pm_add_pattern(merge_, pat.data(), pat.size(), id, esb, eeb) != PM_OK) fatal("add_pattern");
+  ++npat_;
   return id;
 }
 
@@ -268,6 +270,20 @@ bool GpuPatternMatch::find_patterns(CharacterProducer &cp, pattern_hit_vector &h
     got += cnt;
     if (got >= minka || cp.eof()) return got > 0;
   }
+}
+
+void GpuPatternMatch::count_patterns(CharacterProducer &cp, uint64_t max_count, std::vector<uint64_t> &counts,
+                                     std::vector<uint8_t> &capped, pm_count_info *info) {
+  if (group_) { fprintf(stderr, "Fatal error: count_patterns: a position-sharded run tallies on the host\n"); exit(1); }
+  while (!cp.eof()) {                                                         // the ranges find_patterns would walk
+    const int64_t begin = cp.pos();
+    const int64_t end = begin + chunk_ < n_ ? begin + chunk_ : n_;
+    if (pm_count_scan(h_, begin, end, max_count) != PM_OK) fatal("count_patterns");
+    cp.pos(end);
+  }
+  counts.assign(npat_ * (size_t)(k_ + 1), 0);
+  capped.assign(npat_, 0);
+  if (pm_counts(h_, counts.data(), capped.data(), npat_, info) != PM_OK) fatal("count_patterns");
 }
 
 void GpuPatternMatch::reset() { if (pm_reset(h_) != PM_OK) fatal("reset"); }

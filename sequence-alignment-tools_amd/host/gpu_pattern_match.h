@@ -115,6 +115,13 @@ class GpuPatternMatch {
   void init(CharacterProducer &cp);                                           // pattern_match.h:130
   bool find_patterns(CharacterProducer &cp, pattern_hit_vector &hits, unsigned long minka = 1);  // :131
   void reset();                                                               // :134
+  // find_patterns over the rest of the stream plus the caller's tally loop (primer_match.cc:1118-1268, -c [-M max_count])
+  // with nothing handed out (pm_count_scan / pm_counts): counts[i * (k + 1) + d] and capped[i] for the i-th added
+  // pattern, the tally of the whole pass since the last reset().  One rank only: the cap depends on the order of a
+  // pattern's hits across the shards.
+  void count_patterns(CharacterProducer &cp, uint64_t max_count, std::vector<uint64_t> &counts, std::vector<uint8_t> &capped,
+                      pm_count_info *info = nullptr);
+  bool sharded() const { return group_ != nullptr; }
   int selected_semantics() const;
   int selected_kernel() const;
   void chunk_bytes(int64_t c) { chunk_ = c; }
@@ -134,6 +141,8 @@ class GpuPatternMatch {
   int64_t n_ = 0;
   int64_t chunk_ = (int64_t)1 << 30;
   unsigned long next_id_ = 0;
+  size_t npat_ = 0;
+  unsigned int k_ = 0;
   int device_ = 0;
   bool verbose_ = false;
 };

@@ -397,7 +397,34 @@ int main(int argc, char **argv) {
   std::vector<pm_alignment> al;
   std::vector<char> opsbuf, textbuf;
   StsEntry null_sts;
-  for (;;) {
+  // tallies and no hits (-c without -A), one rank, PM_GPU_COUNTS=1: the hits are re-aligned and tallied on the GPU
+  // (pm_count_scan) and only the tallies come back.  Without the variable (and with -A, --ranks N) the loop below runs: the
+  // device route becomes the default once a count pass has been measured against it.
+  const char *gc_env = getenv("PM_GPU_COUNTS");
+  const bool gpu_counts = opt.print_tallies && !opt.print_hits && !kt.sharded() && gc_env && *gc_env && atoi(gc_env) != 0;
+  if (gpu_counts) {
+    const auto ts0 = std::chrono::steady_clock::now();
+    std::vector<uint64_t> cnt;
+    std::vector<uint8_t> cap;
+    pm_count_info ci;
+    kt.count_patterns(ff, opt.count_cap > 0 ? (uint64_t)opt.count_cap : 0, cnt, cap, &ci);
+    t_scan += std::chrono::duration<double>(std::chrono::steady_clock::now() - ts0).count();
+    if (ci.bogus) {                                                 // "Bogus hit" (primer_match.cc:1249-1263)
+      fprintf(stderr, "Bogus hit returned to primer_match main()\n");
+      fprintf(stderr, "Approximate absolute sequence position:\n %lld\n", (long long)ci.first_bogus.end);
+      fprintf(stderr, "Problem primer:\n %s\n", patarray[ci.first_bogus.pid].c_str());
+      return 1;
+    }
+    for (unsigned long i = 1; i <= N1; ++i) {
+      for (unsigned k = 0; k < K1; ++k) patcount[cidx(i, k)] = (unsigned long)cnt[(i - 1) * K1 + k];
+      if (opt.count_cap > 0) maxpatcount[i] = cap[i - 1] != 0;
+    }
+    nhits = (unsigned long)(ci.tallied + ci.skipped);
+    if (opt.chatty) fprintf(stderr, "counts on the GPU: %llu hits tallied, %llu skipped behind -M, %llu re-aligned on the device, %llu on the host, %llu bytes of hit records to the host\n",
+                            (unsigned long long)ci.tallied, (unsigned long long)ci.skipped, (unsigned long long)ci.aligned_device,
+                            (unsigned long long)ci.aligned_host, (unsigned long long)ci.record_bytes_to_host);
+  }
+  if (!gpu_counts) for (;;) {
     const auto ts0 = std::chrono::steady_clock::now();
     const bool more = kt.find_patterns(ff, l, opt.progress_every);
     const auto ts1 = std::chrono::steady_clock::now();

@@ -10,6 +10,7 @@ _CSRC = os.path.join(_HERE, "csrc")
 _LIB = None
 
 HIT_DTYPE = np.dtype([("end", "<i8"), ("pid", "<u4"), ("k", "u1"), ("aux", "u1", (3,))])
+ALIGNMENT_DTYPE = np.dtype([("start", "<i8"), ("end", "<i8"), ("editdist", "<i4"), ("value", "<i4")])
 
 SEM_AUTO, SEM_KEYWORD_TREE, SEM_SHIFT_AND, SEM_FILTER_BITVEC = 0, 2, 4, 5
 SEM_EXACT_BASES, SEM_EXACT_HALVES, SEM_SHIFT_AND_INEXACT = 8, 12, 100
@@ -26,6 +27,7 @@ ABI_SYMBOLS = [
     "pm_final_hits_device", "pm_copy_records", "pm_pack_time", "pm_init_host", "pm_scan_stats", "pm_measure_pair_edit_floor", "pm_prepare_device",
     "pm_init_windowed", "pm_stream_residency", "pm_device_memory",
     "pm_init_packed", "pm_unpack_device", "pm_unpack_codes", "pm_pack_codes",
+    "pm_align_hits_device", "pm_count_scan", "pm_counts",
     "pm_comm_unique_id", "pm_comm_create", "pm_comm_gather", "pm_comm_destroy", "pm_comm_last_error",
 ]
 
@@ -35,6 +37,16 @@ class PmError(RuntimeError):
         super().__init__("pm_gpu error %d: %s" % (code, msg))
         self.code = code
         self.required = required          # PM_E_OVERFLOW: the record count the buffer must hold
+
+
+class _Hit(C.Structure):
+    _fields_ = [("end", C.c_int64), ("pid", C.c_uint32), ("k", C.c_uint8), ("aux", C.c_uint8 * 3)]
+
+
+class _CountInfo(C.Structure):
+    """pm_count_info"""
+    _fields_ = [("tallied", C.c_uint64), ("skipped", C.c_uint64), ("aligned_device", C.c_uint64), ("aligned_host", C.c_uint64),
+                ("bogus", C.c_uint64), ("record_bytes_to_host", C.c_uint64), ("first_bogus", _Hit)]
 
 
 class _Config(C.Structure):
@@ -120,6 +132,9 @@ def load_library():
         L.pm_scan_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.pm_measure_pair_edit_floor.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
         L.pm_pack_time.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        L.pm_align_hits_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        L.pm_count_scan.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_uint64]
+        L.pm_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(_CountInfo)]
         _LIB = L
     return _LIB
 
@@ -203,6 +218,9 @@ class PatternMatch:
         self._n = 0
         self._pos = 0
         self._keep = None
+        self._k = k
+        self._npat = 0
+        self._maxlen = 0
 
     def _check(self, rc):
         if rc:
@@ -223,6 +241,8 @@ class PatternMatch:
     def add_pattern(self, pat, id=0, exact_start_bases=0, exact_end_bases=0):
         b = pat.encode() if isinstance(pat, str) else bytes(pat)
         self._check(self._L.pm_add_pattern(self._h, b, len(b), id, exact_start_bases, exact_end_bases))
+        self._npat += 1
+        self._maxlen = max(self._maxlen, len(b))
         return id
 
     # -- PatternMatch::init (pattern_match.h:130) -----------------------------------------------
@@ -416,6 +436,82 @@ class PatternMatch:
         if hits.size:
             self._check(self._L.pm_align_hits(self._h, hits.ctypes.data_as(C.c_void_p), hits.size, out.ctypes.data_as(C.c_void_p)))
         return out
+
+    def align_hits_device(self, d_hits, n, text=False, d_out=None, d_ops=None, d_text=None, stride=0):
+        """pm_align_hits_device: re-align n 16-byte records that lie in HBM at `d_hits` (a device pointer); the results
+        stay in HBM.  With the output pointers given they are used; otherwise torch tensors are allocated.  Returns
+        (d_out, d_ops, d_text, stride, keepalive) -- device pointers (d_ops / d_text 0 without text=True) and the
+        tensors that own them."""
+        keep = []
+        if d_out is None:
+            import torch
+            stride = max(int(stride), self._maxlen + self._k + 2) if text else 0
+            out_t = torch.zeros(max(n, 1) * ALIGNMENT_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+            keep.append(out_t)
+            d_out = out_t.data_ptr()
+            if text:
+                ops_t = torch.zeros(max(n, 1) * stride, dtype=torch.uint8, device="cuda")
+                txt_t = torch.zeros(max(n, 1) * stride, dtype=torch.uint8, device="cuda")
+                keep += [ops_t, txt_t]
+                d_ops, d_text = ops_t.data_ptr(), txt_t.data_ptr()
+        self._check(self._L.pm_align_hits_device(self._h, C.c_void_p(d_hits), n, C.c_void_p(d_out), C.c_void_p(d_ops or 0),
+                                                 C.c_void_p(d_text or 0), stride))
+        return d_out, d_ops or 0, d_text or 0, stride, keep
+
+    def align_hits_device_numpy(self, hits, text=False):
+        """Convenience for tests: upload `hits`, pm_align_hits_device, copy the results back.  Returns the alignment
+        array, or (alignments, alignment strings, matching texts) with text=True."""
+        import torch
+        hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+        n = hits.size
+        if n == 0:
+            empty = np.zeros(0, dtype=ALIGNMENT_DTYPE)
+            return (empty, [], []) if text else empty
+        d_hits = torch.from_numpy(hits.view(np.uint8).copy()).cuda()
+        _, _, _, stride, keep = self.align_hits_device(d_hits.data_ptr(), n, text=text)
+        al = keep[0].cpu().numpy().view(ALIGNMENT_DTYPE)[:n].copy()
+        if not text:
+            return al
+        cut = lambda t: [bytes(row).split(b"\0", 1)[0].decode("latin-1") for row in t.cpu().numpy().reshape(n, stride)]
+        return al, cut(keep[1]), cut(keep[2])
+
+    def align_hits_text(self, hits, stride=0):
+        """pm_align_hits_text: (alignments, alignment strings, matching texts) of host records."""
+        hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+        n = hits.size
+        stride = max(int(stride), self._maxlen + self._k + 2)
+        out = np.zeros(n, dtype=ALIGNMENT_DTYPE)
+        ops, txt = C.create_string_buffer(max(n, 1) * stride), C.create_string_buffer(max(n, 1) * stride)
+        if n:
+            self._check(self._L.pm_align_hits_text(self._h, hits.ctypes.data_as(C.c_void_p), n, out.ctypes.data_as(C.c_void_p), ops, txt, stride))
+        cut = lambda b: [b.raw[i * stride:(i + 1) * stride].split(b"\0", 1)[0].decode("latin-1") for i in range(n)]
+        return out, cut(ops), cut(txt)
+
+    # -- the caller's tally loop on the device (primer_match -c) ----------------------------------
+    def count_scan(self, begin, end, max_count=0):
+        """pm_count_scan: the final hits of (begin, end] are re-aligned and tallied in HBM; nothing is handed out."""
+        self._check(self._L.pm_count_scan(self._h, begin, end, int(max_count)))
+        self._pos = min(self._n, max(self._pos, end))
+
+    def counts(self):
+        """pm_counts: (counts uint64[npatterns, k + 1] in add_pattern order, capped uint8[npatterns], info dict)"""
+        counts = np.zeros((self._npat, self._k + 1), dtype=np.uint64)
+        capped = np.zeros(self._npat, dtype=np.uint8)
+        ci = _CountInfo()
+        self._check(self._L.pm_counts(self._h, counts.ctypes.data_as(C.c_void_p), capped.ctypes.data_as(C.c_void_p), self._npat, C.byref(ci)))
+        info = {name: int(getattr(ci, name)) for name in ("tallied", "skipped", "aligned_device", "aligned_host", "bogus", "record_bytes_to_host")}
+        info["first_bogus"] = (int(ci.first_bogus.end), int(ci.first_bogus.pid)) if ci.bogus else None
+        return counts, capped, info
+
+    def count_all(self, max_count=0, chunk=1 << 30):
+        """The tallies of `primer_match -c [-M max_count]` over the whole stream: (counts, capped, info) as counts()."""
+        self.reset()
+        pos = 0
+        while pos < self._n:
+            end = min(self._n, pos + chunk)
+            self.count_scan(pos, end, max_count)
+            pos = end
+        return self.counts()
 
     def selected(self):
         return self._L.pm_selected_semantics(self._h), self._L.pm_selected_kernel(self._h)
