@@ -68,7 +68,9 @@ typedef enum {
 typedef enum {
   PM_KERNEL_AUTO = 0,
   PM_KERNEL_BITPAR = 16,   /* bit-parallel Shift-And / Wu-Manber rows, any alphabet, <= 6 accepted stream codes */
-  PM_KERNEL_SEED = 17      /* 2-bit packed k-mer seeds (LDS filter) + verify; A,C,G,T patterns <= 32 nt */
+  PM_KERNEL_SEED = 17      /* 2-bit packed k-mer seeds (LDS filter) + verify; A,C,G,T patterns <= 32 nt (edit distance,
+                              -k 1 / -k 2 on filter_bitvec or shift_and_inexact: 16..32 nt -- 20..32 on the pair / piece
+                              plans, 16..19 on pm_short_edit_scan) */
 } pm_kernel;
 
 /* Replaces the constructor arguments of the reference engines as pick_pattern_index passes them
@@ -207,7 +209,7 @@ int pm_finalize(pm_handle *h, const pm_hit *cands, size_t n, int64_t scanned_to,
  * pm_scan_candidates), the sort + clustering runs on the GPU and only final hits cross PCIe into
  * `out`.  Available for: exact engines and bare shift_and_inexact (pass-through); filter_bitvec
  * with -K and no exact-base constraints (sort + segmented pass), and with -k on the seed family
- * (A,C,G,T patterns of 20..32 characters, k <= 2: clusters and their DPs on the GPU against the
+ * (A,C,G,T patterns of 16..32 characters, k <= 2: clusters and their DPs on the GPU against the
  * text in HBM); exact_halves on the seed family (exact_halves.cc:142,163,178: its per-pattern
  * "end beyond the last kept end" rule as a sort + one walk per pattern -- stateless, so only with
  * PM_FINALIZE_LAST on an engine state that is fresh since pm_init / pm_reset).

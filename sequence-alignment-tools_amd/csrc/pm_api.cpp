@@ -182,6 +182,12 @@ struct pm_handle {
   size_t vals_cap = 0, htemp_bytes = 0;
   std::vector<uint8_t> in_rest;       // per inner pattern: 1 = scanned by the bit-parallel residue engine beside the seed family
   size_t nrest = 0;
+  // edit-distance plan, patterns of 16..19 characters: a class of their own beside the 20..32 character main class and the
+  // residue (pm_short.hip).  Its device state lives here, not in sd_more: the main class keeps its one-tile plans.
+  std::vector<uint8_t> in_short;      // per inner pattern: 1 = scanned by pm_short_edit_scan
+  size_t nshort = 0;
+  bool short_only = false;            // no main class: the short engine is the handle's whole device stage
+  ShortDevice shd;
   bool halves_fresh = true;           // no host-side exact_halves state (lasthit, carried seeds) since init / pm_reset
 
   // windowed stream (pm_init_windowed): d_text / d_packed point at the bound slot, rebased so that absolute stream
@@ -224,7 +230,9 @@ struct pm_handle {
 };
 
 // per-tile record counts between a scan's first-stage and verify kernels: [0] unused, [1 + t] tile t, then 8 measurement counters
-constexpr size_t SEEDCOUNT_WORDS = 1 + 256 + 8;
+// [SHORT_COUNT_AT]: seed records of the short class (all its tiles)
+constexpr size_t SEEDCOUNT_WORDS = 1 + 256 + 8 + 1;
+constexpr size_t SHORT_COUNT_AT = 1 + 256 + 8;
 
 static thread_local std::string g_create_error;
 
@@ -374,6 +382,7 @@ static void read_knobs(Knobs *k) {
   if (const char *v = getenv("PM_BITPAR_TP")) k->bitpar_tp = atoi(v) != 0;
   k->bitpar_seglen = num("PM_BITPAR_SEGLEN");
   k->dense_bound = num("PM_DENSE_BOUND");
+  k->short_bitpar = is("PM_SHORT_SCAN", "bitpar"); k->short_tile = (long)num("PM_SHORT_TILE");
   k->debug = getenv("PM_DEBUG") != nullptr;
 }
 
@@ -426,6 +435,7 @@ static void free_device(pm_handle *h) {
   if (h->d_fsorted) (void)hipFree(h->d_fsorted);
   h->d_fsorted = nullptr; h->fsorted_cap = 0;
   bitpar_free(&h->bp);
+  short_free(&h->shd);
   seed_free(&h->sd);
   for (SeedDevice &d : h->sd_more) seed_free(&d);
   h->sd_more.clear();
@@ -599,8 +609,9 @@ static bool seed_eligible(pm_handle *h, std::string *why) {
     if (h->cfg.k > 2) { *why = "edit distance > 2 runs on the bit-parallel family"; return false; }
     for (size_t i = 0; i < h->pats.size(); ++i) {
       if (i < h->in_rest.size() && h->in_rest[i]) continue;         // goes to the bit-parallel residue
+      if (i < h->in_short.size() && h->in_short[i]) continue;       // 16..19 characters: pm_short_edit_scan
       const Pattern &p = h->pats[i];
-      if (p.s.size() > 32 || p.s.size() < 20) { *why = "the edit-distance seed plan needs 20..32 character patterns"; return false; }
+      if (p.s.size() > 32 || p.s.size() < 20) { *why = "the edit-distance seed plan needs 16..32 character patterns"; return false; }
     }
     for (uint32_t id : h->inner_ids) if (id >= (1u << 22)) { *why = "the edit-distance seed plan packs pattern ids into 22 bits"; return false; }
     return true;
@@ -650,7 +661,7 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
   h->eos_code = h->alpha.nch[(uint8_t)h->cfg.eos];                  // shift_and_inexact.cc:131
   int rc = resolve(h);
   if (rc) return rc;
-  bitpar_free(&h->bp); seed_free(&h->sd);
+  bitpar_free(&h->bp); seed_free(&h->sd); short_free(&h->shd);
   for (SeedDevice &d : h->sd_more) seed_free(&d);
   h->sd_more.clear();
   for (PairDevice &d : h->pair) pair_free(&d);
@@ -676,7 +687,10 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
   // the bit-parallel kernels into the same record buffer and the rest stays on the seed family.
   h->in_rest.assign(h->inner.size(), 0);
   h->nrest = 0;
+  h->in_short.assign(h->inner.size(), 0);
+  h->nshort = 0; h->short_only = false;
   const bool edits_plan = h->cfg.indels && h->cfg.k > 0 && (h->sem == PM_SEM_FILTER_BITVEC || h->sem == PM_SEM_SHIFT_AND_INEXACT);
+  const bool short_class = edits_plan && h->cfg.k <= 2 && !h->knobs.short_bitpar;   // patterns of 16..19 characters: pm_short_edit_scan
   h->wild_seed = h->cfg.wildcards && want_seed && h->kern == PM_KERNEL_AUTO && stream_letters_plain(h) &&
                  (h->sem == PM_SEM_KEYWORD_TREE || h->sem == PM_SEM_SHIFT_AND || h->sem == PM_SEM_FILTER_BITVEC);
   if (want_seed && (!h->cfg.wildcards || h->wild_seed) && h->kern == PM_KERNEL_AUTO &&
@@ -684,14 +698,30 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
     std::vector<std::string> variants;
     for (size_t i = 0; i < h->inner.size(); ++i) {
       const std::string &ps = h->inner[i].s;
-      bool ok = ps.size() <= 32 && ps.size() >= (edits_plan ? 20u : 10u);
+      const bool is_short = short_class && ps.size() >= 16 && ps.size() <= 19;   // otherwise under exactly the main class's conditions
+      bool ok = (ps.size() <= 32 && ps.size() >= (edits_plan ? 20u : 10u)) || is_short;
       if (h->wild_seed) ok = ok && expand_iupac(ps, 16, &variants) &&   // up to two ambiguity letters (16 variants)
                          !(h->sem == PM_SEM_FILTER_BITVEC && pattern_n_quirk(h, h->inner[i]));   // (its value needs the text-based verify)
       else for (unsigned char ch : ps) ok = ok && (ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T');
       if (!ok) { h->in_rest[i] = 1; ++h->nrest; }
+      else if (is_short) { h->in_short[i] = 1; ++h->nshort; }
     }
-    if (h->nrest == h->inner.size()) { std::fill(h->in_rest.begin(), h->in_rest.end(), 0); h->nrest = 0; }   // nothing for the seed family: one engine
+    // nothing for the main class and something for the residue: one engine, the bit-parallel family
+    if (h->nrest && h->nrest + h->nshort == h->inner.size()) {
+      std::fill(h->in_rest.begin(), h->in_rest.end(), 0); h->nrest = 0;
+      std::fill(h->in_short.begin(), h->in_short.end(), 0); h->nshort = 0;
+    }
   }
+  else if (short_class && h->kern == PM_KERNEL_SEED && !h->cfg.wildcards) {
+    // the seed family on request: no residue, but the two length classes of the edit plan
+    for (size_t i = 0; i < h->inner.size(); ++i) {
+      const std::string &ps = h->inner[i].s;
+      bool ok = ps.size() >= 16 && ps.size() <= 19;
+      for (unsigned char ch : ps) ok = ok && (ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T');
+      if (ok) { h->in_short[i] = 1; ++h->nshort; }
+    }
+  }
+  h->short_only = h->nshort != 0 && h->nshort == h->inner.size();
   if (want_seed && !seed_eligible(h, &why)) {
     if (h->kern == PM_KERNEL_SEED) return fail(h, PM_E_UNSUPPORTED, "seed engine: " + why);
     want_seed = false;
@@ -722,13 +752,13 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
     } else if (h->wild_seed) {                    // every concrete variant of a primer is a seed-family pattern with the primer's id
       std::vector<std::string> variants;
       for (size_t i = 0; i < h->inner.size(); ++i) {
-        if (h->in_rest[i]) continue;
+        if (h->in_rest[i] || h->in_short[i]) continue;
         expand_iupac(h->inner[i].s, 16, &variants);
         for (const std::string &v : variants) { Pattern q = h->inner[i]; q.s = v; sp.push_back(q); sid.push_back(h->inner_ids[i]); }
       }
-      if (sp.empty()) { sp.push_back(Pattern{std::string(edits_mode ? 20 : 10, 'A'), 0, 0, 0}); sid.push_back(0); why = "no primer the seed family could take"; }
-    } else if (h->nrest) {
-      for (size_t i = 0; i < h->inner.size(); ++i) if (!h->in_rest[i]) { sp.push_back(h->inner[i]); sid.push_back(h->inner_ids[i]); }
+      if (sp.empty() && !h->short_only) { sp.push_back(Pattern{std::string(edits_mode ? 20 : 10, 'A'), 0, 0, 0}); sid.push_back(0); why = "no primer the seed family could take"; }
+    } else if (h->nrest || h->nshort) {
+      for (size_t i = 0; i < h->inner.size(); ++i) if (!h->in_rest[i] && !h->in_short[i]) { sp.push_back(h->inner[i]); sid.push_back(h->inner_ids[i]); }
     } else { sp = h->inner; sid = h->inner_ids; }
     // the automata and the keyword tree know nothing of exact_start_bases / exact_end_bases (shift_and_inexact.cc:85-86
     // stores them and never looks): their records are every window within k, whatever zone a substitution falls in
@@ -782,7 +812,7 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
       h->sd.k = sk; h->sd.Lw = 20; h->sd.pb = 5; h->sd.r = 4 - sk; h->sd.ncombos = pt.ncombos; h->sd.ascii = pt.ascii;
       h->sd.maxlen = std::max(h->sd.maxlen, pt.maxlen);
     }
-    for (size_t ti = 0; ti < ntile && why.empty() && !use_pair; ++ti) {
+    for (size_t ti = 0; ti < ntile && why.empty() && !use_pair && !h->short_only; ++ti) {
       const size_t lo = ti * per, hi = std::min(sp.size(), lo + per);
       std::vector<Pattern> tp(sp.begin() + lo, sp.begin() + hi);
       std::vector<uint32_t> tid(sid.begin() + lo, sid.begin() + hi);
@@ -800,10 +830,29 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
       dst->knobs = h->knobs;
       dst->maxlen = std::max(dst->maxlen, h->sd.maxlen);
     }
+    if (why.empty() && h->nshort) {                                 // the short class beside (or instead of) the main class
+      std::vector<Pattern> shp; std::vector<uint32_t> shid;
+      std::vector<std::string> variants;
+      for (size_t i = 0; i < h->inner.size(); ++i) {
+        if (!h->in_short[i]) continue;
+        if (h->wild_seed) {                                           // as in the main class: every concrete variant with the primer's id
+          expand_iupac(h->inner[i].s, 16, &variants);
+          for (const std::string &v : variants) { Pattern q = h->inner[i]; q.s = v; shp.push_back(q); shid.push_back(h->inner_ids[i]); }
+        } else { shp.push_back(h->inner[i]); shid.push_back(h->inner_ids[i]); }
+      }
+      ShortTables stt;
+      why = short_build(shp, shid, h->alpha, sk, h->eos_code, h->knobs.short_tile > 0 ? (size_t)h->knobs.short_tile : 0, &stt);
+      if (why.empty() && stt.tiles.size() > 256) why = "too many pattern tiles for pm_short_edit_scan";
+      if (why.empty()) {
+        HIP_TRY(h, short_upload(stt, &h->shd, h->stream));
+        if (h->short_only) { h->sd.k = sk; h->sd.Lw = 16; h->sd.ascii = stt.ascii; h->sd.maxlen = stt.maxlen; }   // (the plan facts the rest of this file reads from h->sd)
+      }
+    }
     if (!why.empty()) {
       seed_free(&h->sd);
       for (SeedDevice &d : h->sd_more) seed_free(&d);
       h->sd_more.clear();
+      short_free(&h->shd);
       if (h->kern == PM_KERNEL_SEED) return fail(h, PM_E_UNSUPPORTED, "seed engine: " + why);
       want_seed = false;
     } else {
@@ -866,6 +915,7 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
   if (!want_seed) {
     h->halves_dev = false; h->edits_dev = false; h->half_ranked_any = false;
     std::fill(h->in_rest.begin(), h->in_rest.end(), 0); h->nrest = 0;
+    std::fill(h->in_short.begin(), h->in_short.end(), 0); h->nshort = 0; h->short_only = false;
     h->kern = PM_KERNEL_BITPAR;
     BitparTables tabs;
     std::string msg = bitpar_build(h->inner, h->inner_ids, h->alpha, h->scan_k, h->eos_code, &tabs,
@@ -1413,7 +1463,10 @@ static const char *pair_schedule_name(const ScanGeometry &g) {
 
 extern "C" int pm_describe(const pm_handle *h, char *buf, size_t buflen) {
   if (!h || !buf || !h->inited) return PM_E_INVALID;
-  if (h->kern == PM_KERNEL_SEED && !h->pair.empty()) {
+  if (h->kern == PM_KERNEL_SEED && h->short_only)
+    snprintf(buf, buflen, "kernel=pm_short_edit_scan+pm_edits_verify for %zu patterns of 16..19 characters (tiles=%d, tests=%d) fields=2-of-4 x 4 bases, displaced by |d| <= %d window=16 chunk=%lld nchunks=%d grid=%d block=%d",
+             h->nshort, (int)h->shd.tiles.size(), h->shd.k == 2 ? SHORT_NTESTS : 2, h->shd.k, (long long)h->geo.seg_len, h->geo.nseg, h->geo.blocks, h->geo.threads);
+  else if (h->kern == PM_KERNEL_SEED && !h->pair.empty()) {
     snprintf(buf, buflen, "kernel=pm_pair_scan tiles=%d combos=%d fields=2-of-4 x 5 bases window=20 row_slots=%d chunk=%lld nchunks=%d grid=%d block=%d lds=%d schedule=%s",
              (int)h->pair.size(), h->pair[0].ncombos, h->pair[0].stride, (long long)h->geo.seg_len, h->geo.nseg, h->geo.blocks, h->geo.threads, PAIR_LDS_BYTES,
              pair_schedule_name(h->geo));
@@ -1440,6 +1493,11 @@ extern "C" int pm_describe(const pm_handle *h, char *buf, size_t buflen) {
       if (at < buflen) snprintf(buf + at, buflen - at, " + %s for %zu patterns the seed plan does not take", bitpar_kernel_name(h->scan_k, h->scan_indels), h->nrest);
     }
   }
+  if (h->kern == PM_KERNEL_SEED && h->nshort && !h->short_only) {
+    const size_t at = strlen(buf);
+    if (at < buflen) snprintf(buf + at, buflen - at, " + pm_short_edit_scan for %zu patterns of 16..19 characters (tiles=%d, tests=%d)", h->nshort, (int)h->shd.tiles.size(), h->shd.k == 2 ? SHORT_NTESTS : 2);
+  }
+  if (h->kern == PM_KERNEL_SEED) return PM_OK;
   else
     snprintf(buf, buflen, "kernel=%s tiles=%d lanes_per_tile=64 words_per_lane=%d seg_len=%lld nseg=%d grid=%d block=%d",
              bitpar_kernel_name(h->scan_k, h->scan_indels), h->bp.ntiles, BP_WPL, (long long)h->geo.seg_len, h->geo.nseg,
@@ -1484,7 +1542,7 @@ extern "C" int pm_scan_candidates_async(pm_handle *h, int64_t begin, int64_t end
       HIP_TRY(h, hipMalloc((void **)&h->d_seeds, h->seed_cap * sizeof(uint64_t)));
     }
     if (!h->d_seed_count) HIP_TRY(h, hipMalloc((void **)&h->d_seed_count, SEEDCOUNT_WORDS * sizeof(unsigned long long)));
-    const int ntiles = 1 + (int)h->sd_more.size();
+    const int ntiles = h->short_only ? 0 : 1 + (int)h->sd_more.size();
     if (ntiles > 256) return fail(h, PM_E_UNSUPPORTED, "too many pattern tiles for the edit-distance plan");
     HIP_TRY(h, hipMemsetAsync(h->d_seed_count, 0, SEEDCOUNT_WORDS * sizeof(unsigned long long), h->stream));
     for (int t = 0; t < ntiles; ++t) {
@@ -1508,8 +1566,15 @@ extern "C" int pm_scan_candidates_async(pm_handle *h, int64_t begin, int64_t end
       }
       HIP_TRY(h, seed_launch(d, h->d_text, h->d_packed, h->n, begin, end, h->d_cands, h->d_counter, h->cap, h->stream, t == 0 && !es.skip_scan ? &h->geo : nullptr, &es));
     }
-    HIP_TRY(h, hipMemcpyAsync(h->h_seed_count, h->d_seed_count, SEEDCOUNT_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
     h->last_launches = 2 * ntiles + (h->epair_on && h->edits_dev ? 1 : 0);
+    if (h->nshort) {
+      // the short class into the same record buffer; its seed records reuse the seed list, which the main class's automaton
+      // launch has read by then (stream order), under a counter of their own
+      HIP_TRY(h, short_launch(h->shd, h->d_text, h->d_packed, h->n, begin, end, h->d_cands, h->d_counter, h->cap, h->d_seeds, h->d_seed_count + SHORT_COUNT_AT,
+                              h->seed_cap, h->stream, h->short_only ? &h->geo : nullptr));
+      h->last_launches += (int)h->shd.tiles.size() + 1;
+    }
+    HIP_TRY(h, hipMemcpyAsync(h->h_seed_count, h->d_seed_count, SEEDCOUNT_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
     if (h->nrest) { HIP_TRY(h, bitpar_launch(h->bp, h->d_text, h->n, begin, end, h->d_cands, h->d_counter, h->cap, h->stream, nullptr)); ++h->last_launches; }
   }
   else if (h->kern == PM_KERNEL_SEED && !h->pair.empty())
@@ -1596,6 +1661,7 @@ static int edits_start_candidates(pm_handle *h, std::vector<pm_hit> *out) {
   { const int rc = host_codes(h, 0, T, head); if (rc) return rc; }
   for (size_t j = 0; j < h->inner.size(); ++j) {
     if (j < h->in_rest.size() && h->in_rest[j]) continue;           // the residue engine reports its own
+    if (j < h->in_short.size() && h->in_short[j]) continue;         // and so does pm_short_edit_scan
     const std::string &s = h->inner[j].s;
     const int L = (int)s.size();
     uint64_t R[3] = {0, 1, 3};
@@ -1646,6 +1712,7 @@ static int edits_end_candidates(pm_handle *h, std::vector<pm_hit> *extra) {
   std::vector<pm_hit> all;
   for (size_t j = 0; j < h->inner.size(); ++j) {
     if (j < h->in_rest.size() && h->in_rest[j]) continue;           // the residue engine reports its own
+    if (j < h->in_short.size() && h->in_short[j]) continue;         // and so does pm_short_edit_scan
     const std::string &s = h->inner[j].s;
     const int L = (int)s.size();
     const int64_t Tj = std::min<int64_t>(T, L + k + 8);
@@ -1692,6 +1759,7 @@ static int stream_start_candidates(pm_handle *h) {
   extra.clear();
   for (size_t j = 0; j < h->inner.size(); ++j) {
     if (j < h->in_rest.size() && h->in_rest[j]) continue;           // the residue engine reports its own
+    if (j < h->in_short.size() && h->in_short[j]) continue;         // and so does pm_short_edit_scan
     const std::string &s = h->inner[j].s;
     const int L = (int)s.size();
     for (int d = 1; d <= k && d < L; ++d) {
@@ -1859,6 +1927,7 @@ static int scan_wait_once(pm_handle *h, size_t *n_out) {
     const size_t tiles = !h->pair.empty() ? h->pair.size() : 1 + h->sd_more.size();
     for (size_t t = 0; t < tiles && t < 256; ++t) h->last_peak = std::max(h->last_peak, h->h_seed_count[1 + t]);
     h->last_peak = std::max(h->last_peak, h->h_seed_count[260]);
+    if (h->nshort) h->last_peak = std::max(h->last_peak, h->h_seed_count[SHORT_COUNT_AT]);
   }
   if (h->bound_on && cnt > dense_bound(h)) return dense_fail(h, "candidate records", cnt);
   if (cnt > h->cap) { h->last_count = 0; return fail(h, PM_E_OVERFLOW, "candidate buffer too small (pm_set_capacity)"); }
@@ -1867,6 +1936,7 @@ static int scan_wait_once(pm_handle *h, size_t *n_out) {
     // the seed buffer of a tile must have held all its seed records
     unsigned long long worst = 0;
     for (int t = 0; t < 1 + (int)h->sd_more.size(); ++t) worst = std::max(worst, h->h_seed_count[1 + t]);
+    if (h->nshort) worst = std::max(worst, h->h_seed_count[SHORT_COUNT_AT]);
     if (h->knobs.debug) fprintf(stderr, "[pm] %s: %llu seed records (tile with most), seed cap %zu, candidates %zu\n", h->edits_dev ? "edits" : "halves", worst, h->seed_cap, cnt);
     if (h->bound_on && worst > dense_bound(h)) return dense_fail(h, "seed records of the edit-distance plan", worst);
     if (worst > h->seed_cap) {                                     // grow the seed buffer and tell the caller to scan again
@@ -2041,6 +2111,7 @@ extern "C" int pm_scan_stats(pm_handle *h, uint64_t *out, int n) {
   if (h->h_seed_count) {
     const size_t tiles = !h->pair.empty() ? h->pair.size() : 1 + h->sd_more.size();
     for (size_t t = 0; t < tiles && t < 256; ++t) v[1] = std::max<uint64_t>(v[1], h->h_seed_count[1 + t]);
+    if (h->nshort) v[1] += h->h_seed_count[SHORT_COUNT_AT];       // (+ the short class's seed records)
     v[3] = h->h_seed_count[257]; v[4] = h->h_seed_count[258]; v[5] = h->h_seed_count[259];
   }
   v[2] = h->internal_rescans;

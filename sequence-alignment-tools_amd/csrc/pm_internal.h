@@ -28,7 +28,7 @@ struct Alphabet {
 };
 
 // Test and measurement knobs (PM_SEED_CHUNK, PM_SEED_GROUP, PM_SEED_DEBUG, PM_SEED_TILE, PM_PAIR, PM_PAIR_ROW, PM_PAIR_MAP, PM_HALF_SCAN,
-// PM_EDIT_SCAN, PM_EDIT_TABLE_LOG, PM_BITPAR_TP, PM_BITPAR_SEGLEN, PM_DEBUG).  The environment is read ONCE, by
+// PM_EDIT_SCAN, PM_EDIT_TABLE_LOG, PM_SHORT_SCAN, PM_SHORT_TILE, PM_BITPAR_TP, PM_BITPAR_SEGLEN, PM_DEBUG).  The environment is read ONCE, by
 // pm_create (pm_api.cpp read_knobs), into the handle: nothing on the init or launch path calls getenv, and a
 // handle's behaviour does not change when its caller's environment does.  Every field's 0 / -1 / false = unset.
 struct Knobs {
@@ -46,6 +46,8 @@ struct Knobs {
   int bitpar_tp = -1;                // force the text-parallel (1) / tile (0) form of the bit-parallel kernel
   long long bitpar_seglen = 0;
   long long dense_bound = 0;         // PM_DENSE_BOUND: records per list beyond which pm_scan cuts a range in two (0: 2^29)
+  bool short_bitpar = false;         // PM_SHORT_SCAN=bitpar: patterns of 16..19 characters go to the bit-parallel residue, not to pm_short_edit_scan
+  long short_tile = 0;               // PM_SHORT_TILE: patterns per tile of pm_short_edit_scan
   bool debug = false;                // PM_DEBUG: stage timings on stderr
 };
 
@@ -179,6 +181,48 @@ hipError_t align_scatter_device(const uint64_t *d_idx, size_t m, const pm_alignm
 size_t tally_temp_bytes(size_t n);
 hipError_t tally_device(const AlignDevice &a, uint64_t *d_keys, uint64_t *d_keys_alt, uint64_t *d_scan, size_t n, void *d_temp, size_t temp_bytes,
                         uint64_t max_count, unsigned long long *d_counts, unsigned long long *d_info, hipStream_t st);
+
+// ---- edit distance for patterns of 16..19 characters (pm_short.hip) ------------------------------
+// First stage pm_short_edit_scan (field pairs of the last 16 bases, 14 tests at k = 2, 2 at k = 1) + the automaton stage of
+// pm_seed.hip over its seed records.  A class is cut into tiles of at most `tile` patterns (the 16-bit key space fills up):
+// one launch per tile into the same seed list, one automaton launch behind them.
+constexpr int SHORT_NTESTS = 14;
+constexpr size_t SHORT_TILE_DEFAULT = 32768;
+
+struct ShortTables {               // host-built, then uploaded
+  int k = 0, maxlen = 0, eos_code = -1;
+  bool ascii = false;
+  std::vector<uint8_t> records;    // 32-byte automaton record per pattern of the class (pm_seed.h edit_record_fill)
+  struct Tile {
+    uint32_t base = 0;             // class index of the tile's first pattern
+    std::vector<uint32_t> bitmap;  // [field pair][2048]: bit = 16-bit key of some pattern
+    std::vector<uint32_t> rows;    // [field pair][65537]: first entry of the key's run in runs
+    std::vector<uint32_t> runs;    // [field pair][patterns of the tile]: pattern indices (inside the tile) by key
+    std::vector<uint32_t> pat16;   // last 16 bases of every pattern, 2 bits each
+  };
+  std::vector<Tile> tiles;
+};
+
+struct ShortDevice {
+  int k = 0, maxlen = 0, eos_code = -1;
+  bool ascii = false;
+  size_t npat = 0;
+  uint8_t *records = nullptr;
+  struct Tile { uint32_t base = 0; uint32_t *bitmap = nullptr, *rows = nullptr, *runs = nullptr, *pat16 = nullptr; };
+  std::vector<Tile> tiles;
+};
+
+// Build the tables of the class (`tile` = patterns per tile, 0: SHORT_TILE_DEFAULT).  Returns "" or an error message.
+std::string short_build(const std::vector<Pattern> &pats, const std::vector<uint32_t> &ids, const Alphabet &alpha, int k, int eos_code,
+                        size_t tile, ShortTables *out);
+hipError_t short_upload(const ShortTables &t, ShortDevice *d, hipStream_t st);
+void short_free(ShortDevice *d);
+// Enqueue the scan of (begin, end] on `st`: candidate records are appended to d_out / d_counter like bitpar_launch's; the seed
+// records in between go to d_seeds[0 .. seed_cap), counted in *d_seed_count (zeroed by the caller; it may exceed seed_cap:
+// the caller grows the list and scans again).  d_packed: the stream's 2-bit words (pack_stream).
+hipError_t short_launch(const ShortDevice &d, const uint8_t *d_text, const uint32_t *d_packed, int64_t n, int64_t begin, int64_t end,
+                        pm_hit *d_out, unsigned long long *d_counter, uint64_t cap, uint64_t *d_seeds, unsigned long long *d_seed_count,
+                        uint64_t seed_cap, hipStream_t st, ScanGeometry *geo_out);
 
 // ---- seed extension DP on the GPU (pm_extend.hip) ---------------------------------------------
 hipError_t extend_seeds(const uint8_t *d_text, int64_t n, const pm_hit *d_seeds, size_t nseeds,

@@ -99,4 +99,11 @@ hipError_t seed_launch(const SeedDevice &d, const uint8_t *d_text, const uint32_
                        pm_hit *d_out, unsigned long long *d_counter, uint64_t cap, hipStream_t st,
                        ScanGeometry *geo_out, const EditStage *es = nullptr);
 
+
+// the automaton stage of the edit-distance plan on its own (first stages outside pm_seed.hip: pm_short.hip)
+void edit_record_fill(const std::string &s, uint32_t id, uint8_t *rec);
+hipError_t edits_verify_launch(const uint8_t *d_records, int k, int maxlen, bool ascii, int eos_code, const uint8_t *d_text, int64_t n,
+                               int64_t begin, int64_t end, const uint64_t *d_seeds, const unsigned long long *d_seed_count, uint64_t seed_cap,
+                               pm_hit *d_out, unsigned long long *d_counter, uint64_t cap, hipStream_t st);
+
 }  // namespace pm

@@ -1915,6 +1915,34 @@ static void edit_cover(int k, int m, const std::vector<std::array<int, 4>> &comb
   }
 }
 
+// The 32-byte automaton record edits_verify reads: masks of A, C, G, T over the pattern positions | length | id.
+void edit_record_fill(const std::string &s, uint32_t id, uint8_t *rec) {
+  uint32_t M[4] = {0, 0, 0, 0};
+  for (size_t i = 0; i < s.size() && i < 32; ++i) {
+    const char *at = strchr("ACGT", s[i]);
+    if (at && s[i]) M[at - "ACGT"] |= 1u << i;
+  }
+  const uint32_t len = (uint32_t)s.size();
+  memcpy(rec, M, 16); memcpy(rec + 16, &len, 4); memcpy(rec + 20, &id, 4); memset(rec + 24, 0, 8);
+}
+
+// pm_edits_verify alone, for a first stage that lives in another file (pm_short.hip): one automaton run per seed record
+// (pattern index << 40 | position, ~0 = unused slot) of d_seeds[0 .. min(*d_seed_count, seed_cap)) over the records
+// d_records[pattern index] (edit_record_fill); ends in (begin, end] leave as candidate records.
+hipError_t edits_verify_launch(const uint8_t *d_records, int k, int maxlen, bool ascii, int eos_code, const uint8_t *d_text, int64_t n,
+                               int64_t begin, int64_t end, const uint64_t *d_seeds, const unsigned long long *d_seed_count, uint64_t seed_cap,
+                               pm_hit *d_out, unsigned long long *d_counter, uint64_t cap, hipStream_t st) {
+  if (!d_records || !d_seeds || !d_seed_count || k < 1 || k > 2 || maxlen < 1 || maxlen > 32) return hipErrorInvalidValue;
+  EditVerifyArgs v;
+  memset(&v, 0, sizeof(v));
+  v.a.text = d_text; v.a.n = n; v.a.begin = begin; v.a.end = end > n ? n : end;
+  v.a.pat_codes = d_records; v.a.ascii = ascii ? 1 : 0; v.a.eos_code = eos_code; v.a.edits = k; v.a.k = k; v.a.maxlen = maxlen;
+  v.a.out = d_out; v.a.counter = d_counter; v.a.cap = cap;
+  v.seeds = d_seeds; v.nseeds = d_seed_count; v.seed_cap = seed_cap;
+  hipLaunchKernelGGL(pm_edits_verify, dim3(256 * 16), dim3(256), 0, st, v);
+  return hipGetLastError();
+}
+
 std::string seed_build(const std::vector<Pattern> &pats, const std::vector<uint32_t> &ids,
                        const Alphabet &alpha, int k, int eos_code, SeedTables *out, int force_lmin,
                        const std::vector<std::string> *partners, const std::vector<uint8_t> *sides, int halves_k, bool edits, const Knobs &knobs) {
@@ -2049,13 +2077,7 @@ std::string seed_build(const std::vector<Pattern> &pats, const std::vector<uint3
     t.pat_len[j] = (uint8_t)L;
     t.pat_id[j] = ids[j];
     for (int i = 0; i < L; ++i) t.pat_codes[j * 32 + i] = (uint8_t)alpha.nch[(unsigned char)s[i]];
-    if (edits) {                                   // the row becomes the automaton record edits_verify reads
-      uint32_t M[4] = {0, 0, 0, 0};
-      for (int i = 0; i < L; ++i) M[base2((unsigned char)s[i]) ^ (t.ascii && base2((unsigned char)s[i]) >= 2 ? 1 : 0)] |= 1u << i;   // A,C,G,T order
-      uint8_t *rec = &t.pat_codes[j * 32];
-      const uint32_t len = (uint32_t)L, idv = ids[j];
-      memcpy(rec, M, 16); memcpy(rec + 16, &len, 4); memcpy(rec + 20, &idv, 4); memset(rec + 24, 0, 8);
-    }
+    if (edits) edit_record_fill(s, ids[j], &t.pat_codes[j * 32]);   // the row becomes the automaton record edits_verify reads
     if (partners) {                                // halves: the row doubles as the 32-byte record verify_half reads
       if (L > 16) return "exact_halves half longer than 16 characters";
       uint8_t *rec = &t.pat_codes[j * 32];
