@@ -103,7 +103,10 @@ int pm_add_pattern(pm_handle *h, const char *pat, size_t len, uint64_t id, int32
 int pm_init(pm_handle *h, const uint8_t *text, int64_t n, const uint8_t *table, int32_t table_len);
 
 /* Same, for a stream that is already resident in HBM (borrowed; 4-byte aligned).  `hip_stream`
- * is a hipStream_t (NULL = default stream) on which all work of this handle is enqueued. */
+ * is a hipStream_t (NULL = default stream) on which all work of this handle is enqueued.  pm_scan / pm_scan_view may
+ * return with a scan of the next range in flight on it (see pm_scan_view), so d_text must stay valid and unchanged
+ * until pm_reset or pm_destroy has returned, or the next scan, finalize or pm_candidates_device call on the handle has:
+ * each of them waits for that scan first.  Do not free or rewrite the text straight after the last pm_scan. */
 int pm_init_device(pm_handle *h, const void *d_text, int64_t n, const uint8_t *table, int32_t table_len,
                    void *hip_stream);
 
@@ -176,7 +179,9 @@ int pm_scan(pm_handle *h, int64_t begin, int64_t end, pm_hit *out, size_t cap, s
  * straight from this span.  Both forms share one pipeline: when the finalize stage of the option set runs on the GPU, the
  * scan of the range expected next (the same number of stream bytes, as primer_match.cc:1118's loop walks the stream) is
  * enqueued before the call returns, and the copy out of HBM, the caller's work on the hits and its next call overlap it.
- * A different next range, pm_reset or pm_destroy simply let that scan finish unused. */
+ * A different next range, pm_reset or pm_destroy simply let that scan finish unused.  So both forms may return with a
+ * scan in flight on the handle's stream: it reads the stream text and refills the handle's record buffer, never the
+ * memory the hits were handed out in (pm_scan_stats out[7] counts these scans). */
 int pm_scan_view(pm_handle *h, int64_t begin, int64_t end, const pm_hit **hits, size_t *n);
 
 /* Device stage only, position-independent (what shards across GPUs): candidate records for
@@ -189,7 +194,8 @@ int pm_scan_candidates(pm_handle *h, int64_t begin, int64_t end, pm_hit *out, si
 int pm_scan_candidates_async(pm_handle *h, int64_t begin, int64_t end);
 int pm_scan_wait(pm_handle *h, size_t *n_out);
 
-/* HBM address of the records of the last pm_scan_candidates (for an RCCL gather) */
+/* HBM address of the records of the last pm_scan_candidates (for an RCCL gather).  After pm_scan / pm_scan_view the
+ * buffer is not the caller's: the call waits for a look-ahead scan they left in flight, drops it and reports *n = 0. */
 int pm_candidates_device(pm_handle *h, void **d_records, size_t *n);
 int pm_set_capacity(pm_handle *h, size_t max_candidates);
 
@@ -332,7 +338,9 @@ int pm_last_kernel_time(pm_handle *h, float *ms, int *launches);
  * because an internal buffer was too small (pm_last_kernel_time then covers every attempt); with PM_SEED_DEBUG bit 5 set
  * on the pair plan also out[3] blocks of 1024 positions, out[4] rounds of its second pass, out[5] key hits, summed over
  * waves and field pairs; out[6] times pm_scan halved its piece length since pm_init because a range's record lists would have
- * outgrown its bound (hit-dense text).  n <= 8 values are written. */
+ * outgrown its bound (hit-dense text); out[7] look-ahead scans pm_scan / pm_scan_view enqueued since pm_init for the range
+ * they expected next (see pm_scan_view).  While such a scan is in flight the call waits for it (it stays pm_scan's to
+ * collect): out[1] and out[3..5] are then that scan's, out[0] the range's that was handed out.  n <= 8 values are written. */
 int pm_scan_stats(pm_handle *h, uint64_t *out, int n);
 
 /* Measurement helper (no reference counterpart; DESIGN.md 4.6 "pair geometry for edits"): on a -K 2 handle of the pair plan,

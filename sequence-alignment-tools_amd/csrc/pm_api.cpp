@@ -137,6 +137,7 @@ struct pm_handle {
   int64_t piece_len = 0;                     // pm_scan scans in pieces of at most this many positions (0: whole ranges)
   unsigned long long last_peak = 0;          // longest record list of the last scan
   unsigned long long range_splits = 0;       // times pm_scan halved its piece length since pm_init
+  unsigned long long lookaheads = 0;         // scans pm_scan enqueued for the range it expected next, since pm_init
   ScanGeometry geo{};
 
   // host stage state
@@ -614,6 +615,13 @@ static bool seed_eligible(pm_handle *h, std::string *why) {
       if (p.s.size() > 32 || p.s.size() < 20) { *why = "the edit-distance seed plan needs 16..32 character patterns"; return false; }
     }
     for (uint32_t id : h->inner_ids) if (id >= (1u << 22)) { *why = "the edit-distance seed plan packs pattern ids into 22 bits"; return false; }
+    if (sem == PM_SEM_SHIFT_AND_INEXACT) {
+      // its records carry the pattern's id and the dedup keeps one per (id, end); the automaton reports every pattern on its
+      // own (shift_and_inexact.cc:316-335), so two patterns under one id that end at the same character are two hits
+      std::vector<uint32_t> ids(h->inner_ids);
+      std::sort(ids.begin(), ids.end());
+      if (std::adjacent_find(ids.begin(), ids.end()) != ids.end()) { *why = "patterns that share an id: the edit-distance seed plan keeps one record per (id, end)"; return false; }
+    }
     return true;
   }
   if (h->cfg.k > 0 && h->cfg.indels && sem == PM_SEM_EXACT_BASES) {
@@ -943,7 +951,7 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
   // pm_scan's landing buffer for a database-sized stream: pinned now, beside the upload, rather than inside the first range
   // (2^20 records = 16 MiB take ~5 ms to pin; a 1 GiB range of uniform text hands back 3.3e5 -K 2 hits, 1.2e6 with -k 2)
   if (!h->host_only && h->n >= ((int64_t)1 << 28) && h->land_cap < ((size_t)1 << 20)) { rc = ensure_landing(h, (size_t)1 << 20); if (rc) return rc; }
-  h->internal_rescans = 0; h->range_splits = 0; h->dense_mode = false; h->piece_len = 0;
+  h->internal_rescans = 0; h->range_splits = 0; h->lookaheads = 0; h->dense_mode = false; h->piece_len = 0;
   h->inited = true;
   return pm_reset(h);
 }
@@ -2099,6 +2107,7 @@ extern "C" int pm_scan_candidates(pm_handle *h, int64_t begin, int64_t end, pm_h
 
 extern "C" int pm_candidates_device(pm_handle *h, void **d_records, size_t *n) {
   if (!h || !h->inited) return PM_E_INVALID;
+  drain_spec(h);                                                    // (after pm_scan: the buffer belongs to the next range's scan -- no records)
   if (d_records) *d_records = h->d_cands;
   if (n) *n = h->last_count;
   return PM_OK;
@@ -2107,6 +2116,8 @@ extern "C" int pm_candidates_device(pm_handle *h, void **d_records, size_t *n) {
 extern "C" int pm_scan_stats(pm_handle *h, uint64_t *out, int n) {
   if (!h || !h->inited || !out || n < 0) return PM_E_INVALID;
   uint64_t v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  // pm_scan's look-ahead scan copies its counters into h_seed_count when it ends: wait for it (it stays pm_scan's to collect)
+  if (h->spec && h->scan_pending) (void)hipStreamSynchronize(h->stream);
   v[0] = h->last_count;
   if (h->h_seed_count) {
     const size_t tiles = !h->pair.empty() ? h->pair.size() : 1 + h->sd_more.size();
@@ -2116,6 +2127,7 @@ extern "C" int pm_scan_stats(pm_handle *h, uint64_t *out, int n) {
   }
   v[2] = h->internal_rescans;
   v[6] = h->range_splits;
+  v[7] = h->lookaheads;
   for (int i = 0; i < n && i < 8; ++i) out[i] = v[i];
   return PM_OK;
 }
@@ -2665,6 +2677,16 @@ static int ensure_fpat(pm_handle *h) {
   return PM_OK;
 }
 
+// room for n records in d_fsorted, where pm_scan's final hits wait for their copy to the host
+static int ensure_fsorted(pm_handle *h, size_t n) {
+  if (h->fsorted_cap >= n) return PM_OK;
+  if (h->d_fsorted) (void)hipFree(h->d_fsorted);
+  h->d_fsorted = nullptr;
+  h->fsorted_cap = std::max<size_t>(n + n / 4, (size_t)1 << 16);
+  HIP_TRY(h, hipMalloc((void **)&h->d_fsorted, h->fsorted_cap * sizeof(pm_hit)));
+  return PM_OK;
+}
+
 // pm_scan's landing: n_upper bounds the number of final hits at d_hits (their count is d_count on the device when the
 // kernels in front produce it, else n_upper itself).  Enqueues the sort; *sorted tells whether the device could.
 static int land_enqueue_sort(pm_handle *h, const pm_hit *d_hits, const unsigned long long *d_count, size_t n_upper, bool *sorted) {
@@ -2673,12 +2695,7 @@ static int land_enqueue_sort(pm_handle *h, const pm_hit *d_hits, const unsigned 
   if (n_upper == 0 || n_upper > (size_t)INT_MAX / 2 || !h->sort_dev) return PM_OK;
   { int rcw = ensure_sort_workspace(h, n_upper, false); if (rcw) return rcw; }
   { int rcp = ensure_fpat(h); if (rcp) return rcp; }
-  if (h->fsorted_cap < n_upper) {
-    if (h->d_fsorted) (void)hipFree(h->d_fsorted);
-    h->d_fsorted = nullptr;
-    h->fsorted_cap = std::max<size_t>(n_upper + n_upper / 4, (size_t)1 << 16);
-    HIP_TRY(h, hipMalloc((void **)&h->d_fsorted, h->fsorted_cap * sizeof(pm_hit)));
-  }
+  { int rcf = ensure_fsorted(h, n_upper); if (rcf) return rcf; }
   HIP_TRY(h, sort_final_device(d_hits, d_count, n_upper, h->d_fpat_id, (uint32_t)h->pats.size(), h->sort_idxbits, h->sort_keybits,
                                h->d_keys, h->d_keys_alt, h->d_fsorted, h->d_ctemp, h->ctemp_bytes, h->stream));
   *sorted = true;
@@ -2690,7 +2707,7 @@ static int finalize_sync(pm_handle *h, const ScanNext *next) {
   if (!next) { HIP_TRY(h, stream_wait(h)); return PM_OK; }
   HIP_TRY(h, hipEventRecord(h->ev_fin, h->stream));
   if (next->on && !h->spec) {
-    if (pm_scan_candidates_async(h, next->b, next->e) == PM_OK) { h->spec = true; h->spec_b = next->b; h->spec_e = next->e; }
+    if (pm_scan_candidates_async(h, next->b, next->e) == PM_OK) { h->spec = true; h->spec_b = next->b; h->spec_e = next->e; ++h->lookaheads; }
   }
   HIP_TRY(h, hipEventSynchronize(h->ev_fin));
   return PM_OK;
@@ -2778,7 +2795,18 @@ static int finalize_device_impl(pm_handle *h, const void *d_cands, size_t n, int
   if (passthrough && land) {                                        // the records are the hits: sort, [next scan], copy
     bool sorted = false;
     { int rcs = land_enqueue_sort(h, src, nullptr, n, &sorted); if (rcs) return rcs; }
-    { int rcy = finalize_sync(h, next); if (rcy) return rcy; }
+    // Not sorted on the device (pattern ids in any order, 2^22 patterns, 2^30 hits): the copy to the host would read the
+    // record buffer itself, which the next range's scan refills from slot 0.  The records move to d_fsorted on the handle's
+    // stream, in front of that scan, and land from there; a list too long for that keeps the buffer: no scan behind it.
+    ScanNext after = *next;
+    if (!sorted && !h->counting && n) {
+      if (n <= (size_t)INT_MAX / 2) {
+        { int rcf = ensure_fsorted(h, n); if (rcf) return rcf; }
+        HIP_TRY(h, hipMemcpyAsync(h->d_fsorted, src, n * sizeof(pm_hit), hipMemcpyDeviceToDevice, h->stream));
+        src = h->d_fsorted;
+      } else after.on = false;
+    }
+    { int rcy = finalize_sync(h, &after); if (rcy) return rcy; }
     return land_collect(h, src, sorted, n, none, n_out);
   }
   if (passthrough && keep) {

@@ -522,10 +522,11 @@ class PatternMatch:
         return buf.value.decode()
 
     def scan_stats(self):
-        """pm_scan_stats: counters of the last scan (see include/pm_gpu.h)"""
+        """pm_scan_stats: counters of the last scan (see include/pm_gpu.h).  Waits for a look-ahead scan that scan() / scan_view()
+        left in flight: polled between ranges it takes away the overlap of that scan with the caller's work."""
         v = (C.c_uint64 * 8)()
         self._check(self._L.pm_scan_stats(self._h, v, 8))
-        names = ("candidates", "between_stages", "internal_rescans", "blocks", "rounds", "key_hits", "range_splits")
+        names = ("candidates", "between_stages", "internal_rescans", "blocks", "rounds", "key_hits", "range_splits", "lookahead")
         return {k: int(v[i]) for i, k in enumerate(names)}
 
     def residency(self):

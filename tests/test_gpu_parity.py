@@ -1182,7 +1182,8 @@ def test_pm_scan_order_with_pattern_ids_in_any_order(k, indels):
     """pm_scan hands its hits out in (end, pid, k) order.  With pattern ids that grow with the pattern index (what the reference's
     callers add, primer_match.cc:1105-1107) the order comes from one keys-only radix sort on the device (pm_cluster.hip
     sort_final_device: key = end | pattern index | k); with ids in any other order the host sorts.  Both must give the oracle's
-    hits in that order, whole and in small ranges."""
+    hits in that order, whole and in small ranges.  (A handful of hits per range here: whether the host-sorted landing gets out
+    of the way of the next range's look-ahead scan is decided by tests/test_gpu_scan_lookahead.py, on ranges of 2^21 hits.)"""
     rng = np.random.default_rng(77 + k)
     ents = synth.make_entries(rng, 3, 5000, n_runs=2, repeats=True)
     pats = synth.make_patterns(rng, ents, 200, length=22, planted=0.8, indel_frac=0.3 if indels else 0.0, extras=False)
