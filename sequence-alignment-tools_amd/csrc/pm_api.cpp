@@ -54,6 +54,21 @@ struct WinSlot {
   hipEvent_t used = nullptr;          // the last kernel that reads the slot (recorded on the handle's stream when it is unbound)
 };
 
+// The host-side rules that add a few records at the stream's edges, where the scan kernels have no whole window.  Each
+// rule's records depend on the stream and the patterns only: built once per init, handed to whatever range holds their end.
+enum EdgeRule {
+  EDGE_EDITS_START,                   // edits: candidates that end in the first Lw+2k+2 characters (edits_start_candidates)
+  EDGE_EDITS_END,                     // edits: candidates that end in the last four characters (edits_end_candidates)
+  EDGE_STREAM_START,                  // -K on the automaton's semantics: records of the stream start (stream_start_candidates)
+  EDGE_OVERHANG,                      // exact_halves / exact_bases -K: hits that hang over the end of the stream (stream_end_overhang_candidates)
+  EDGE_BLOCKS,                        // exact_bases -k: block occurrences in the first and last 56 characters (bases_edge_candidates)
+  EDGE_RULES
+};
+struct EdgeRecords {
+  std::vector<pm_hit> recs;
+  bool built = false;
+};
+
 struct pm_handle {
   pm_config cfg{};
   Knobs knobs;                        // the environment's test / measurement knobs as pm_create found them
@@ -101,16 +116,7 @@ struct pm_handle {
   void *d_susp = nullptr;                       // pair plan: 16-byte suspect records between its scan and verify kernels
   size_t susp_cap = 0;
   unsigned long long *h_seed_count = nullptr;   // pinned, 1 + 256 entries: a copy into pageable memory would make the "async" scan call wait for the kernels
-  std::vector<pm_hit> start_cache;    // edits: candidates that end in the first Lw+2k+2 characters (whole-prefix scans only)
-  bool start_cached = false;
-  std::vector<pm_hit> end_cache;      // edits: candidates that end in the last four characters (scans that reach the end of the stream)
-  bool end_cached = false;
-  std::vector<pm_hit> overhang_cache; // exact_halves / exact_bases -K: hits that hang over the end of the stream
-  bool overhang_cached = false;
-  std::vector<pm_hit> edge_cache;     // exact_bases -k: block occurrences in the first and last 56 characters
-  bool edge_cached = false;
-  std::vector<pm_hit> head_cache;     // -K on the automaton's semantics: records of the stream start (stream_start_candidates)
-  bool head_cached = false;
+  EdgeRecords edge[EDGE_RULES];       // the records the host adds at the stream's edges, per rule
   uint8_t *d_dp_codes = nullptr;      // device DP (pm_cluster_dp): 32 stream codes per pattern, exact zones
   int32_t *d_dp_esb = nullptr, *d_dp_eeb = nullptr;
   pm_hit *d_ext = nullptr;            // its output (swapped with d_cands after every scan)
@@ -124,7 +130,6 @@ struct pm_handle {
   unsigned long long *h_counter = nullptr;     // pinned
   size_t cap = 0;
   size_t last_count = 0;
-  size_t overflow_need = 0;           // record count a PM_E_OVERFLOW of the host-added records asks for
   int64_t scan_begin = 0;
   bool scan_pending = false;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -245,6 +250,25 @@ static int hipfail(pm_handle *h, hipError_t e, const char *what) {
   return fail(h, PM_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
 #define HIP_TRY(h, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return hipfail((h), e_, #expr); } while (0)
+#define PM_TRY(expr) do { const int rc_ = (expr); if (rc_) return rc_; } while (0)
+
+// A device buffer whose contents need not survive is too small: discard it and allocate `bytes` (the caller's size rule).
+// The old block goes first, so the peak of HBM in use does not rise.  `what` names the buffer in the error message.
+template <class T> static int dev_regrow(pm_handle *h, T **p, size_t bytes, const char *what) {
+  if (*p) { (void)hipFree(*p); *p = nullptr; }
+  const hipError_t e = hipMalloc((void **)p, bytes);
+  return e == hipSuccess ? PM_OK : hipfail(h, e, (std::string("hipMalloc of ") + what).c_str());
+}
+
+// A small host table into a fresh device allocation of at least `minimum` bytes (an empty table still has a pointer).
+static int dev_upload(pm_handle *h, void **dst, const void *src, size_t bytes, size_t minimum, const char *what) {
+  hipError_t e = hipMalloc(dst, std::max(bytes, minimum));
+  if (e == hipSuccess && bytes) e = hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
+  return e == hipSuccess ? PM_OK : hipfail(h, e, (std::string("upload of ") + what).c_str());
+}
+template <class D, class T> static int dev_upload(pm_handle *h, D **dst, const std::vector<T> &v, size_t minimum, const char *what) {
+  return dev_upload(h, (void **)dst, v.data(), v.size() * sizeof(T), minimum, what);
+}
 
 // ---- bit-packed codes on the host (<db>.sqz: char_io.t:18-214) ---------------------------------
 // Code c sits in bits [c*bits, (c+1)*bits) of the packed bytes, bit 0 being the MSB of byte 0.  Eight codes are exactly
@@ -473,9 +497,7 @@ static void free_device(pm_handle *h) {
 
 static int ensure_capacity(pm_handle *h, size_t cap, bool exact = false) {
   if (h->d_cands && (exact ? h->cap == cap : h->cap >= cap)) return PM_OK;
-  if (h->d_cands) (void)hipFree(h->d_cands);
-  h->d_cands = nullptr;
-  HIP_TRY(h, hipMalloc((void **)&h->d_cands, cap * sizeof(pm_hit)));
+  PM_TRY(dev_regrow(h, &h->d_cands, cap * sizeof(pm_hit), "d_cands"));
   if (h->d_ext) { (void)hipFree(h->d_ext); h->d_ext = nullptr; }
   h->cap = cap;
   return PM_OK;
@@ -686,7 +708,7 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
   for (const Pattern &p : h->pats) h->zoned = h->zoned || p.esb || p.eeb;
   h->nn_quirk = false;
   for (const Pattern &p : h->pats) h->nn_quirk = h->nn_quirk || pattern_n_quirk(h, p);
-  h->start_cached = false; h->start_cache.clear(); h->end_cached = false; h->end_cache.clear(); h->overhang_cached = false; h->overhang_cache.clear(); h->edge_cached = false; h->edge_cache.clear(); h->head_cached = false; h->head_cache.clear();
+  for (EdgeRecords &e : h->edge) e = EdgeRecords();
   std::string why;
   bool want_seed = h->kern == PM_KERNEL_SEED || h->kern == PM_KERNEL_AUTO;
   // A pattern set is rarely uniform: a few primers with an ambiguity letter, one that is too short
@@ -906,16 +928,10 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
         std::vector<int32_t> es(h->pats.size()), ee(h->pats.size());
         for (size_t i = 0; i < h->pats.size(); ++i) { es[i] = h->pats[i].esb; ee[i] = h->pats[i].eeb; }
         { void *hx[] = {h->d_half_codes, h->d_half_len, h->d_hesb, h->d_heeb}; for (void *q : hx) if (q) (void)hipFree(q); }
-        HIP_TRY(h, hipMalloc((void **)&h->d_half_codes, codes.size() ? codes.size() : 16));
-        HIP_TRY(h, hipMalloc((void **)&h->d_half_len, lens.size() ? lens.size() : 16));
-        HIP_TRY(h, hipMalloc((void **)&h->d_hesb, es.size() ? es.size() * 4 : 16));
-        HIP_TRY(h, hipMalloc((void **)&h->d_heeb, ee.size() ? ee.size() * 4 : 16));
-        if (nh) {
-          HIP_TRY(h, hipMemcpy(h->d_half_codes, codes.data(), codes.size(), hipMemcpyHostToDevice));
-          HIP_TRY(h, hipMemcpy(h->d_half_len, lens.data(), lens.size(), hipMemcpyHostToDevice));
-          HIP_TRY(h, hipMemcpy(h->d_hesb, es.data(), es.size() * 4, hipMemcpyHostToDevice));
-          HIP_TRY(h, hipMemcpy(h->d_heeb, ee.data(), ee.size() * 4, hipMemcpyHostToDevice));
-        }
+        PM_TRY(dev_upload(h, &h->d_half_codes, codes, 16, "d_half_codes"));
+        PM_TRY(dev_upload(h, &h->d_half_len, lens, 16, "d_half_len"));
+        PM_TRY(dev_upload(h, &h->d_hesb, es, 16, "d_hesb"));
+        PM_TRY(dev_upload(h, &h->d_heeb, ee, 16, "d_heeb"));
       }
       h->seed_k = sk;
     }
@@ -1048,10 +1064,24 @@ static void stream_halo(const pm_handle *h, int64_t *back, int64_t *fwd) {
   *fwd = *back;
 }
 
-// the records pm_scan carries into the next piece: the earliest text the device cluster DP will read for them
-static bool dp_on_device(const pm_handle *h) {
-  return h->sem == PM_SEM_FILTER_BITVEC && h->edits_dev && !h->cfg.wildcards && h->pats.size() < ((size_t)1 << 22);
+// Where the records of a scan become final hits: the handle's route through the finalize stage, decided by its option set.
+enum class Route {
+  Host,                               // pm_finalize: the order-dependent rules of the reference wrappers on the host
+  Passthrough,                        // the records are the hits
+  Cluster,                            // filter_bitvec -K: clusters and "smallest level, left-most end" on the device (pm_cluster.hip)
+  ClusterDp,                          // filter_bitvec -k on the seed family (A,C,G,T patterns of <= 32 characters): clusters and their DPs on the device
+  Halves                              // exact_halves on the seed family: its per-pattern sequential rule as a sort + one walk per pattern (pm_halves_rule)
+};
+static bool device_cluster_plain(const pm_handle *h);
+static Route finalize_route(const pm_handle *h) {
+  if (h->sem == PM_SEM_EXACT_HALVES && (h->seed_flags || h->halves_dev) && h->pats.size() < ((size_t)1 << 22) - 1) return Route::Halves;
+  if (h->sem == PM_SEM_KEYWORD_TREE || h->sem == PM_SEM_SHIFT_AND || h->sem == PM_SEM_SHIFT_AND_INEXACT || (h->sem == PM_SEM_EXACT_BASES && h->bases_flags))
+    return Route::Passthrough;
+  if (h->sem == PM_SEM_FILTER_BITVEC && h->edits_dev && !h->cfg.wildcards && h->pats.size() < ((size_t)1 << 22)) return Route::ClusterDp;
+  return device_cluster_plain(h) ? Route::Cluster : Route::Host;
 }
+
+// the records pm_scan carries into the next piece: the earliest text the device cluster DP will read for them
 static int64_t carry_reach(const pm_handle *h) {
   int64_t lo = INT64_MAX, L = 0;
   for (const pm_hit &c : h->carry) lo = std::min(lo, c.end);
@@ -1258,47 +1288,61 @@ static void win_prefetch(pm_handle *h, int64_t end, int64_t len) {
   (void)win_load(h, o, nlo, std::min(h->n, nlo + h->win));          // (a failure leaves the slot unloaded: the next range loads it itself)
 }
 
+// One stream per handle.  Drops the stream of an earlier init -- its window ring, an owned text: before the new one takes
+// memory -- and names the new one: n codes, on the host at `text` (NULL: none, or bit-packed: pm_init_packed sets those
+// fields itself), in HBM at d_text or, with `own`, in n + 16 bytes allocated here.  On the default stream, with a device stage.
+static int set_stream_source(pm_handle *h, int64_t n, const uint8_t *text, const void *d_text, bool own) {
+  win_release(h);
+  if (h->own_d_text && h->d_text) (void)hipFree((void *)h->d_text);
+  h->d_text = nullptr; h->own_d_text = false;
+  void *d = nullptr;
+  if (own) { HIP_TRY(h, hipMalloc(&d, (size_t)(n > 0 ? n : 1) + 16)); d_text = d; }
+  h->d_text = (const uint8_t *)d_text; h->own_d_text = own; h->h_text = text; h->n = n; h->stream = nullptr; h->host_only = false;
+  h->h_packed = nullptr; h->h_packed_bytes = 0; h->pk_bits = 0; h->pk_peak_extra = 0;
+  return PM_OK;
+}
+
+// `bytes` of the stream's host form go to d while init_common builds the pattern tables: with `overlap` on a second
+// thread -- the stream crosses PCIe (≈0.3 s for 3 GB of pageable memory) beside the table build --, else in one copy first.
+// An upload that failed is reported in `who`'s name after the table build; else the result is init_common's.  (pm_init
+// makes its one-copy upload itself and passes bytes = 0: it returns before the tables when that copy fails.)  ti0: when `who` began.
+static int upload_and_init(pm_handle *h, const char *who, void *d, const uint8_t *src, int64_t bytes, bool overlap,
+                           const uint8_t *table, int32_t table_len, double ti0) {
+  const double ti1 = now_ms();
+  hipError_t copy_err = hipSuccess;
+  std::thread copier;
+  if (bytes > 0 && overlap) {
+    const int dev = h->cfg.device;
+    copier = std::thread([=, &copy_err]() {
+      copy_err = hipSetDevice(dev);
+      if (copy_err == hipSuccess) copy_err = upload_stream(dev, d, src, (size_t)bytes);
+    });
+  } else if (bytes > 0) copy_err = hipMemcpy(d, src, (size_t)bytes, hipMemcpyHostToDevice);
+  const int rc = init_common(h, table, table_len);
+  const double ti2 = now_ms();
+  if (copier.joinable()) copier.join();
+  if (h->knobs.debug) fprintf(stderr, "[pm] %s: runtime + stream buffers %.0f ms, tables %.0f ms, then %.0f ms more for the upload of %lld bytes\n", who, ti1 - ti0, ti2 - ti1, now_ms() - ti2, (long long)bytes);
+  if (copy_err != hipSuccess) return fail(h, PM_E_HIP, std::string(who) + ": stream upload: " + hipGetErrorString(copy_err));
+  return rc;
+}
+
 extern "C" int pm_init(pm_handle *h, const uint8_t *text, int64_t n, const uint8_t *table, int32_t table_len) {
   if (!h || (!text && n > 0) || n < 0) return fail(h, PM_E_INVALID, "pm_init: bad arguments");
   const double ti0 = now_ms();
   HIP_TRY(h, hipSetDevice(h->cfg.device));
-  win_release(h);
-  if (h->own_d_text && h->d_text) { (void)hipFree((void *)h->d_text); h->d_text = nullptr; }
-  void *d = nullptr;
-  HIP_TRY(h, hipMalloc(&d, (size_t)(n > 0 ? n : 1) + 16));
-  const double ti1 = now_ms();
-  h->d_text = (const uint8_t *)d; h->own_d_text = true; h->h_text = text; h->n = n; h->stream = nullptr; h->host_only = false; h->h_packed = nullptr; h->h_packed_bytes = 0; h->pk_bits = 0; h->pk_peak_extra = 0;
-  // the stream crosses PCIe (≈0.3 s for 3 GB of pageable memory) while this thread builds the
-  // pattern tables; raw streams with wildcards look at the stream on the device first, so they wait
+  PM_TRY(set_stream_source(h, n, text, nullptr, true));
+  // raw streams with wildcards look at the stream on the device first, so they wait for it
   const bool overlap = n > ((int64_t)1 << 24) && !(!table && h->cfg.wildcards);
-  hipError_t copy_err = hipSuccess;
-  std::thread copier;
-  if (n > 0) {
-    if (overlap) {
-      const int dev = h->cfg.device;
-      copier = std::thread([=, &copy_err]() {
-        copy_err = hipSetDevice(dev);
-        if (copy_err == hipSuccess) copy_err = upload_stream(dev, d, text, (size_t)n);
-      });
-    } else {
-      HIP_TRY(h, hipMemcpy(d, text, (size_t)n, hipMemcpyHostToDevice));
-    }
-  }
-  const int rc = init_common(h, table, table_len);
-  const double ti2 = now_ms();
-  if (copier.joinable()) copier.join();
-  if (h->knobs.debug) fprintf(stderr, "[pm] init: runtime + stream buffer %.0f ms, tables %.0f ms, then %.0f ms more for the stream upload\n", ti1 - ti0, ti2 - ti1, now_ms() - ti2);
-  if (copy_err != hipSuccess) return fail(h, PM_E_HIP, std::string("pm_init: stream upload: ") + hipGetErrorString(copy_err));
-  if (rc) return rc;
+  void *d = (void *)h->d_text;
+  if (!overlap && n > 0) HIP_TRY(h, hipMemcpy(d, text, (size_t)n, hipMemcpyHostToDevice));   // (a failure returns before the tables are touched)
+  PM_TRY(upload_and_init(h, "pm_init", d, text, overlap ? n : 0, true, table, table_len, ti0));
   return ensure_packed(h);
 }
 
 extern "C" int pm_init_host(pm_handle *h, const uint8_t *text, int64_t n, const uint8_t *table, int32_t table_len) {
   if (!h || (!text && n > 0) || n < 0) return fail(h, PM_E_INVALID, "pm_init_host: bad arguments");
   HIP_TRY(h, hipSetDevice(h->cfg.device));
-  win_release(h);
-  if (h->own_d_text && h->d_text) (void)hipFree((void *)h->d_text);
-  h->d_text = nullptr; h->own_d_text = false; h->h_text = text; h->n = n; h->stream = nullptr; h->h_packed = nullptr; h->h_packed_bytes = 0; h->pk_bits = 0; h->pk_peak_extra = 0;
+  PM_TRY(set_stream_source(h, n, text, nullptr, false));
   h->host_only = true;
   return init_common(h, table, table_len);
 }
@@ -1308,32 +1352,26 @@ extern "C" int pm_init_device(pm_handle *h, const void *d_text, int64_t n, const
   if (!h || (!d_text && n > 0) || n < 0) return fail(h, PM_E_INVALID, "pm_init_device: bad arguments");
   if (((uintptr_t)d_text) & 3) return fail(h, PM_E_INVALID, "pm_init_device: stream must be 4-byte aligned");
   HIP_TRY(h, hipSetDevice(h->cfg.device));
-  win_release(h);
-  if (h->own_d_text && h->d_text) (void)hipFree((void *)h->d_text);
-  h->d_text = (const uint8_t *)d_text; h->own_d_text = false; h->h_text = nullptr; h->n = n; h->host_only = false; h->h_packed = nullptr; h->h_packed_bytes = 0; h->pk_bits = 0; h->pk_peak_extra = 0;
+  PM_TRY(set_stream_source(h, n, nullptr, d_text, false));
   h->stream = (hipStream_t)hip_stream;
-  const int rc = init_common(h, table, table_len);
-  if (rc) return rc;
+  PM_TRY(init_common(h, table, table_len));
   return ensure_packed(h);
 }
 
-// the part pm_init_windowed and the windowed form of pm_init_packed share: the host form is set by the caller
-static int init_window_ring(pm_handle *h, int64_t n, const uint8_t *table, int32_t table_len, int64_t window_bytes);
+// the part pm_init_windowed and the windowed form of pm_init_packed share: the stream's source is set by the caller
+static int init_window_ring(pm_handle *h, const uint8_t *table, int32_t table_len, int64_t window_bytes);
 
 extern "C" int pm_init_windowed(pm_handle *h, const uint8_t *text, int64_t n, const uint8_t *table, int32_t table_len,
                                 int64_t window_bytes) {
   if (!h || (!text && n > 0) || n < 0 || window_bytes <= 0) return fail(h, PM_E_INVALID, "pm_init_windowed: bad arguments");
   HIP_TRY(h, hipSetDevice(h->cfg.device));
-  h->h_text = text; h->h_packed = nullptr; h->h_packed_bytes = 0; h->pk_bits = 0; h->pk_peak_extra = 0;
-  return init_window_ring(h, n, table, table_len, window_bytes);
+  PM_TRY(set_stream_source(h, n, text, nullptr, false));
+  return init_window_ring(h, table, table_len, window_bytes);
 }
 
-static int init_window_ring(pm_handle *h, int64_t n, const uint8_t *table, int32_t table_len, int64_t window_bytes) {
-  win_release(h);
-  if (h->own_d_text && h->d_text) (void)hipFree((void *)h->d_text);
+static int init_window_ring(pm_handle *h, const uint8_t *table, int32_t table_len, int64_t window_bytes) {
   if (h->d_packed) (void)hipFree(h->d_packed);                      // (a resident init's 2-bit copy)
   h->d_packed = nullptr; h->packed_cap = 0;
-  h->d_text = nullptr; h->own_d_text = false; h->n = n; h->stream = nullptr; h->host_only = false;
   stream_halo(h, &h->win_back, &h->win_fwd);
   // guard: the halo plus the longest aligned run a kernel starts in front of `begin` (bit-parallel segment: 4 Mi positions,
   // seed / pair chunk: 2 Mi, or what the test knobs set) and the seed kernels' prefetch of four blocks of 1024 bases ahead
@@ -1356,38 +1394,15 @@ extern "C" int pm_init_packed(pm_handle *h, const uint8_t *packed, int64_t packe
   if (table_len > (1 << bits)) return fail(h, PM_E_INVALID, "pm_init_packed: the table has more symbols than codes of this width");
   const double ti0 = now_ms();
   HIP_TRY(h, hipSetDevice(h->cfg.device));
-  win_release(h);
-  if (window_bytes > 0) {
-    h->h_text = nullptr; h->h_packed = packed; h->h_packed_bytes = packed_bytes; h->pk_bits = bits; h->pk_peak_extra = 0;
-    return init_window_ring(h, n, table, table_len, window_bytes);
-  }
+  PM_TRY(set_stream_source(h, n, nullptr, nullptr, window_bytes == 0));
+  h->h_packed = packed; h->h_packed_bytes = packed_bytes; h->pk_bits = bits;
+  if (window_bytes > 0) return init_window_ring(h, table, table_len, window_bytes);
   // resident: the packed bytes cross PCIe as they are (upload_stream, beside the pattern-table build) into a staging buffer
   // in HBM; one kernel on the handle's stream unpacks them into the owned text and, for the seed family, its 2-bit words
-  if (h->own_d_text && h->d_text) { (void)hipFree((void *)h->d_text); h->d_text = nullptr; }
   const int64_t up = (n * bits + 7) / 8;
-  void *d = nullptr, *d_pk = nullptr;
-  HIP_TRY(h, hipMalloc(&d, (size_t)(n > 0 ? n : 1) + 16));
-  h->d_text = (const uint8_t *)d; h->own_d_text = true; h->h_text = nullptr; h->n = n; h->stream = nullptr; h->host_only = false;
-  h->h_packed = packed; h->h_packed_bytes = packed_bytes; h->pk_bits = bits; h->pk_peak_extra = 0;
+  void *d = (void *)h->d_text, *d_pk = nullptr;
   HIP_TRY(h, hipMalloc(&d_pk, (size_t)up + 8));
-  const double ti1 = now_ms();
-  const bool overlap = up > ((int64_t)1 << 24);
-  hipError_t copy_err = hipSuccess;
-  std::thread copier;
-  if (up > 0) {
-    if (overlap) {
-      const int dev = h->cfg.device;
-      copier = std::thread([=, &copy_err]() {
-        copy_err = hipSetDevice(dev);
-        if (copy_err == hipSuccess) copy_err = upload_stream(dev, d_pk, packed, (size_t)up);
-      });
-    } else copy_err = hipMemcpy(d_pk, packed, (size_t)up, hipMemcpyHostToDevice);
-  }
-  int rc = init_common(h, table, table_len);
-  const double ti2 = now_ms();
-  if (copier.joinable()) copier.join();
-  if (h->knobs.debug) fprintf(stderr, "[pm] init (packed, %d bits): runtime + stream buffers %.0f ms, tables %.0f ms, then %.0f ms more for the upload of %lld bytes\n", bits, ti1 - ti0, ti2 - ti1, now_ms() - ti2, (long long)up);
-  if (copy_err != hipSuccess) { (void)hipFree(d_pk); return fail(h, PM_E_HIP, std::string("pm_init_packed: stream upload: ") + hipGetErrorString(copy_err)); }
+  int rc = upload_and_init(h, "pm_init_packed", d_pk, packed, up, up > ((int64_t)1 << 24), table, table_len, ti0);
   const bool words = h->kern == PM_KERNEL_SEED;
   if (!rc && words) rc = ensure_words(h);
   if (rc) { (void)hipFree(d_pk); return rc; }
@@ -1515,6 +1530,7 @@ extern "C" int pm_describe(const pm_handle *h, char *buf, size_t buflen) {
 
 // ---- device stage ------------------------------------------------------------------------------
 static int ensure_dp_tables(pm_handle *h);
+static int ensure_fpat(pm_handle *h);
 
 extern "C" int pm_scan_candidates_async(pm_handle *h, int64_t begin, int64_t end) {
   if (!h || !h->inited) return fail(h, PM_E_INVALID, "pm_scan_candidates: handle not initialised");
@@ -1525,7 +1541,7 @@ extern "C" int pm_scan_candidates_async(pm_handle *h, int64_t begin, int64_t end
   drain_spec(h);
   if (h->win) {                                                     // windowed handle: the range's text, its halo and what carried clusters need
     int64_t lo = begin - h->win_back;
-    if (dp_on_device(h) && !h->carry.empty()) lo = std::min(lo, carry_reach(h));
+    if (finalize_route(h) == Route::ClusterDp && !h->carry.empty()) lo = std::min(lo, carry_reach(h));
     const int rcw = win_need(h, lo, end + h->win_fwd, h->bound_on, "pm_scan_candidates");
     if (rcw) return rcw;
   }
@@ -1545,9 +1561,8 @@ extern "C" int pm_scan_candidates_async(pm_handle *h, int64_t begin, int64_t end
     // (sized for the range being scanned; a denser stream overflows once and the buffer grows)
     const size_t want_seeds = (size_t)((end - begin) / 6) + ((size_t)1 << 20);
     if (!h->d_seeds || h->seed_cap < want_seeds) {
-      if (h->d_seeds) { (void)hipFree(h->d_seeds); h->d_seeds = nullptr; }
       h->seed_cap = std::max(h->seed_cap, want_seeds);
-      HIP_TRY(h, hipMalloc((void **)&h->d_seeds, h->seed_cap * sizeof(uint64_t)));
+      PM_TRY(dev_regrow(h, &h->d_seeds, h->seed_cap * sizeof(uint64_t), "d_seeds"));
     }
     if (!h->d_seed_count) HIP_TRY(h, hipMalloc((void **)&h->d_seed_count, SEEDCOUNT_WORDS * sizeof(unsigned long long)));
     const int ntiles = h->short_only ? 0 : 1 + (int)h->sd_more.size();
@@ -1564,9 +1579,8 @@ extern "C" int pm_scan_candidates_async(pm_handle *h, int64_t begin, int64_t end
         // first stage on the pair geometry: windows whose frame can hold an end in (begin, end] are the positions begin - 3 .. end + 1
         const size_t want_susp = (size_t)((end - begin) / 10) + ((size_t)1 << 20);
         if (!h->d_susp || h->susp_cap < want_susp) {
-          if (h->d_susp) { (void)hipFree(h->d_susp); h->d_susp = nullptr; }
           h->susp_cap = std::max(h->susp_cap, want_susp);
-          HIP_TRY(h, hipMalloc(&h->d_susp, h->susp_cap * PAIR_SUSPECT_BYTES));
+          PM_TRY(dev_regrow(h, &h->d_susp, h->susp_cap * PAIR_SUSPECT_BYTES, "d_susp"));
         }
         HIP_TRY(h, pair_launch(h->epair, h->d_text, h->d_packed, h->n, std::max<int64_t>(0, begin - 3), std::min<int64_t>(h->n, end + 2), h->d_cands, h->d_counter, h->cap,
                                h->d_susp, h->d_seed_count + 260, h->susp_cap, h->stream, &h->geo, nullptr, 3, h->d_seeds, h->d_seed_count + 1, h->seed_cap));
@@ -1592,9 +1606,8 @@ extern "C" int pm_scan_candidates_async(pm_handle *h, int64_t begin, int64_t end
     // (+ up to 15 unused slots per wave of the scan grid: slots are reserved 16 at a time)
     const size_t want = (size_t)((end - begin) / 128) + (size_t)((end - begin) / 8192) * h->pair[0].ncombos + ((size_t)1 << 20);
     if (!h->d_susp || h->susp_cap < want) {
-      if (h->d_susp) { (void)hipFree(h->d_susp); h->d_susp = nullptr; }
       h->susp_cap = std::max(h->susp_cap, want);
-      HIP_TRY(h, hipMalloc(&h->d_susp, h->susp_cap * PAIR_SUSPECT_BYTES));
+      PM_TRY(dev_regrow(h, &h->d_susp, h->susp_cap * PAIR_SUSPECT_BYTES, "d_susp"));
     }
     if (!h->d_seed_count) HIP_TRY(h, hipMalloc((void **)&h->d_seed_count, SEEDCOUNT_WORDS * sizeof(unsigned long long)));
     if (h->pair.size() > 256) return fail(h, PM_E_UNSUPPORTED, "too many pattern tiles");
@@ -1649,53 +1662,82 @@ static int ensure_sort_workspace(pm_handle *h, size_t n, bool with_out) {
   return PM_OK;
 }
 
-// Edit-distance seed plan: windows that do not fit in front of the stream start are not seeded, so
-// every candidate that ends in the first Lw+2k+2 characters is produced here by running the
-// automaton itself (shift_and_inexact.cc:249-352, rows start with l prefix bits :162-164) for each
-// pattern over those few characters; the kernel's records for the same ends are duplicates and
-// leave with the dedup.  Whatever range holds such an end gets them -- a caller's first range may be shorter than that
-// (found by scripts/fuzz_families.py --dense-bound, seed 605103, at the other end of the stream).
-static int edits_start_candidates(pm_handle *h, std::vector<pm_hit> *out) {
+// ---- records the host adds at the stream's edges (EdgeRule) --------------------------------------
+// Every rule below builds its records once per init and hands out the ones that end in the caller's range
+// (own_begin, own_end] -- whatever range holds the end gets the record: a first or last range may be shorter than a
+// pattern; scan_wait_once puts them behind the kernels' records (append_host_records).
+static void edge_owned(const pm_handle *h, const EdgeRecords &e, std::vector<pm_hit> *out) {
+  for (const pm_hit &x : e.recs) if (x.end > h->own_begin && x.end <= h->own_end) out->push_back(x);
+}
+
+// inner pattern j belongs to the seed family's main class, whose edge records the host makes
+static bool in_main_class(const pm_handle *h, size_t j) {
+  if (j < h->in_rest.size() && h->in_rest[j]) return false;         // the residue engine reports its own
+  if (j < h->in_short.size() && h->in_short[j]) return false;       // and so does pm_short_edit_scan
+  return true;
+}
+
+// `extra` behind the records of the scan in HBM.  A buffer too small for both: PM_E_OVERFLOW, and *n_out is the record
+// count it must hold.
+static int append_host_records(pm_handle *h, const std::vector<pm_hit> &extra, size_t *n_out) {
+  const size_t tot = h->last_count + extra.size();
+  if (n_out) *n_out = tot;
+  if (tot > h->cap) { h->last_count = 0; return fail(h, PM_E_OVERFLOW, "candidate buffer too small (pm_set_capacity)"); }
+  if (!extra.empty()) HIP_TRY(h, hipMemcpy(h->d_cands + h->last_count, extra.data(), extra.size() * sizeof(pm_hit), hipMemcpyHostToDevice));
+  h->last_count = tot;
+  return PM_OK;
+}
+
+// The k-error automaton itself (shift_and_inexact.cc:249-352) for inner pattern j over the stream characters
+// text[0, T), text[0] being stream position `base`: its ends beyond keep_after go to *out.  At the start of the stream the
+// rows start with l prefix bits (:162-164), elsewhere from the empty state.
+static void edit_automaton_ends(const pm_handle *h, size_t j, const uint8_t *text, int64_t T, int64_t base, int64_t keep_after, std::vector<pm_hit> *out) {
   const int k = h->cfg.k;
-  const int64_t Tfull = std::min<int64_t>(h->n, h->sd.Lw + 2 * k + 2);
-  const int64_t T = Tfull;
-  if (T <= 0 || h->scan_begin >= Tfull) return PM_OK;
-  if (h->start_cached) {                                            // same stream, same patterns: computed once
-    for (const pm_hit &x : h->start_cache) if (x.end > h->scan_begin && x.end <= h->scan_end) out->push_back(x);
-    return PM_OK;
-  }
-  std::vector<pm_hit> all, *extra = &all;
-  uint8_t head[64] = {0};
-  { const int rc = host_codes(h, 0, T, head); if (rc) return rc; }
-  for (size_t j = 0; j < h->inner.size(); ++j) {
-    if (j < h->in_rest.size() && h->in_rest[j]) continue;           // the residue engine reports its own
-    if (j < h->in_short.size() && h->in_short[j]) continue;         // and so does pm_short_edit_scan
-    const std::string &s = h->inner[j].s;
-    const int L = (int)s.size();
-    uint64_t R[3] = {0, 1, 3};
-    const uint64_t last = 1ull << (L - 1);
-    uint64_t M[4] = {0, 0, 0, 0};                       // positions of A, C, G, T (the only pattern characters of the seed family)
-    int code[4];
-    for (int q = 0; q < 4; ++q) code[q] = h->alpha.nch[(unsigned char)"ACGT"[q]];
-    for (int i = 0; i < L; ++i) for (int q = 0; q < 4; ++q)
-      if (h->wild_seed ? acgt_of((unsigned char)s[i]).find("ACGT"[q]) != std::string::npos : s[i] == "ACGT"[q]) M[q] |= 1ull << i;
-    for (int64_t t = 0; t < T; ++t) {
-      const int c = head[t];
-      if (c == h->eos_code) { R[0] = R[1] = R[2] = 0; continue; }
-      const uint64_t U = c == code[0] ? M[0] : c == code[1] ? M[1] : c == code[2] ? M[2] : c == code[3] ? M[3] : 0;
-      const uint64_t x0 = (R[0] << 1) | 1, m1 = x0 | R[0], n0 = x0 & U;
-      const uint64_t x1 = (R[1] << 1) | 1, n1 = (x1 & U) | m1 | (n0 << 1) | 1 | n0, m2 = x1 | R[1];
-      const uint64_t x2 = (R[2] << 1) | 1, n2 = (x2 & U) | m2 | (n1 << 1) | 1 | n1;
-      R[0] = n0; R[1] = n1; R[2] = n2;
-      const int lvl = (R[0] & last) ? 0 : (R[1] & last) ? 1 : (k >= 2 && (R[2] & last)) ? 2 : -1;
-      if (lvl >= 0) {
-        pm_hit x; x.end = t + 1; x.pid = h->inner_ids[j]; x.k = (uint8_t)lvl; x.aux[0] = x.aux[1] = x.aux[2] = 0;
-        extra->push_back(x);
-      }
+  const std::string &s = h->inner[j].s;
+  const int L = (int)s.size();
+  uint64_t R[3] = {0, 0, 0};
+  if (base == 0) { R[1] = 1; R[2] = 3; }
+  const uint64_t last = 1ull << (L - 1);
+  uint64_t M[4] = {0, 0, 0, 0};                       // positions of A, C, G, T (the only pattern characters of the seed family)
+  int code[4];
+  for (int q = 0; q < 4; ++q) code[q] = h->alpha.nch[(unsigned char)"ACGT"[q]];
+  for (int i = 0; i < L; ++i) for (int q = 0; q < 4; ++q)
+    if (h->wild_seed ? acgt_of((unsigned char)s[i]).find("ACGT"[q]) != std::string::npos : s[i] == "ACGT"[q]) M[q] |= 1ull << i;
+  for (int64_t t = 0; t < T; ++t) {
+    const int c = text[t];
+    if (c == h->eos_code) { R[0] = R[1] = R[2] = 0; continue; }
+    const uint64_t U = c == code[0] ? M[0] : c == code[1] ? M[1] : c == code[2] ? M[2] : c == code[3] ? M[3] : 0;
+    const uint64_t x0 = (R[0] << 1) | 1, m1 = x0 | R[0], n0 = x0 & U;
+    const uint64_t x1 = (R[1] << 1) | 1, n1 = (x1 & U) | m1 | (n0 << 1) | 1 | n0, m2 = x1 | R[1];
+    const uint64_t x2 = (R[2] << 1) | 1, n2 = (x2 & U) | m2 | (n1 << 1) | 1 | n1;
+    R[0] = n0; R[1] = n1; R[2] = n2;
+    const int lvl = (R[0] & last) ? 0 : (R[1] & last) ? 1 : (k >= 2 && (R[2] & last)) ? 2 : -1;
+    const int64_t end = base + t + 1;
+    if (lvl >= 0 && end > keep_after) {
+      pm_hit x; x.end = end; x.pid = h->inner_ids[j]; x.k = (uint8_t)lvl; x.aux[0] = x.aux[1] = x.aux[2] = 0;
+      out->push_back(x);
     }
   }
-  h->start_cache = all; h->start_cached = true;
-  for (const pm_hit &x : all) if (x.end > h->scan_begin && x.end <= h->scan_end) out->push_back(x);
+}
+
+// Edit-distance seed plan: windows that do not fit in front of the stream start are not seeded, so
+// every candidate that ends in the first Lw+2k+2 characters is produced here by running the
+// automaton itself (edit_automaton_ends) for each pattern over those few characters; the kernel's
+// records for the same ends are duplicates and leave with the dedup.  Whatever range holds such an
+// end gets them -- a caller's first range may be shorter than that
+// (found by scripts/fuzz_families.py --dense-bound, seed 605103, at the other end of the stream).
+static int edits_start_candidates(pm_handle *h, std::vector<pm_hit> *out) {
+  const int64_t T = std::min<int64_t>(h->n, h->sd.Lw + 2 * h->cfg.k + 2);
+  if (T <= 0 || h->own_begin >= T) return PM_OK;
+  EdgeRecords &e = h->edge[EDGE_EDITS_START];
+  if (!e.built) {                                                   // same stream, same patterns: computed once
+    uint8_t head[64] = {0};
+    { const int rc = host_codes(h, 0, T, head); if (rc) return rc; }
+    for (size_t j = 0; j < h->inner.size(); ++j)
+      if (in_main_class(h, j)) edit_automaton_ends(h, j, head, T, 0, 0, &e.recs);
+    e.built = true;
+  }
+  edge_owned(h, e, out);
   return PM_OK;
 }
 
@@ -1706,50 +1748,23 @@ static int edits_start_candidates(pm_handle *h, std::vector<pm_hit> *out) {
 // L + k + 8 characters -- its last bit depends on the last L + k only -- (from the stream-start state when that
 // is the whole stream); duplicates of the kernel's records leave with the dedup.  Computed once per stream.
 // Found by scripts/fuzz_families.py (seed 1308).
-static int edits_end_candidates(pm_handle *h, std::vector<pm_hit> *extra) {
+static int edits_end_candidates(pm_handle *h, std::vector<pm_hit> *out) {
   const int k = h->cfg.k;
   const int64_t n = h->n;
-  if (h->scan_end <= n - 4 || n <= 0) return PM_OK;                 // (the range that holds such an end gets it: the last range may be shorter than four positions)
-  if (h->end_cached) {
-    for (const pm_hit &x : h->end_cache) if (x.end > h->scan_begin && x.end <= h->scan_end) extra->push_back(x);
-    return PM_OK;
-  }
-  const int64_t T = std::min<int64_t>(n, 32 + k + 8);
-  uint8_t tail[64] = {0};
-  { const int rc = host_codes(h, n - T, T, tail); if (rc) return rc; }
-  std::vector<pm_hit> all;
-  for (size_t j = 0; j < h->inner.size(); ++j) {
-    if (j < h->in_rest.size() && h->in_rest[j]) continue;           // the residue engine reports its own
-    if (j < h->in_short.size() && h->in_short[j]) continue;         // and so does pm_short_edit_scan
-    const std::string &s = h->inner[j].s;
-    const int L = (int)s.size();
-    const int64_t Tj = std::min<int64_t>(T, L + k + 8);
-    uint64_t R[3] = {0, 0, 0};
-    if (Tj == n) { R[1] = 1; R[2] = 3; }                            // the whole stream: rows start with l prefix bits
-    const uint64_t last = 1ull << (L - 1);
-    uint64_t M[4] = {0, 0, 0, 0};
-    int code[4];
-    for (int q = 0; q < 4; ++q) code[q] = h->alpha.nch[(unsigned char)"ACGT"[q]];
-    for (int i = 0; i < L; ++i) for (int q = 0; q < 4; ++q)
-      if (h->wild_seed ? acgt_of((unsigned char)s[i]).find("ACGT"[q]) != std::string::npos : s[i] == "ACGT"[q]) M[q] |= 1ull << i;
-    for (int64_t t = T - Tj; t < T; ++t) {
-      const int c = tail[t];
-      if (c == h->eos_code) { R[0] = R[1] = R[2] = 0; continue; }
-      const uint64_t U = c == code[0] ? M[0] : c == code[1] ? M[1] : c == code[2] ? M[2] : c == code[3] ? M[3] : 0;
-      const uint64_t x0 = (R[0] << 1) | 1, m1 = x0 | R[0], n0 = x0 & U;
-      const uint64_t x1 = (R[1] << 1) | 1, n1 = (x1 & U) | m1 | (n0 << 1) | 1 | n0, m2 = x1 | R[1];
-      const uint64_t x2 = (R[2] << 1) | 1, n2 = (x2 & U) | m2 | (n1 << 1) | 1 | n1;
-      R[0] = n0; R[1] = n1; R[2] = n2;
-      const int lvl = (R[0] & last) ? 0 : (R[1] & last) ? 1 : (k >= 2 && (R[2] & last)) ? 2 : -1;
-      const int64_t end = n - T + t + 1;
-      if (lvl >= 0 && end > n - 4) {
-        pm_hit x; x.end = end; x.pid = h->inner_ids[j]; x.k = (uint8_t)lvl; x.aux[0] = x.aux[1] = x.aux[2] = 0;
-        all.push_back(x);
-      }
+  if (h->own_end <= n - 4 || n <= 0) return PM_OK;                  // (the range that holds such an end gets it: the last range may be shorter than four positions)
+  EdgeRecords &e = h->edge[EDGE_EDITS_END];
+  if (!e.built) {
+    const int64_t T = std::min<int64_t>(n, 32 + k + 8);
+    uint8_t tail[64] = {0};
+    { const int rc = host_codes(h, n - T, T, tail); if (rc) return rc; }
+    for (size_t j = 0; j < h->inner.size(); ++j) {
+      if (!in_main_class(h, j)) continue;
+      const int64_t Tj = std::min<int64_t>(T, (int64_t)h->inner[j].s.size() + k + 8);
+      edit_automaton_ends(h, j, tail + (T - Tj), Tj, n - Tj, n - 4, &e.recs);
     }
+    e.built = true;
   }
-  h->end_cache = all; h->end_cached = true;
-  for (const pm_hit &x : all) if (x.end > h->scan_begin && x.end <= h->scan_end) extra->push_back(x);
+  edge_owned(h, e, out);
   return PM_OK;
 }
 
@@ -1757,47 +1772,36 @@ static int edits_end_candidates(pm_handle *h, std::vector<pm_hit> *extra) {
 // (shift_and_inexact.cc:162-164), so at the very start of the stream a pattern whose first
 // d <= k characters are "missing" is reported at end = L-d with level d + mismatches.  The seed
 // kernel only sees whole windows; these few records are produced here and appended in HBM.
-static int stream_start_candidates(pm_handle *h) {
+static int stream_start_candidates(pm_handle *h, std::vector<pm_hit> *out) {
   const int k = h->seed_k;
-  if (!h->head_cached) {                                            // same stream, same patterns: computed once (0.3 ms per scan at 200k patterns)
-  const int64_t need = std::min<int64_t>(h->n, 32);
-  uint8_t head[32] = {0};
-  { const int rc = host_codes(h, 0, need, head); if (rc) return rc; }
-  std::vector<pm_hit> &extra = h->head_cache;
-  extra.clear();
-  for (size_t j = 0; j < h->inner.size(); ++j) {
-    if (j < h->in_rest.size() && h->in_rest[j]) continue;           // the residue engine reports its own
-    if (j < h->in_short.size() && h->in_short[j]) continue;         // and so does pm_short_edit_scan
-    const std::string &s = h->inner[j].s;
-    const int L = (int)s.size();
-    for (int d = 1; d <= k && d < L; ++d) {
-      const int e = L - d;
-      if (e > h->n) continue;
-      int lvl = d;
-      bool dead = false;
-      for (int i = 0; i < e && !dead; ++i) {
-        if ((int)head[i] == h->eos_code) dead = true;                // EOS clears every row
-        else if (h->wild_seed) { if (acgt_of((unsigned char)s[d + i]).find((char)h->alpha.ch[head[i]]) == std::string::npos) ++lvl; }
-        else if ((int)head[i] != h->alpha.nch[(unsigned char)s[d + i]]) ++lvl;
-      }
-      if (!dead && lvl <= k) {
-        pm_hit x; x.end = e; x.pid = h->inner_ids[j]; x.k = (uint8_t)lvl; x.aux[0] = x.aux[1] = x.aux[2] = 0;
-        extra.push_back(x);
+  EdgeRecords &e = h->edge[EDGE_STREAM_START];
+  if (!e.built) {                                                   // same stream, same patterns: computed once (0.3 ms per scan at 200k patterns)
+    const int64_t need = std::min<int64_t>(h->n, 32);
+    uint8_t head[32] = {0};
+    { const int rc = host_codes(h, 0, need, head); if (rc) return rc; }
+    for (size_t j = 0; j < h->inner.size(); ++j) {
+      if (!in_main_class(h, j)) continue;
+      const std::string &s = h->inner[j].s;
+      const int L = (int)s.size();
+      for (int d = 1; d <= k && d < L; ++d) {
+        const int end = L - d;
+        if (end > h->n) continue;
+        int lvl = d;
+        bool dead = false;
+        for (int i = 0; i < end && !dead; ++i) {
+          if ((int)head[i] == h->eos_code) dead = true;              // EOS clears every row
+          else if (h->wild_seed) { if (acgt_of((unsigned char)s[d + i]).find((char)h->alpha.ch[head[i]]) == std::string::npos) ++lvl; }
+          else if ((int)head[i] != h->alpha.nch[(unsigned char)s[d + i]]) ++lvl;
+        }
+        if (!dead && lvl <= k) {
+          pm_hit x; x.end = end; x.pid = h->inner_ids[j]; x.k = (uint8_t)lvl; x.aux[0] = x.aux[1] = x.aux[2] = 0;
+          e.recs.push_back(x);
+        }
       }
     }
+    e.built = true;
   }
-  h->head_cached = true;
-  }
-  std::vector<pm_hit> extra;                                        // (the range that holds the end gets the record: a first range may be shorter than a pattern)
-  for (const pm_hit &x : h->head_cache) if (x.end > h->own_begin && x.end <= h->own_end) extra.push_back(x);
-  if (extra.empty()) return PM_OK;
-  if (h->last_count + extra.size() > h->cap) {
-    h->overflow_need = h->last_count + extra.size();
-    h->last_count = 0;
-    return fail(h, PM_E_OVERFLOW, "candidate buffer too small (pm_set_capacity)");
-  }
-  HIP_TRY(h, hipMemcpy(h->d_cands + h->last_count, extra.data(), extra.size() * sizeof(pm_hit), hipMemcpyHostToDevice));
-  h->last_count += extra.size();
+  edge_owned(h, e, out);
   return PM_OK;
 }
 
@@ -1812,12 +1816,12 @@ static int stream_start_candidates(pm_handle *h) {
 // and appended in HBM, like the records of the stream start.  With indels the half seeds are extended by
 // pm_seed_extend, which reads code 0 past the end itself.  exact_bases -K is the same with the mandated first
 // block in the left half's place (its records are final: the primer's id, no flag).
-static int stream_end_overhang_candidates(pm_handle *h, bool bases) {
+// (All of them end beyond the stream: they go to the range that reaches its end, own_end >= n.)
+static int stream_end_overhang_candidates(pm_handle *h, bool bases, std::vector<pm_hit> *out) {
   const int k = h->cfg.k;
   const int64_t n = h->n;
-  if (!h->overhang_cached) {                                        // same stream, same patterns: computed once
-    std::vector<pm_hit> &all = h->overhang_cache;
-    all.clear();
+  EdgeRecords &e = h->edge[EDGE_OVERHANG];
+  if (!e.built) {                                                   // same stream, same patterns: computed once
     const int64_t need = std::min<int64_t>(n, 32);
     uint8_t tail[32] = {0};                                         // tail[32 - need .. 32) = the last `need` characters
     { const int rc = host_codes(h, n - need, need, tail + 32 - need); if (rc) return rc; }
@@ -1849,22 +1853,51 @@ static int stream_end_overhang_candidates(pm_handle *h, bool bases) {
           }
           if (!dead && lvl <= k) {
             pm_hit x; x.end = n + t; x.pid = bases ? (uint32_t)p.id : (uint32_t)(j + 1); x.k = (uint8_t)lvl; x.aux[0] = bases ? 0 : 1; x.aux[1] = x.aux[2] = 0;
-            all.push_back(x);
+            e.recs.push_back(x);
           }
         }
       }
     }
-    h->overhang_cached = true;
+    e.built = true;
   }
-  const std::vector<pm_hit> &extra = h->overhang_cache;
-  if (extra.empty()) return PM_OK;
-  if (h->last_count + extra.size() > h->cap) {
-    h->overflow_need = h->last_count + extra.size();
-    h->last_count = 0;
-    return fail(h, PM_E_OVERFLOW, "candidate buffer too small (pm_set_capacity)");
+  out->insert(out->end(), e.recs.begin(), e.recs.end());
+  return PM_OK;
+}
+
+// exact_bases -k: the records are occurrences of the mandated block, found through windows within k edits of
+// the whole pattern.  A pattern that hangs over the end of the stream has no such window (the extension DP reads
+// code 0 there, see stream_end_overhang_candidates), and at the start of the stream the windows that do not
+// fit are not seeded (a pattern whose first characters are deleted there ends in them).  Every block occurrence
+// in the first and last 56 characters therefore comes from the host as well -- more than needed: the
+// reference extends EVERY occurrence, the records are verified by the same DP, duplicates leave with the dedup.
+static int bases_edge_candidates(pm_handle *h, std::vector<pm_hit> *out) {
+  const int64_t n = h->n, E = std::min<int64_t>(n, 56);
+  if (h->own_begin >= 56 && h->own_end <= n - 56) return PM_OK;
+  EdgeRecords &e = h->edge[EDGE_BLOCKS];
+  if (!e.built) {                                                   // same stream, same patterns: computed once
+    uint8_t edge[2][64] = {{0}, {0}};
+    { int rc = host_codes(h, 0, E, edge[0]); if (!rc) rc = host_codes(h, n - E, E, edge[1]); if (rc) return rc; }
+    for (size_t j = 0; j < h->pats.size(); ++j) {
+      const Pattern &p = h->pats[j];
+      const int L = (int)p.s.size();
+      const int es = std::max(0, std::min(L, p.esb)), ee = std::max(0, std::min(L, p.eeb));
+      const bool prefix = es >= ee;                                 // exact_bases.cc:139-150: the larger block decides
+      const int blk = prefix ? es : ee;
+      if (blk <= 0) continue;
+      const char *bs = p.s.data() + (prefix ? 0 : L - blk);
+      for (int side = 0; side < 2; ++side) {
+        const int64_t base = side == 0 ? 0 : n - E;                 // stream index of edge[side][0]
+        for (int64_t o = 0; o + blk <= E; ++o) {
+          if (side == 1 && base + o + blk <= E) continue;           // (a short stream: already taken from its start)
+          bool ok = true;
+          for (int q = 0; q < blk && ok; ++q) ok = (int)edge[side][o + q] == h->alpha.nch[(unsigned char)bs[q]];
+          if (ok) { pm_hit x; x.end = base + o + blk; x.pid = (uint32_t)(j + 1); x.k = 0; x.aux[0] = x.aux[1] = x.aux[2] = 0; e.recs.push_back(x); }
+        }
+      }
+    }
+    e.built = true;
   }
-  HIP_TRY(h, hipMemcpy(h->d_cands + h->last_count, extra.data(), extra.size() * sizeof(pm_hit), hipMemcpyHostToDevice));
-  h->last_count += extra.size();
+  edge_owned(h, e, out);
   return PM_OK;
 }
 
@@ -1879,26 +1912,11 @@ static int ensure_dp_tables(pm_handle *h) {
       for (size_t q = 0; q < h->pats[i].s.size() && q < 32; ++q) codes[i * 32 + q] = (uint8_t)h->alpha.nch[(unsigned char)h->pats[i].s[q]];
       es[i] = h->pats[i].esb; ee[i] = h->pats[i].eeb;
     }
-    HIP_TRY(h, hipMalloc((void **)&h->d_dp_codes, codes.size() ? codes.size() : 32));
-    HIP_TRY(h, hipMalloc((void **)&h->d_dp_esb, np ? np * 4 : 4));
-    HIP_TRY(h, hipMalloc((void **)&h->d_dp_eeb, np ? np * 4 : 4));
-    if (np) {
-      HIP_TRY(h, hipMemcpy(h->d_dp_codes, codes.data(), codes.size(), hipMemcpyHostToDevice));
-      HIP_TRY(h, hipMemcpy(h->d_dp_esb, es.data(), np * 4, hipMemcpyHostToDevice));
-      HIP_TRY(h, hipMemcpy(h->d_dp_eeb, ee.data(), np * 4, hipMemcpyHostToDevice));
-    }
+    PM_TRY(dev_upload(h, &h->d_dp_codes, codes, 32, "d_dp_codes"));
+    PM_TRY(dev_upload(h, &h->d_dp_esb, es, 4, "d_dp_esb"));
+    PM_TRY(dev_upload(h, &h->d_dp_eeb, ee, 4, "d_dp_eeb"));
   }
-  if (!h->d_fpat_len) {
-    std::vector<uint8_t> pl(np); std::vector<uint32_t> pi(np);
-    for (size_t i = 0; i < np; ++i) { pl[i] = (uint8_t)std::min<size_t>(h->pats[i].s.size(), 255); pi[i] = (uint32_t)h->pats[i].id; }
-    HIP_TRY(h, hipMalloc((void **)&h->d_fpat_len, pl.size() ? pl.size() : 1));
-    HIP_TRY(h, hipMalloc((void **)&h->d_fpat_id, pi.size() ? pi.size() * 4 : 4));
-    if (!pl.empty()) {
-      HIP_TRY(h, hipMemcpy(h->d_fpat_len, pl.data(), pl.size(), hipMemcpyHostToDevice));
-      HIP_TRY(h, hipMemcpy(h->d_fpat_id, pi.data(), pi.size() * 4, hipMemcpyHostToDevice));
-    }
-  }
-  return PM_OK;
+  return ensure_fpat(h);
 }
 
 // An internal buffer between two kernels of one scan (seed records, suspects) was too small: it has
@@ -1948,17 +1966,17 @@ static int scan_wait_once(pm_handle *h, size_t *n_out) {
     if (h->knobs.debug) fprintf(stderr, "[pm] %s: %llu seed records (tile with most), seed cap %zu, candidates %zu\n", h->edits_dev ? "edits" : "halves", worst, h->seed_cap, cnt);
     if (h->bound_on && worst > dense_bound(h)) return dense_fail(h, "seed records of the edit-distance plan", worst);
     if (worst > h->seed_cap) {                                     // grow the seed buffer and tell the caller to scan again
-      (void)hipFree(h->d_seeds); h->d_seeds = nullptr;
       h->seed_cap = (size_t)worst + (size_t)worst / 8 + 1024;
       h->last_count = 0;
+      PM_TRY(dev_regrow(h, &h->d_seeds, h->seed_cap * sizeof(uint64_t), "d_seeds"));
       return SCAN_AGAIN;
     }
     if (h->bound_on && h->epair_on && h->edits_dev && h->h_seed_count[260] > dense_bound(h))
       return dense_fail(h, "suspects of the edit-distance plan", h->h_seed_count[260]);
     if (h->epair_on && h->edits_dev && h->h_seed_count[260] > h->susp_cap) {   // the pair geometry's suspect list between its two kernels
-      (void)hipFree(h->d_susp); h->d_susp = nullptr;
       h->susp_cap = (size_t)h->h_seed_count[260] + (size_t)h->h_seed_count[260] / 8 + 1024;
       h->last_count = 0;
+      PM_TRY(dev_regrow(h, &h->d_susp, h->susp_cap * PAIR_SUSPECT_BYTES, "d_susp"));
       return SCAN_AGAIN;
     }
   }
@@ -1982,67 +2000,26 @@ static int scan_wait_once(pm_handle *h, size_t *n_out) {
     if (h->knobs.debug) fprintf(stderr, "[pm] pair plan: %llu suspects (tile with most), capacity %zu, candidates %zu\n", worst, h->susp_cap, cnt);
     if (h->bound_on && worst > dense_bound(h)) return dense_fail(h, "suspects of the pair plan", worst);
     if (worst > h->susp_cap) {                                     // grow it and tell the caller to scan again
-      (void)hipFree(h->d_susp); h->d_susp = nullptr;
       h->susp_cap = (size_t)worst + (size_t)worst / 8 + 1024;
       h->last_count = 0;
+      PM_TRY(dev_regrow(h, &h->d_susp, h->susp_cap * PAIR_SUSPECT_BYTES, "d_susp"));
       return SCAN_AGAIN;
     }
   }
   if (h->edits_dev) {
-    // records of the stream start (host), then sort + unique on the device: several seeds report each candidate
-    size_t tot = cnt;
-    if (h->bases_edits && (h->own_begin < 56 || h->own_end > h->n - 56)) {
-      // exact_bases -k: the records are occurrences of the mandated block, found through windows within k edits of
-      // the whole pattern.  A pattern that hangs over the end of the stream has no such window (the extension DP reads
-      // code 0 there, see stream_end_overhang_candidates), and at the start of the stream the windows that do not
-      // fit are not seeded (a pattern whose first characters are deleted there ends in them).  Every block occurrence
-      // in the first and last 56 characters therefore comes from the host as well -- more than needed: the
-      // reference extends EVERY occurrence, the records are verified by the same DP, duplicates leave with the dedup.
-      const int64_t n = h->n, E = std::min<int64_t>(n, 56);
-      if (!h->edge_cached) {                                        // same stream, same patterns: computed once
-        uint8_t edge[2][64] = {{0}, {0}};
-        { int rc = host_codes(h, 0, E, edge[0]); if (!rc) rc = host_codes(h, n - E, E, edge[1]); if (rc) return rc; }
-        h->edge_cache.clear();
-        for (size_t j = 0; j < h->pats.size(); ++j) {
-          const Pattern &p = h->pats[j];
-          const int L = (int)p.s.size();
-          const int es = std::max(0, std::min(L, p.esb)), ee = std::max(0, std::min(L, p.eeb));
-          const bool prefix = es >= ee;                              // exact_bases.cc:139-150: the larger block decides
-          const int blk = prefix ? es : ee;
-          if (blk <= 0) continue;
-          const char *bs = p.s.data() + (prefix ? 0 : L - blk);
-          for (int side = 0; side < 2; ++side) {
-            const int64_t base = side == 0 ? 0 : n - E;               // stream index of edge[side][0]
-            for (int64_t o = 0; o + blk <= E; ++o) {
-              if (side == 1 && base + o + blk <= E) continue;         // (a short stream: already taken from its start)
-              bool ok = true;
-              for (int q = 0; q < blk && ok; ++q) ok = (int)edge[side][o + q] == h->alpha.nch[(unsigned char)bs[q]];
-              if (ok) { pm_hit x; x.end = base + o + blk; x.pid = (uint32_t)(j + 1); x.k = 0; x.aux[0] = x.aux[1] = x.aux[2] = 0; h->edge_cache.push_back(x); }
-            }
-          }
-        }
-        h->edge_cached = true;
-      }
-      std::vector<pm_hit> extra;
-      for (const pm_hit &x : h->edge_cache) {
-        if (x.end > h->own_begin && x.end <= h->own_end) extra.push_back(x);     // (whatever range holds the end)
-      }
-      if (tot + extra.size() > h->cap) { h->last_count = 0; if (n_out) *n_out = tot + extra.size(); return fail(h, PM_E_OVERFLOW, "candidate buffer too small (pm_set_capacity)"); }
-      if (!extra.empty()) HIP_TRY(h, hipMemcpy(h->d_cands + tot, extra.data(), extra.size() * sizeof(pm_hit), hipMemcpyHostToDevice));
-      tot += extra.size();
+    // records of the stream's edges (host), then sort + unique on the device: several seeds report each candidate
+    std::vector<pm_hit> extra;
+    int rc;
+    if (h->bases_edits) rc = bases_edge_candidates(h, &extra);      // (exact_bases: the records are block seeds, not automaton ends)
+    else {
+      rc = edits_start_candidates(h, &extra);
+      if (!rc) rc = edits_end_candidates(h, &extra);
     }
-    if (!h->bases_edits) {                                          // (exact_bases: the records are block seeds, not automaton ends)
-      std::vector<pm_hit> extra;
-      int rc = edits_start_candidates(h, &extra);
-      if (rc) return rc;
-      rc = edits_end_candidates(h, &extra);
-      if (rc) return rc;
-      if (tot + extra.size() > h->cap) { h->last_count = 0; if (n_out) *n_out = tot + extra.size(); return fail(h, PM_E_OVERFLOW, "candidate buffer too small (pm_set_capacity)"); }
-      if (!extra.empty()) HIP_TRY(h, hipMemcpy(h->d_cands + tot, extra.data(), extra.size() * sizeof(pm_hit), hipMemcpyHostToDevice));
-      tot += extra.size();
-    }
+    if (!rc) rc = append_host_records(h, extra, n_out);
+    if (rc) return rc;
+    const size_t tot = h->last_count;
     if (tot >= ((size_t)1 << 31)) return dense_fail(h, "edit-distance plan, 2^31 or more candidate", tot);
-    int rc = ensure_sort_workspace(h, tot, false);
+    rc = ensure_sort_workspace(h, tot, false);
     if (rc) return rc;
     const double td0 = now_ms();
     HIP_TRY(h, dedup_device(h->d_cands, tot, h->d_keys, h->d_keys_alt, h->d_ctemp, h->ctemp_bytes, h->d_cands, h->d_fcounts, h->stream));
@@ -2054,18 +2031,17 @@ static int scan_wait_once(pm_handle *h, size_t *n_out) {
     h->last_launches += 3;
     return PM_OK;
   }
+  std::vector<pm_hit> extra;
   if (h->kern == PM_KERNEL_SEED && h->own_begin < 32 && h->seed_k > 0 &&
       (h->sem == PM_SEM_FILTER_BITVEC || h->sem == PM_SEM_SHIFT_AND_INEXACT)) {
-    int rc = stream_start_candidates(h);
-    if (rc) { if (rc == PM_E_OVERFLOW && n_out) *n_out = h->overflow_need; return rc; }
-    if (n_out) *n_out = h->last_count;
+    const int rc = stream_start_candidates(h, &extra);
+    if (rc) return rc;
   }
   if (h->kern == PM_KERNEL_SEED && (h->seed_flags || h->bases_flags) && h->own_end >= h->n) {
-    int rc = stream_end_overhang_candidates(h, h->bases_flags);
-    if (rc) { if (rc == PM_E_OVERFLOW && n_out) *n_out = h->overflow_need; return rc; }
-    if (n_out) *n_out = h->last_count;
+    const int rc = stream_end_overhang_candidates(h, h->bases_flags, &extra);
+    if (rc) return rc;
   }
-  return PM_OK;
+  return extra.empty() ? PM_OK : append_host_records(h, extra, n_out);
 }
 
 extern "C" int pm_scan_wait(pm_handle *h, size_t *n_out) {
@@ -2668,23 +2644,15 @@ static int ensure_fpat(pm_handle *h) {
   if (h->d_fpat_len) return PM_OK;
   std::vector<uint8_t> pl(h->pats.size()); std::vector<uint32_t> pi(h->pats.size());
   for (size_t i = 0; i < h->pats.size(); ++i) { pl[i] = (uint8_t)std::min<size_t>(h->pats[i].s.size(), 255); pi[i] = (uint32_t)h->pats[i].id; }
-  HIP_TRY(h, hipMalloc((void **)&h->d_fpat_len, pl.size() ? pl.size() : 1));
-  HIP_TRY(h, hipMalloc((void **)&h->d_fpat_id, pi.size() ? pi.size() * 4 : 4));
-  if (!pl.empty()) {
-    HIP_TRY(h, hipMemcpy(h->d_fpat_len, pl.data(), pl.size(), hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemcpy(h->d_fpat_id, pi.data(), pi.size() * 4, hipMemcpyHostToDevice));
-  }
-  return PM_OK;
+  PM_TRY(dev_upload(h, &h->d_fpat_len, pl, 1, "d_fpat_len"));
+  return dev_upload(h, &h->d_fpat_id, pi, 4, "d_fpat_id");
 }
 
 // room for n records in d_fsorted, where pm_scan's final hits wait for their copy to the host
 static int ensure_fsorted(pm_handle *h, size_t n) {
   if (h->fsorted_cap >= n) return PM_OK;
-  if (h->d_fsorted) (void)hipFree(h->d_fsorted);
-  h->d_fsorted = nullptr;
   h->fsorted_cap = std::max<size_t>(n + n / 4, (size_t)1 << 16);
-  HIP_TRY(h, hipMalloc((void **)&h->d_fsorted, h->fsorted_cap * sizeof(pm_hit)));
-  return PM_OK;
+  return dev_regrow(h, &h->d_fsorted, h->fsorted_cap * sizeof(pm_hit), "d_fsorted");
 }
 
 // pm_scan's landing: n_upper bounds the number of final hits at d_hits (their count is d_count on the device when the
@@ -2737,6 +2705,25 @@ static int land_collect(pm_handle *h, const pm_hit *d_hits, bool sorted, size_t 
   return PM_OK;
 }
 
+// The end of a device finalize: nfin final hits at d_fout and the host-decided `extra` go to pm_scan's landing (land), stay
+// in HBM (out == NULL: pm_final_hits_device), or are copied to the caller's buffer.
+static int deliver_finals(pm_handle *h, bool land, bool sorted, size_t nfin, std::vector<pm_hit> &extra, int flags, pm_hit *out, size_t cap, size_t *n_out) {
+  if (land) return land_collect(h, h->d_fout, sorted, nfin, extra, n_out);
+  const size_t tot = nfin + extra.size();
+  if (!out) {                                                       // the few host-decided hits join the device's in HBM
+    if (tot > h->ckeys_cap) return fail(h, PM_E_OVERFLOW, "pm_finalize_device: device output buffer too small");
+    if (!extra.empty()) HIP_TRY(h, hipMemcpy(h->d_fout + nfin, extra.data(), extra.size() * sizeof(pm_hit), hipMemcpyHostToDevice));
+    h->d_final = h->d_fout; h->n_final = tot;
+  } else {
+    if (tot > cap) return fail(h, PM_E_OVERFLOW, "pm_finalize_device: out buffer too small");
+    if (nfin) HIP_TRY(h, hipMemcpy(out, h->d_fout, nfin * sizeof(pm_hit), hipMemcpyDeviceToHost));
+    if (!extra.empty()) memcpy(out + nfin, extra.data(), extra.size() * sizeof(pm_hit));
+    if (flags & PM_FINALIZE_SORTED) sort_hits(out, tot);
+  }
+  if (n_out) *n_out = tot;
+  return PM_OK;
+}
+
 static int finalize_device_impl(pm_handle *h, const void *d_cands, size_t n, int64_t scanned_to, int flags,
                                 const OwnedRange &own, pm_hit *out, size_t cap, size_t *n_out, const ScanNext *next) {
   if (!h || !h->inited) return fail(h, PM_E_INVALID, "pm_finalize_device: handle not initialised");
@@ -2751,22 +2738,16 @@ static int finalize_device_impl(pm_handle *h, const void *d_cands, size_t n, int
   const bool keep = out == nullptr && !land;
   h->d_final = nullptr; h->n_final = 0;
   if (keep && (flags & PM_FINALIZE_SORTED)) return fail(h, PM_E_INVALID, "pm_finalize_device: PM_FINALIZE_SORTED needs a host buffer");
-  const bool passthrough = h->sem == PM_SEM_KEYWORD_TREE || h->sem == PM_SEM_SHIFT_AND || h->sem == PM_SEM_SHIFT_AND_INEXACT ||
-                           (h->sem == PM_SEM_EXACT_BASES && h->bases_flags);
-  // edits on the seed family (A,C,G,T patterns of <= 32 characters): clusters and their DPs on the device
-  const bool cluster_dp = h->sem == PM_SEM_FILTER_BITVEC && h->edits_dev && !h->cfg.wildcards && h->pats.size() < ((size_t)1 << 22);
-  const bool cluster = cluster_dp || device_cluster_plain(h);
-  // exact_halves on the seed family: its per-pattern sequential rule as a sort + one walk per pattern
-  // (pm_halves_rule).  Stateless, so only for a complete range on a fresh engine state.
-  const bool halves = h->sem == PM_SEM_EXACT_HALVES && (h->seed_flags || h->halves_dev) && h->pats.size() < ((size_t)1 << 22) - 1;
+  const Route route = finalize_route(h);
+  const bool passthrough = route == Route::Passthrough, cluster_dp = route == Route::ClusterDp;
   std::vector<pm_hit> none;
-  if (halves) {
+  if (route == Route::Halves) {                                     // stateless, so only for a complete range on a fresh engine state
     if (!last || own.on || !h->halves_fresh || !h->carry.empty())
       return fail(h, PM_E_UNSUPPORTED, "pm_finalize_device: exact_halves on the device needs the whole range in one call after pm_reset (use pm_finalize)");
     const size_t m = h->seed_flags ? 2 * n : n;
     { int rcw = ensure_sort_workspace(h, m, true); if (rcw) return rcw; }
     if (h->vals_cap < h->ckeys_cap) {
-      void *old[] = {h->d_vals, h->d_vals_alt, h->d_htemp};
+      void *old[] = {h->d_vals, h->d_vals_alt, h->d_htemp};           // (all three go before the first is allocated again)
       for (void *q : old) if (q) (void)hipFree(q);
       h->d_vals = h->d_vals_alt = nullptr; h->d_htemp = nullptr;
       h->vals_cap = h->ckeys_cap;
@@ -2784,14 +2765,9 @@ static int finalize_device_impl(pm_handle *h, const void *d_cands, size_t n, int
     { int rcy = finalize_sync(h, next); if (rcy) return rcy; }
     const size_t nfin = (size_t)h->h_fcounts[0];
     if (n_out) *n_out = nfin;
-    if (land) return land_collect(h, h->d_fout, sorted, nfin, none, n_out);
-    if (keep) { h->d_final = h->d_fout; h->n_final = nfin; return PM_OK; }
-    if (nfin > cap) return fail(h, PM_E_OVERFLOW, "pm_finalize_device: out buffer too small");
-    if (nfin) HIP_TRY(h, hipMemcpy(out, h->d_fout, nfin * sizeof(pm_hit), hipMemcpyDeviceToHost));
-    if (flags & PM_FINALIZE_SORTED) sort_hits(out, nfin);
-    return PM_OK;
+    return deliver_finals(h, land, sorted, nfin, none, flags, out, cap, n_out);
   }
-  if (!passthrough && !cluster) return fail(h, PM_E_UNSUPPORTED, "pm_finalize_device: this option set needs the host stage (pm_finalize)");
+  if (route == Route::Host) return fail(h, PM_E_UNSUPPORTED, "pm_finalize_device: this option set needs the host stage (pm_finalize)");
   if (passthrough && land) {                                        // the records are the hits: sort, [next scan], copy
     bool sorted = false;
     { int rcs = land_enqueue_sort(h, src, nullptr, n, &sorted); if (rcs) return rcs; }
@@ -2844,10 +2820,8 @@ static int finalize_device_impl(pm_handle *h, const void *d_cands, size_t n, int
   const size_t ncarry = h->carry.size();
   if (ncarry) {
     if (h->d_carry_cap < ncarry) {
-      if (h->d_carry) (void)hipFree(h->d_carry);
-      h->d_carry = nullptr;
       h->d_carry_cap = ncarry + ncarry / 2 + 1024;
-      HIP_TRY(h, hipMalloc((void **)&h->d_carry, h->d_carry_cap * sizeof(pm_hit)));
+      PM_TRY(dev_regrow(h, &h->d_carry, h->d_carry_cap * sizeof(pm_hit), "d_carry"));
     }
     HIP_TRY(h, hipMemcpyAsync(h->d_carry, h->carry.data(), ncarry * sizeof(pm_hit), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, stream_wait(h));
@@ -2886,27 +2860,11 @@ static int finalize_device_impl(pm_handle *h, const void *d_cands, size_t n, int
     if (rc) return rc;
     if (own.on) extra.erase(std::remove_if(extra.begin(), extra.end(), [&](const pm_hit &x) { return !(x.end > own.own_lo && x.end <= own.own_hi); }), extra.end());
   }
-  if (land) {
-    const int rcl = land_collect(h, h->d_fout, sorted, nfin, extra, n_out);
-    if (h->knobs.debug) fprintf(stderr, "[pm] finalize_device (pm_scan): %zu records, device %.1f ms (%zu finals, %zu left for the host), host part + copies %.1f ms%s\n",
-                                n, tfd1 - tfd0, nfin, nleft, now_ms() - tfd1, h->spec ? ", next range's scan in flight" : "");
-    return rcl;
-  }
-  if (keep) {                                                       // the few host-decided hits join the device's in HBM
-    if (nfin + extra.size() > h->ckeys_cap) return fail(h, PM_E_OVERFLOW, "pm_finalize_device: device output buffer too small");
-    if (!extra.empty()) HIP_TRY(h, hipMemcpy(h->d_fout + nfin, extra.data(), extra.size() * sizeof(pm_hit), hipMemcpyHostToDevice));
-    h->d_final = h->d_fout; h->n_final = nfin + extra.size();
-    if (n_out) *n_out = h->n_final;
-    return PM_OK;
-  }
-  if (nfin + extra.size() > cap) return fail(h, PM_E_OVERFLOW, "pm_finalize_device: out buffer too small");
-  if (nfin) HIP_TRY(h, hipMemcpy(out, h->d_fout, nfin * sizeof(pm_hit), hipMemcpyDeviceToHost));
-  if (!extra.empty()) memcpy(out + nfin, extra.data(), extra.size() * sizeof(pm_hit));
-  const size_t tot = nfin + extra.size();
-  if (h->knobs.debug) fprintf(stderr, "[pm] finalize_device: %zu records, device %.1f ms (%zu finals, %zu left for the host), host part + copies %.1f ms\n", n, tfd1 - tfd0, nfin, nleft, now_ms() - tfd1);
-  if (flags & PM_FINALIZE_SORTED) sort_hits(out, tot);
-  if (n_out) *n_out = tot;
-  return PM_OK;
+  const int rcd = deliver_finals(h, land, sorted, nfin, extra, flags, out, cap, n_out);
+  if (h->knobs.debug && (land || (out && !rcd)))
+    fprintf(stderr, "[pm] finalize_device%s: %zu records, device %.1f ms (%zu finals, %zu left for the host), host part + copies %.1f ms%s\n",
+            land ? " (pm_scan)" : "", n, tfd1 - tfd0, nfin, nleft, now_ms() - tfd1, land && h->spec ? ", next range's scan in flight" : "");
+  return rcd;
 }
 
 // primer_match's per-hit re-alignment (reference primer_match.cc:1135-1151): exact_alignment
@@ -3072,10 +3030,7 @@ static int ensure_align_tables(pm_handle *h) {
   for (size_t r = 0; r < np; ++r) rank[perm[r]] = (uint32_t)r;
   const void *src[8] = {tab.data(), chars.data(), off.data(), esb.data(), eeb.data(), ids.data(), perm.data(), rank.data()};
   const size_t bytes[8] = {tab.size(), chars.size(), off.size() * 4, np * 4, np * 4, np * 4, np * 4, np * 4};
-  for (int i = 0; i < 8; ++i) {
-    HIP_TRY(h, hipMalloc(&h->ad_mem[i], bytes[i] ? bytes[i] : 4));
-    if (bytes[i]) HIP_TRY(h, hipMemcpy(h->ad_mem[i], src[i], bytes[i], hipMemcpyHostToDevice));
-  }
+  for (int i = 0; i < 8; ++i) PM_TRY(dev_upload(h, &h->ad_mem[i], src[i], bytes[i], 4, "ad_mem"));
   AlignDevice &a = h->ad;
   a.tab = (const uint8_t *)h->ad_mem[0]; a.pchars = (const uint8_t *)h->ad_mem[1]; a.poff = (const uint32_t *)h->ad_mem[2];
   a.esb = (const int32_t *)h->ad_mem[3]; a.eeb = (const int32_t *)h->ad_mem[4];
@@ -3177,10 +3132,8 @@ static int ensure_count_keys(pm_handle *h, size_t need, size_t keep) {
     HIP_TRY(h, hipMalloc((void **)&h->d_ck_scan, cap * 8));
   }
   if (h->cktemp_for < h->ck_cap) {
-    if (h->d_cktemp) (void)hipFree(h->d_cktemp);
-    h->d_cktemp = nullptr;
     h->cktemp_bytes = tally_temp_bytes(h->ck_cap);
-    HIP_TRY(h, hipMalloc(&h->d_cktemp, h->cktemp_bytes ? h->cktemp_bytes : 16));
+    PM_TRY(dev_regrow(h, &h->d_cktemp, h->cktemp_bytes ? h->cktemp_bytes : 16, "d_cktemp"));
     h->cktemp_for = h->ck_cap;
   }
   return PM_OK;
@@ -3212,10 +3165,8 @@ static int count_feed_device(pm_handle *h, const pm_hit *d_hits, const unsigned 
   if (n_upper >= ((size_t)1 << 31)) return fail(h, PM_E_INVALID, "pm_count_scan: internal: 2^31 or more final hits in one range");
   { int rc = ensure_count_keys(h, n_upper + ((size_t)1 << 12), 0); if (rc) return rc; }
   if (h->ad_any_long && h->hostq_cap < n_upper) {
-    if (h->d_hostq) (void)hipFree(h->d_hostq);
-    h->d_hostq = nullptr;
     h->hostq_cap = n_upper + n_upper / 4;
-    HIP_TRY(h, hipMalloc((void **)&h->d_hostq, h->hostq_cap * sizeof(pm_hit)));
+    PM_TRY(dev_regrow(h, &h->d_hostq, h->hostq_cap * sizeof(pm_hit), "d_hostq"));
   }
   HIP_TRY(h, align_hits_device(h->ad, h->d_text, h->n, d_hits, d_count, n_upper, nullptr, nullptr, nullptr, 0, h->d_ck,
                                h->ad_any_long ? h->d_hostq : nullptr, nullptr, h->d_actr, h->stream));
@@ -3298,16 +3249,12 @@ static int count_collect(pm_handle *h, size_t nfin, std::vector<pm_hit> &extra, 
   if (m) {
     { int rc = ensure_count_keys(h, nfin + 2 * m + ((size_t)1 << 12), nfin); if (rc) return rc; }
     if (h->d_extra_cap < m) {
-      if (h->d_extra) (void)hipFree(h->d_extra);
-      h->d_extra = nullptr;
       h->d_extra_cap = std::max<size_t>(2 * m, (size_t)1 << 12);
-      HIP_TRY(h, hipMalloc((void **)&h->d_extra, h->d_extra_cap * sizeof(pm_hit)));
+      PM_TRY(dev_regrow(h, &h->d_extra, h->d_extra_cap * sizeof(pm_hit), "d_extra"));
     }
     if (h->ad_any_long && h->hostq_cap < m) {
-      if (h->d_hostq) (void)hipFree(h->d_hostq);
-      h->d_hostq = nullptr;
       h->hostq_cap = std::max<size_t>(2 * m, (size_t)1 << 12);
-      HIP_TRY(h, hipMalloc((void **)&h->d_hostq, h->hostq_cap * sizeof(pm_hit)));
+      PM_TRY(dev_regrow(h, &h->d_hostq, h->hostq_cap * sizeof(pm_hit), "d_hostq"));
     }
     HIP_TRY(h, hipMemcpy(h->d_extra, extra.data(), m * sizeof(pm_hit), hipMemcpyHostToDevice));
     HIP_TRY(h, align_hits_device(h->ad, h->d_text, h->n, h->d_extra, nullptr, m, nullptr, nullptr, nullptr, 0, h->d_ck + nfin,
@@ -3404,12 +3351,11 @@ static int scan_piece(pm_handle *h, int64_t begin, int64_t end) {
     rc = pm_scan_candidates(h, begin, end, nullptr, 0, &cnt);
   }
   if (rc) return rc;
-  const bool halves_whole = h->sem == PM_SEM_EXACT_HALVES && (h->seed_flags || h->halves_dev) && begin == 0 && end >= h->n &&
-                            h->halves_fresh && h->carry.empty() && h->pats.size() < ((size_t)1 << 22) - 1;
-  const bool passthrough = h->sem == PM_SEM_KEYWORD_TREE || h->sem == PM_SEM_SHIFT_AND || h->sem == PM_SEM_SHIFT_AND_INEXACT ||
-                           (h->sem == PM_SEM_EXACT_BASES && h->bases_flags);
-  if ((h->edits_dev && h->sem == PM_SEM_FILTER_BITVEC && !h->cfg.wildcards && h->pats.size() < ((size_t)1 << 22)) || halves_whole ||
-      (device_cluster_plain(h) && h->kern == PM_KERNEL_SEED) || passthrough) {
+  // pm_scan's own conditions: the halves rule needs the whole stream on a fresh state, plain clustering the seed kernels' records
+  const Route route = finalize_route(h);
+  const bool halves_whole = begin == 0 && end >= h->n && h->halves_fresh && h->carry.empty();
+  if (route == Route::Passthrough || route == Route::ClusterDp || (route == Route::Halves && halves_whole) ||
+      (route == Route::Cluster && h->kern == PM_KERNEL_SEED)) {
     // sort, clusters and their DPs on the device; only what it hands back goes through the host stage
     ScanNext next = {end < h->n && !h->dense_mode, end, std::min<int64_t>(h->n, end + (end - begin))};   // (no guess after a cut: the pieces are not the caller's ranges)
     const OwnedRange all = {0, 0, 0, 0, 0};

@@ -444,6 +444,81 @@ def test_halves_seed_overflow_is_recovered():
     assert want == [tuple(h) for h in c["engine"]["auto_k1"]["hits"]]
 
 
+def test_host_added_edge_records_overflow_reports_the_need():
+    """PM_E_OVERFLOW raised by the records the host adds at the stream's edges (pm_api.cpp: edits_start_candidates /
+    edits_end_candidates, stream_start_candidates, stream_end_overhang_candidates, the exact_bases -k edge blocks).
+    From a record buffer of one entry a whole-stream scan overflows exactly twice: first with the kernels' count, then --
+    the buffer now holds just that -- with the kernels' count plus the host's records; the third scan succeeds and
+    leaves the records a generous buffer gets."""
+    table = b"ACGT\n"
+    rng = np.random.default_rng(2033)
+    body = "".join("ACGT"[c] for c in rng.integers(0, 4, 2000))
+    head, tail = body[:32], body[-32:]
+    other = lambda c: "ACGT"[("ACGT".index(c) + 1) % 4]
+    codes = synth.normalize(body.encode(), table)
+    text = O.Text(codes, table)
+    n = codes.size
+    cut = lambda L: [head[:L], head[32 - L:], tail[:L], tail[32 - L:]]
+    at_start, at_end, beyond = (lambda h: h[0] <= 32), (lambda h: h[0] > n - 4), (lambda h: h[0] > n)
+    cases = [
+        # edit start / end rules: the automaton's candidates that end in the first Lw + 2k + 2 and the last four characters
+        ("edits", dict(k=2, indels=True, semantics=sat_amd.SEM_FILTER_BITVEC), 5, cut(22), 0, lambda h: at_start(h) or at_end(h)),
+        # stream_start_candidates: a pattern whose first character is missing in front of stream index 0 (end 19, one error)
+        ("start", dict(k=1, indels=False, semantics=sat_amd.SEM_SHIFT_AND_INEXACT), 100, cut(20) + [other(body[0]) + body[:19]], 0, lambda h: h[0] < 20),
+        # stream_end_overhang_candidates: the last t pattern characters lie on the zero padding behind the stream
+        ("overhang", dict(k=1, indels=False, semantics=sat_amd.SEM_EXACT_HALVES), 12, cut(22) + [tail[-(22 - t):] + "A" * t for t in (1, 2, 5)], 0, beyond),
+        # exact_bases -k: occurrences of the mandated first block in the first and last 56 characters
+        ("blocks", dict(k=1, indels=True, semantics=sat_amd.SEM_EXACT_BASES), 8, cut(22) + [head[1:22] + "G", "C" + tail[-21:]], 8, lambda h: h[0] < 40 or h[0] > n - 3),
+    ]
+    for name, opts, eng, pats, esb, is_edge in cases:
+        E, F = [esb] * len(pats), [0] * len(pats)
+        want = O.sorted_tuples(O.find_all(text, pats, engine=eng, k=opts["k"], indels=opts["indels"], esb=E, eeb=F))
+        assert any(is_edge(h) for h in want), (name, want)
+
+        def handle():
+            pm = sat_amd.PatternMatch(kernel=sat_amd.KERNEL_SEED, **opts)
+            for i, p in enumerate(pats):
+                pm.add_pattern(p, i + 1, esb, 0)
+            pm.init(codes, table)
+            assert pm.selected()[1] == sat_amd.KERNEL_SEED, name
+            return pm
+
+        def records(pm, count):
+            ptr, cnt = pm.candidates_device()
+            assert cnt == count, (name, cnt, count)
+            return sorted(r.tobytes() for r in pm.copy_records(ptr, cnt))
+
+        pm = handle()
+        pm.scan_async(0, n)
+        generous = records(pm, pm.scan_wait())
+        pm.close()
+        pm = handle()
+        capacity, needs, got = 1, [], None
+        pm.set_capacity(capacity)
+        while got is None:
+            assert len(needs) < 4, (name, needs)
+            pm.scan_async(0, n)
+            try:
+                got = pm.scan_wait()
+            except sat_amd.PmError as err:
+                assert err.code == sat_amd.PM_E_OVERFLOW and "pm_set_capacity" in str(err), (name, err)
+                assert err.required > capacity, (name, err.required, capacity)
+                needs.append(err.required)
+                capacity = err.required
+                pm.set_capacity(capacity)
+        print(name, "kernel records, with the host's:", needs, "after the scan:", got, "of", len(generous))
+        assert len(needs) == 2 and needs[0] < needs[1], (name, needs)
+        if name in ("start", "overhang"):
+            # no dedup behind these rules and one record per hit: the kernels' records are the oracle's hits inside the
+            # stream, the host's the edge hits, and the second need is exactly what the generous buffer ends up holding
+            host = sum(1 for h in want if is_edge(h))
+            assert needs == [len(generous) - host, len(generous)] and len(generous) == len(want), (name, needs, host, len(generous))
+        else:
+            assert needs[0] >= got, (name, needs, got)              # (the dedup only ever removes records)
+        assert records(pm, got) == generous and got > 0, (name, got, len(generous))
+        pm.close()
+
+
 def test_internal_suspect_buffer_overflow_rescans_inside_the_library():
     """The pair plan's suspect list (between pm_pair_scan and pm_pair_verify) is sized for random streams; on
     3 x 1.4 Mbp of A against A^20 and its neighbours every window is a suspect of every field pair: the
