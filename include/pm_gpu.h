@@ -70,7 +70,9 @@ typedef enum {
   PM_KERNEL_BITPAR = 16,   /* bit-parallel Shift-And / Wu-Manber rows, any alphabet, <= 6 accepted stream codes */
   PM_KERNEL_SEED = 17      /* 2-bit packed k-mer seeds (LDS filter) + verify; A,C,G,T patterns <= 32 nt (edit distance,
                               -k 1 / -k 2 on filter_bitvec or shift_and_inexact: 16..32 nt -- 20..32 on the pair / piece
-                              plans, 16..19 on pm_short_edit_scan) */
+                              plans, 16..19 on pm_short_edit_scan).  Under PM_KERNEL_AUTO a -K 1 / -K 2 list of 20..32
+                              and 16..19 nt patterns runs on the pair plan and pm_short_sub_scan side by side; asked
+                              for by name, this family keeps such a list on one plan, the Bloom plan */
 } pm_kernel;
 
 /* Replaces the constructor arguments of the reference engines as pick_pattern_index passes them

@@ -11,7 +11,12 @@ the hit count and a checksum of the final hits.
 The same script runs on the commit before pm_short_edit_scan (PM_GPU_LIB=<that build's libpm_gpu.so>): there the 18-mers
 are "patterns the seed plan does not take" and go to the bit-parallel residue kernel.  --merge joins two such outputs
 into the table of DESIGN.md 4.7 and checks that hit count and checksum agree at every S.  Kernel times of their own come
-from a run under rocprofv3 --kernel-trace --stats (--s 20000 --runs 0)."""
+from a run under rocprofv3 --kernel-trace --stats (--s 20000 --runs 0).
+
+--indels 0 is the same measurement for -K 2 and pm_short_sub_scan: the 18-mers carry substitutions only (a
+third exact, a third with one, a third with two), the output goes to profiles/short_sub_class.json, and on the commit
+before (or with PM_SHORT_SUB=off) one 18-mer sends the whole list from the pair plan to the Bloom plan.  For interleaved
+runs of the two builds each side of --merge takes several outputs, comma separated: their passes are pooled per S."""
 import argparse
 import json
 import os
@@ -41,14 +46,16 @@ def make_stream(n, seed):
     return t
 
 
-def short_primers(dev, rng, count, L):
+def short_primers(dev, rng, count, L, indels=True):
     host = dev[: 1 << 26].cpu().numpy()
     out = []
     while len(out) < count:
         a = int(rng.integers(1, host.size - L - 3))
         w = LUT[host[a:a + L + 2] & 3].tobytes().decode()
         kind = len(out) % 3
-        if kind == 0:
+        if not indels:
+            w = synth.mutate(rng, w[:L], nsub=kind)
+        elif kind == 0:
             w = w[:L]
         elif kind == 1:
             w = synth.mutate(rng, w[:L], nsub=int(rng.integers(0, 2)), nins=0, ndel=0) if rng.random() < 0.5 else synth.mutate(rng, w[:L + 1], ndel=1)
@@ -78,8 +85,20 @@ def one_pass(pm, n, chunk):
     return time.perf_counter() - t0, nhits, check, dev_ms, between
 
 
+def pooled(paths):
+    """outputs of several runs of one build: per S, the passes of all of them"""
+    docs = [json.load(open(p)) for p in paths.split(",")]
+    for d in docs[1:]:
+        for r0, r in zip(docs[0]["rows"], d["rows"]):
+            assert (r0["S"], r0["hits"], r0["checksum"]) == (r["S"], r["hits"], r["checksum"]), (r0, r)
+            if r0["pass_s"] and r["pass_s"]:
+                r0["pass_s"] = [min(r0["pass_s"][0], r["pass_s"][0]), max(r0["pass_s"][1], r["pass_s"][1])]
+    docs[0]["runs"] = sum(d["runs"] for d in docs)
+    return docs[0]
+
+
 def merge(paths, out):
-    a, b = (json.load(open(p)) for p in paths)
+    a, b = (pooled(p) for p in paths)
     rows = []
     for ra in a["rows"]:
         rb = next((r for r in b["rows"] if r["S"] == ra["S"]), None)
@@ -103,9 +122,12 @@ def main():
     ap.add_argument("--length", type=int, default=18)
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--chunk", type=int, default=1 << 30)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "short_class.json"))
+    ap.add_argument("--indels", type=int, default=1, help="1: -k 2 (pm_short_edit_scan), 0: -K 2 (pm_short_sub_scan)")
+    ap.add_argument("--out", default=None, help="default: profiles/short_class.json, with --indels 0 profiles/short_sub_class.json")
     ap.add_argument("--merge", nargs=2, metavar=("THIS", "PARENT"), help="join two outputs of this script into --out")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "short_class.json" if args.indels else "short_sub_class.json")
     if args.merge:
         return merge(args.merge, args.out)
     dev = make_stream(args.n, 7)
@@ -113,10 +135,10 @@ def main():
     longs = [LUT[r].tobytes().decode() for r in rng.integers(0, 4, size=(args.npat, 20), dtype=np.uint8)]
     rows = []
     for S in (int(x) for x in args.s.split(",")):
-        shorts = short_primers(dev, np.random.default_rng(100 + S), S, args.length)
+        shorts = short_primers(dev, np.random.default_rng(100 + S), S, args.length, bool(args.indels))
         pats = longs + shorts
         allp = pats + [sat_amd.reverse_comp(p) for p in pats]
-        pm = sat_amd.PatternMatch(k=2, indels=True)
+        pm = sat_amd.PatternMatch(k=2, indels=bool(args.indels))
         for i, p in enumerate(allp):
             pm.add_pattern(p, i + 1)
         pm.init_device(dev.data_ptr(), args.n, TABLE, keepalive=dev)

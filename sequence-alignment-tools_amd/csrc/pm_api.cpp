@@ -194,6 +194,11 @@ struct pm_handle {
   size_t nshort = 0;
   bool short_only = false;            // no main class: the short engine is the handle's whole device stage
   ShortDevice shd;
+  // -K 1 / -K 2, patterns of 16..19 characters: a class of their own on pm_short_sub_scan beside a main class on the pair
+  // plan.  Both classes write the same records into d_cands; the host's edge records cover both.
+  std::vector<uint8_t> in_ssub;       // per pattern: 1 = scanned by pm_short_sub_scan
+  size_t nssub = 0;
+  ShortSubDevice ssd;
   bool halves_fresh = true;           // no host-side exact_halves state (lasthit, carried seeds) since init / pm_reset
 
   // windowed stream (pm_init_windowed): d_text / d_packed point at the bound slot, rebased so that absolute stream
@@ -236,7 +241,7 @@ struct pm_handle {
 };
 
 // per-tile record counts between a scan's first-stage and verify kernels: [0] unused, [1 + t] tile t, then 8 measurement counters
-// [SHORT_COUNT_AT]: seed records of the short class (all its tiles)
+// [SHORT_COUNT_AT]: seed records of the short class (all its tiles); the pair plan's short class counts its suspects there
 constexpr size_t SEEDCOUNT_WORDS = 1 + 256 + 8 + 1;
 constexpr size_t SHORT_COUNT_AT = 1 + 256 + 8;
 
@@ -408,6 +413,7 @@ static void read_knobs(Knobs *k) {
   k->bitpar_seglen = num("PM_BITPAR_SEGLEN");
   k->dense_bound = num("PM_DENSE_BOUND");
   k->short_bitpar = is("PM_SHORT_SCAN", "bitpar"); k->short_tile = (long)num("PM_SHORT_TILE");
+  k->short_sub_off = is("PM_SHORT_SUB", "off");
   k->debug = getenv("PM_DEBUG") != nullptr;
 }
 
@@ -461,6 +467,7 @@ static void free_device(pm_handle *h) {
   h->d_fsorted = nullptr; h->fsorted_cap = 0;
   bitpar_free(&h->bp);
   short_free(&h->shd);
+  short_sub_free(&h->ssd);
   seed_free(&h->sd);
   for (SeedDevice &d : h->sd_more) seed_free(&d);
   h->sd_more.clear();
@@ -662,8 +669,10 @@ static bool seed_eligible(pm_handle *h, std::string *why) {
   // (pm_pair.hip), whose exact verify knows the patterns' exact zones: a substitution there fails
   // the reference's constrained verifies (pattern_alignment.cc:320-323, primer_alignment.cc:155)
   bool pair_ok = !h->cfg.indels && (h->cfg.k == 1 || h->cfg.k == 2) && !h->pats.empty();
-  for (const Pattern &p : h->pats) {
-    pair_ok = pair_ok && p.s.size() >= 20 && p.s.size() <= 32;
+  for (size_t i = 0; i < h->pats.size(); ++i) {
+    const Pattern &p = h->pats[i];
+    const bool sub = i < h->in_ssub.size() && h->in_ssub[i];        // 16..19 characters beside the pair plan: pm_short_sub_scan, the same exact verify
+    pair_ok = pair_ok && p.s.size() >= (sub ? 16u : 20u) && p.s.size() <= 32;
     for (unsigned char ch : p.s) pair_ok = pair_ok && (ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T');
   }
   if (h->knobs.pair >= 0) pair_ok = pair_ok && h->knobs.pair != 0;
@@ -671,6 +680,43 @@ static bool seed_eligible(pm_handle *h, std::string *why) {
   if ((sem == PM_SEM_FILTER_BITVEC || sem == PM_SEM_EXACT_HALVES) && !pair_ok)
     for (const Pattern &p : h->pats) if (p.esb || p.eeb) { *why = "exact-base constraints need the text-based verify of the bit-parallel family"; return false; }
   return true;
+}
+
+// -K 1 / -K 2 on a list of mixed lengths: the primers of 16..19 characters become a class of their own
+// (in_ssub) when the list also holds a primer of 20..32 characters the pair plan takes and every other primer the seed
+// family could take has 16..19.  Anything else -- a primer of 10..15 characters, no long or no short primer, more short
+// primers than SHORT_SUB_MAX_PATTERNS, exact_bases, a kernel on request, -k, k = 0, PM_SHORT_SUB=off -- leaves the list on
+// the route it had.  Called with in_rest decided.
+static void short_sub_route(pm_handle *h) {
+  h->in_ssub.assign(h->pats.size(), 0);
+  h->nssub = 0;
+  if (h->knobs.short_sub_off || h->knobs.pair == 0 || h->cfg.indels || (h->cfg.k != 1 && h->cfg.k != 2) || h->kern != PM_KERNEL_AUTO) return;
+  if (h->sem != PM_SEM_FILTER_BITVEC && h->sem != PM_SEM_SHIFT_AND_INEXACT && h->sem != PM_SEM_EXACT_HALVES) return;
+  if (h->cfg.wildcards && !h->wild_seed) return;
+  const Alphabet &A = h->alpha;
+  const bool norm = A.nch['A'] == 0 && A.nch['C'] == 1 && A.nch['G'] == 2 && A.nch['T'] == 3;
+  const bool ascii = A.size == 256 && A.nch['A'] == 'A' && A.nch['C'] == 'C' && A.nch['G'] == 'G' && A.nch['T'] == 'T';
+  if (!norm && !ascii) return;                                      // (what pair_build asks of the stream)
+  size_t nmain = 0, nsub = 0;
+  std::vector<uint8_t> sub(h->pats.size(), 0);
+  std::vector<std::string> variants;
+  for (size_t i = 0; i < h->pats.size(); ++i) {
+    const Pattern &p = h->pats[i];
+    const size_t L = p.s.size();
+    bool ok = L >= 10 && L <= 32;                                   // the main class's conditions (init_common)
+    if (h->wild_seed) ok = ok && expand_iupac(p.s, 16, &variants) && !(h->sem == PM_SEM_FILTER_BITVEC && pattern_n_quirk(h, p));
+    else for (unsigned char ch : p.s) ok = ok && (ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T');
+    if (!ok) {
+      if (h->sem == PM_SEM_EXACT_HALVES) return;                    // (no residue beside exact_halves)
+      continue;                                                     // residue: the bit-parallel kernel, after both classes
+    }
+    if (L >= 20) ++nmain;
+    else if (L >= 16) { sub[i] = 1; ++nsub; }
+    else return;
+  }
+  if (!nmain || !nsub || nsub > SHORT_SUB_MAX_PATTERNS) return;     // (above the cap the key runs outgrow what the Bloom plan costs)
+  h->in_ssub.swap(sub);
+  h->nssub = nsub;
 }
 
 static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
@@ -691,7 +737,7 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
   h->eos_code = h->alpha.nch[(uint8_t)h->cfg.eos];                  // shift_and_inexact.cc:131
   int rc = resolve(h);
   if (rc) return rc;
-  bitpar_free(&h->bp); seed_free(&h->sd); short_free(&h->shd);
+  bitpar_free(&h->bp); seed_free(&h->sd); short_free(&h->shd); short_sub_free(&h->ssd);
   for (SeedDevice &d : h->sd_more) seed_free(&d);
   h->sd_more.clear();
   for (PairDevice &d : h->pair) pair_free(&d);
@@ -752,6 +798,7 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
     }
   }
   h->short_only = h->nshort != 0 && h->nshort == h->inner.size();
+  short_sub_route(h);
   if (want_seed && !seed_eligible(h, &why)) {
     if (h->kern == PM_KERNEL_SEED) return fail(h, PM_E_UNSUPPORTED, "seed engine: " + why);
     want_seed = false;
@@ -770,7 +817,7 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
         partners.push_back(sp[i].s); sides.push_back(1);          // right half: partner to the left
       }
     } else if (h->sem == PM_SEM_EXACT_HALVES) {   // -K: whole patterns, distance <= k, halves decided by flags
-      for (size_t i = 0; i < h->pats.size(); ++i) { sp.push_back(h->pats[i]); sid.push_back((uint32_t)(i + 1)); }
+      for (size_t i = 0; i < h->pats.size(); ++i) if (!h->in_ssub[i]) { sp.push_back(h->pats[i]); sid.push_back((uint32_t)(i + 1)); }
       sk = h->cfg.k;
     } else if (h->sem == PM_SEM_EXACT_BASES) {
       // -K: an occurrence of the mandated exact block whose remainder verifies (exact_bases.cc:92-121, the
@@ -782,13 +829,13 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
     } else if (h->wild_seed) {                    // every concrete variant of a primer is a seed-family pattern with the primer's id
       std::vector<std::string> variants;
       for (size_t i = 0; i < h->inner.size(); ++i) {
-        if (h->in_rest[i] || h->in_short[i]) continue;
+        if (h->in_rest[i] || h->in_short[i] || h->in_ssub[i]) continue;
         expand_iupac(h->inner[i].s, 16, &variants);
         for (const std::string &v : variants) { Pattern q = h->inner[i]; q.s = v; sp.push_back(q); sid.push_back(h->inner_ids[i]); }
       }
       if (sp.empty() && !h->short_only) { sp.push_back(Pattern{std::string(edits_mode ? 20 : 10, 'A'), 0, 0, 0}); sid.push_back(0); why = "no primer the seed family could take"; }
-    } else if (h->nrest || h->nshort) {
-      for (size_t i = 0; i < h->inner.size(); ++i) if (!h->in_rest[i] && !h->in_short[i]) { sp.push_back(h->inner[i]); sid.push_back(h->inner_ids[i]); }
+    } else if (h->nrest || h->nshort || h->nssub) {
+      for (size_t i = 0; i < h->inner.size(); ++i) if (!h->in_rest[i] && !h->in_short[i] && !h->in_ssub[i]) { sp.push_back(h->inner[i]); sid.push_back(h->inner_ids[i]); }
     } else { sp = h->inner; sid = h->inner_ids; }
     // the automata and the keyword tree know nothing of exact_start_bases / exact_end_bases (shift_and_inexact.cc:85-86
     // stores them and never looks): their records are every window within k, whatever zone a substitution falls in
@@ -878,11 +925,33 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
         if (h->short_only) { h->sd.k = sk; h->sd.Lw = 16; h->sd.ascii = stt.ascii; h->sd.maxlen = stt.maxlen; }   // (the plan facts the rest of this file reads from h->sd)
       }
     }
+    if (why.empty() && h->nssub) {                                  // -K: the class of 16..19 characters beside the pair plan's tiles
+      std::vector<Pattern> shp; std::vector<uint32_t> shid;
+      std::vector<std::string> variants;
+      for (size_t i = 0; i < h->pats.size(); ++i) {
+        if (!h->in_ssub[i]) continue;
+        if (h->sem == PM_SEM_EXACT_HALVES) { shp.push_back(h->pats[i]); shid.push_back((uint32_t)(i + 1)); }   // whole patterns, as in the main class
+        else if (h->wild_seed) {
+          expand_iupac(h->inner[i].s, 16, &variants);
+          for (const std::string &v : variants) { Pattern q = h->inner[i]; q.s = v; shp.push_back(q); shid.push_back(h->inner_ids[i]); }
+        } else { shp.push_back(h->inner[i]); shid.push_back(h->inner_ids[i]); }
+      }
+      if (h->sem == PM_SEM_SHIFT_AND_INEXACT) for (Pattern &p : shp) { p.esb = 0; p.eeb = 0; }   // (the automaton knows no exact zones, see above)
+      ShortSubTables stt;
+      why = use_pair ? short_sub_build(shp, shid, h->alpha, sk, h->eos_code, h->knobs.short_tile > 0 ? (size_t)h->knobs.short_tile : 0, &stt)
+                     : std::string("the pair plan does not take the list's patterns of 20..32 characters");
+      if (why.empty() && stt.tiles.size() > 256) why = "too many pattern tiles for pm_short_sub_scan";
+      if (why.empty()) {
+        HIP_TRY(h, short_sub_upload(stt, &h->ssd, h->stream));
+        h->ssd.viol_level = h->sem == PM_SEM_FILTER_BITVEC ? 3 : 0;  // as the main class's
+      }
+    }
     if (!why.empty()) {
       seed_free(&h->sd);
       for (SeedDevice &d : h->sd_more) seed_free(&d);
       h->sd_more.clear();
       short_free(&h->shd);
+      short_sub_free(&h->ssd);
       if (h->kern == PM_KERNEL_SEED) return fail(h, PM_E_UNSUPPORTED, "seed engine: " + why);
       want_seed = false;
     } else {
@@ -940,6 +1009,7 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
     h->halves_dev = false; h->edits_dev = false; h->half_ranked_any = false;
     std::fill(h->in_rest.begin(), h->in_rest.end(), 0); h->nrest = 0;
     std::fill(h->in_short.begin(), h->in_short.end(), 0); h->nshort = 0; h->short_only = false;
+    std::fill(h->in_ssub.begin(), h->in_ssub.end(), 0); h->nssub = 0;
     h->kern = PM_KERNEL_BITPAR;
     BitparTables tabs;
     std::string msg = bitpar_build(h->inner, h->inner_ids, h->alpha, h->scan_k, h->eos_code, &tabs,
@@ -1520,6 +1590,10 @@ extern "C" int pm_describe(const pm_handle *h, char *buf, size_t buflen) {
     const size_t at = strlen(buf);
     if (at < buflen) snprintf(buf + at, buflen - at, " + pm_short_edit_scan for %zu patterns of 16..19 characters (tiles=%d, tests=%d)", h->nshort, (int)h->shd.tiles.size(), h->shd.k == 2 ? SHORT_NTESTS : 2);
   }
+  if (h->kern == PM_KERNEL_SEED && h->nssub) {
+    const size_t at = strlen(buf);
+    if (at < buflen) snprintf(buf + at, buflen - at, " + pm_short_sub_scan for %zu patterns of 16..19 characters (tiles=%d, pairs=%d)", h->nssub, (int)h->ssd.tiles.size(), h->ssd.ncombos);
+  }
   if (h->kern == PM_KERNEL_SEED) return PM_OK;
   else
     snprintf(buf, buflen, "kernel=%s tiles=%d lanes_per_tile=64 words_per_lane=%d seg_len=%lld nseg=%d grid=%d block=%d",
@@ -1615,8 +1689,15 @@ extern "C" int pm_scan_candidates_async(pm_handle *h, int64_t begin, int64_t end
     for (size_t t = 0; t < h->pair.size(); ++t)
       HIP_TRY(h, pair_launch(h->pair[t], h->d_text, h->d_packed, h->n, begin, end, h->d_cands, h->d_counter, h->cap,
                              h->d_susp, h->d_seed_count + 1 + t, h->susp_cap, h->stream, t == 0 ? &h->geo : nullptr, h->d_seed_count + 257));
-    HIP_TRY(h, hipMemcpyAsync(h->h_seed_count, h->d_seed_count, SEEDCOUNT_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
     h->last_launches = 2 * (int)h->pair.size();
+    if (h->nssub) {
+      // the class of 16..19 characters into the same record buffer; its 8-byte suspects reuse the suspect list, which the
+      // main class's verify launches have read by then (stream order), under a counter of their own
+      HIP_TRY(h, short_sub_launch(h->ssd, h->d_text, h->d_packed, h->n, begin, end, h->d_cands, h->d_counter, h->cap, (uint64_t *)h->d_susp,
+                                  h->d_seed_count + SHORT_COUNT_AT, h->susp_cap * (PAIR_SUSPECT_BYTES / sizeof(uint64_t)), h->stream));
+      h->last_launches += (int)h->ssd.tiles.size() + 1;
+    }
+    HIP_TRY(h, hipMemcpyAsync(h->h_seed_count, h->d_seed_count, SEEDCOUNT_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
     if (h->nrest) { HIP_TRY(h, bitpar_launch(h->bp, h->d_text, h->n, begin, end, h->d_cands, h->d_counter, h->cap, h->stream, nullptr)); ++h->last_launches; }
   }
   else if (h->kern == PM_KERNEL_SEED)
@@ -1953,7 +2034,7 @@ static int scan_wait_once(pm_handle *h, size_t *n_out) {
     const size_t tiles = !h->pair.empty() ? h->pair.size() : 1 + h->sd_more.size();
     for (size_t t = 0; t < tiles && t < 256; ++t) h->last_peak = std::max(h->last_peak, h->h_seed_count[1 + t]);
     h->last_peak = std::max(h->last_peak, h->h_seed_count[260]);
-    if (h->nshort) h->last_peak = std::max(h->last_peak, h->h_seed_count[SHORT_COUNT_AT]);
+    if (h->nshort || h->nssub) h->last_peak = std::max(h->last_peak, h->h_seed_count[SHORT_COUNT_AT]);
   }
   if (h->bound_on && cnt > dense_bound(h)) return dense_fail(h, "candidate records", cnt);
   if (cnt > h->cap) { h->last_count = 0; return fail(h, PM_E_OVERFLOW, "candidate buffer too small (pm_set_capacity)"); }
@@ -1997,6 +2078,7 @@ static int scan_wait_once(pm_handle *h, size_t *n_out) {
     // the suspect buffer must have held every tile's suspects
     unsigned long long worst = 0;
     for (size_t t = 0; t < h->pair.size(); ++t) worst = std::max(worst, h->h_seed_count[1 + t]);
+    if (h->nssub) worst = std::max(worst, (h->h_seed_count[SHORT_COUNT_AT] + 1) / 2);   // (8-byte suspects in the 16-byte slots)
     if (h->knobs.debug) fprintf(stderr, "[pm] pair plan: %llu suspects (tile with most), capacity %zu, candidates %zu\n", worst, h->susp_cap, cnt);
     if (h->bound_on && worst > dense_bound(h)) return dense_fail(h, "suspects of the pair plan", worst);
     if (worst > h->susp_cap) {                                     // grow it and tell the caller to scan again
@@ -2098,7 +2180,7 @@ extern "C" int pm_scan_stats(pm_handle *h, uint64_t *out, int n) {
   if (h->h_seed_count) {
     const size_t tiles = !h->pair.empty() ? h->pair.size() : 1 + h->sd_more.size();
     for (size_t t = 0; t < tiles && t < 256; ++t) v[1] = std::max<uint64_t>(v[1], h->h_seed_count[1 + t]);
-    if (h->nshort) v[1] += h->h_seed_count[SHORT_COUNT_AT];       // (+ the short class's seed records)
+    if (h->nshort || h->nssub) v[1] += h->h_seed_count[SHORT_COUNT_AT];   // (+ the short class's seed records / suspects)
     v[3] = h->h_seed_count[257]; v[4] = h->h_seed_count[258]; v[5] = h->h_seed_count[259];
   }
   v[2] = h->internal_rescans;

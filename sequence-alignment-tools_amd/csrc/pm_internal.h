@@ -28,7 +28,7 @@ struct Alphabet {
 };
 
 // Test and measurement knobs (PM_SEED_CHUNK, PM_SEED_GROUP, PM_SEED_DEBUG, PM_SEED_TILE, PM_PAIR, PM_PAIR_ROW, PM_PAIR_MAP, PM_HALF_SCAN,
-// PM_EDIT_SCAN, PM_EDIT_TABLE_LOG, PM_SHORT_SCAN, PM_SHORT_TILE, PM_BITPAR_TP, PM_BITPAR_SEGLEN, PM_DEBUG).  The environment is read ONCE, by
+// PM_EDIT_SCAN, PM_EDIT_TABLE_LOG, PM_SHORT_SCAN, PM_SHORT_TILE, PM_SHORT_SUB, PM_BITPAR_TP, PM_BITPAR_SEGLEN, PM_DEBUG).  The environment is read ONCE, by
 // pm_create (pm_api.cpp read_knobs), into the handle: nothing on the init or launch path calls getenv, and a
 // handle's behaviour does not change when its caller's environment does.  Every field's 0 / -1 / false = unset.
 struct Knobs {
@@ -47,7 +47,8 @@ struct Knobs {
   long long bitpar_seglen = 0;
   long long dense_bound = 0;         // PM_DENSE_BOUND: records per list beyond which pm_scan cuts a range in two (0: 2^29)
   bool short_bitpar = false;         // PM_SHORT_SCAN=bitpar: patterns of 16..19 characters go to the bit-parallel residue, not to pm_short_edit_scan
-  long short_tile = 0;               // PM_SHORT_TILE: patterns per tile of pm_short_edit_scan
+  long short_tile = 0;               // PM_SHORT_TILE: patterns per tile of pm_short_edit_scan / pm_short_sub_scan
+  bool short_sub_off = false;        // PM_SHORT_SUB=off: -K lists with patterns of 16..19 characters leave the pair plan as a whole (A/B runs, tests)
   bool debug = false;                // PM_DEBUG: stage timings on stderr
 };
 
@@ -223,6 +224,56 @@ void short_free(ShortDevice *d);
 hipError_t short_launch(const ShortDevice &d, const uint8_t *d_text, const uint32_t *d_packed, int64_t n, int64_t begin, int64_t end,
                         pm_hit *d_out, unsigned long long *d_counter, uint64_t cap, uint64_t *d_seeds, unsigned long long *d_seed_count,
                         uint64_t seed_cap, hipStream_t st, ScanGeometry *geo_out);
+
+// ---- substitutions only (-K 1, -K 2) for patterns of 16..19 characters (pm_short.hip) ---------------
+// A class beside a main class on the pair plan (pm_pair.hip): pm_short_sub_scan (field pairs of the last 16 bases: six at
+// k = 2, two at k = 1; 8-byte run entries {pattern, its last 16 bases}) + pm_short_sub_verify, which runs pm_verify.h's
+// pair_verify<4> -- the pair plan's exact stage with fields of four bases -- so both classes write records of one meaning.
+constexpr int SUB_MAX_COMBOS = 6;
+// Largest class the routing takes (patterns as added, both strands counted): where the pass with the class met the
+// Bloom plan's pass for the whole list (3 Gbp, 100k 20-mers x 2 strands, 12,000 18-mers x 2: 75 - 102 ms against 78 - 107 ms;
+// 8,000 x 2: 57 against 75 ms; 16,000 x 2: 93 against 81 - 106 ms).  Lists above it keep the Bloom plan.
+constexpr size_t SHORT_SUB_MAX_PATTERNS = 24000;
+
+struct ShortSubTables {            // host-built, then uploaded
+  int k = 0, maxlen = 0, eos_code = -1, ncombos = 0;
+  bool ascii = false;
+  int fa[SUB_MAX_COMBOS] = {}, fb[SUB_MAX_COMBOS] = {};   // key fields of every combo (a < b) in the order that decides who reports
+  std::vector<uint8_t> pat_len;    // per pattern of the class
+  std::vector<uint32_t> pat_id;
+  std::vector<uint8_t> pat_codes;  // 32 stream codes per pattern
+  std::vector<uint32_t> pat_zone;  // bit i: pattern character i lies in an exact zone
+  struct Tile {
+    uint32_t base = 0;             // class index of the tile's first pattern
+    std::vector<uint32_t> bitmap;  // [combo][2048]: bit = 16-bit key of some pattern
+    std::vector<uint32_t> rows;    // [combo][65537]: first entry of the key's run in runs
+    std::vector<uint64_t> runs;    // [combo][patterns of the tile] by key: pattern index inside the tile | last 16 bases << 32
+  };
+  std::vector<Tile> tiles;
+};
+
+struct ShortSubDevice {
+  int k = 0, maxlen = 0, eos_code = -1, ncombos = 0;
+  bool ascii = false;
+  int fa[SUB_MAX_COMBOS] = {}, fb[SUB_MAX_COMBOS] = {};
+  size_t npat = 0;
+  uint8_t *pat_len = nullptr, *pat_codes = nullptr;
+  uint32_t *pat_id = nullptr, *pat_zone = nullptr;
+  struct Tile { uint32_t base = 0; uint32_t *bitmap = nullptr, *rows = nullptr; uint64_t *runs = nullptr; };
+  std::vector<Tile> tiles;
+  int viol_level = 0;              // as PairDevice::viol_level (set by the caller after short_sub_upload)
+};
+
+std::string short_sub_build(const std::vector<Pattern> &pats, const std::vector<uint32_t> &ids, const Alphabet &alpha, int k, int eos_code,
+                            size_t tile, ShortSubTables *out);
+hipError_t short_sub_upload(const ShortSubTables &t, ShortSubDevice *d, hipStream_t st);
+void short_sub_free(ShortSubDevice *d);
+// Enqueue the scan of (begin, end] on `st`: candidate records are appended to d_out / d_counter like pair_launch's.  The
+// 8-byte suspects in between go to d_susp[0 .. susp_cap), counted in *d_susp_count (zeroed by the caller; it may exceed
+// susp_cap: the caller grows the list and scans again).
+hipError_t short_sub_launch(const ShortSubDevice &d, const uint8_t *d_text, const uint32_t *d_packed, int64_t n, int64_t begin, int64_t end,
+                            pm_hit *d_out, unsigned long long *d_counter, uint64_t cap, uint64_t *d_susp, unsigned long long *d_susp_count,
+                            uint64_t susp_cap, hipStream_t st);
 
 // ---- seed extension DP on the GPU (pm_extend.hip) ---------------------------------------------
 hipError_t extend_seeds(const uint8_t *d_text, int64_t n, const pm_hit *d_seeds, size_t nseeds,

@@ -44,6 +44,7 @@
 // direct table could not settle, and did the rank / address / compare work branch-free for all windows.
 #include "pm_internal.h"
 #include "pm_pair.h"
+#include "pm_verify.h"
 #include "pm_workmap.h"
 
 #include <algorithm>
@@ -133,15 +134,6 @@ __device__ __forceinline__ uint32_t bits_at(uint32_t p2, uint32_t p1, uint32_t c
   else if constexpr (O == 32) return p1;
   else if constexpr (O < 64) return __builtin_amdgcn_alignbit(cur, p1, O - 32);
   else return cur >> (O - 64);
-}
-
-// substitutions between two strings of 2-bit symbols
-__device__ __host__ __forceinline__ int sym_distance(uint32_t x) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  return __popc((x | (x >> 1)) & 0x55555555u);
-#else
-  return __builtin_popcount((x | (x >> 1)) & 0x55555555u);
-#endif
 }
 
 // The 20-bit key of field pair (a, b) of a 40-bit window W and the other 20 bits (fields c < d).
@@ -309,100 +301,7 @@ __device__ __forceinline__ void edit_variant(int v, F &&f) {
 }
 __device__ __host__ __forceinline__ int edit_variant_table(int var) { return var == 0 ? 0 : (var <= 3 ? 1 : (var <= 8 ? 2 : (var == 9 ? 3 : (var <= 12 ? 4 : 5)))); }
 
-// Exact part of the verify (second kernel): (window ending at p, pattern pi) agree on this combo's key
-// and are within k substitutions on the rest of the packed window; count mismatches on the raw stream
-// codes over the whole pattern (N = mismatch, EOS = reject) and report -- once: only through the first
-// combo of the plan whose two fields are clean.
-// Returns whether (p, pi) is a candidate this combo reports; *hh is then its record.
-__device__ __forceinline__ bool pair_verify(const PairArgs &a, int combo, int64_t p, uint32_t pi, pm_hit *hh) {
-  const int L = a.pat_len[pi];
-  const int64_t start = p + 1 - L;
-  if (start < 0) return false;
-  // all 32 pattern codes and the 32 stream bytes from `start` at once (every load independent of the
-  // others: this kernel is a chain of dependent loads as it is), per-byte verdicts by SWAR
-  const uint4 *pcv = reinterpret_cast<const uint4 *>(a.pat_codes + (size_t)pi * 32);
-  const uint4 pc0 = pcv[0], pc1 = pcv[1];
-  uint32_t tw[8];
-  if (start + 32 <= a.n) {
-    uint4 t0, t1;
-    __builtin_memcpy(&t0, a.text + start, 16);
-    __builtin_memcpy(&t1, a.text + start + 16, 16);
-    tw[0] = t0.x; tw[1] = t0.y; tw[2] = t0.z; tw[3] = t0.w; tw[4] = t1.x; tw[5] = t1.y; tw[6] = t1.z; tw[7] = t1.w;
-  } else {                                            // the last bytes of the stream
-#pragma unroll
-    for (int d = 0; d < 8; ++d) {
-      tw[d] = 0;
-      for (int b = 0; b < 4; ++b) { const int64_t q = start + 4 * d + b; if (q < a.n) tw[d] |= (uint32_t)a.text[q] << (8 * b); }
-    }
-  }
-  const uint32_t pcw[8] = {pc0.x, pc0.y, pc0.z, pc0.w, pc1.x, pc1.y, pc1.z, pc1.w};
-  const uint32_t eb = (uint32_t)(a.eos_code & 0xff) * 0x01010101u;
-  uint32_t mism = 0, eos = 0;                         // bit i: stream byte i differs from the pattern / is EOS
-#pragma unroll
-  for (int d = 0; d < 8; ++d) {
-    const uint32_t x = tw[d] ^ pcw[d], z = tw[d] ^ eb;
-    const uint32_t y = (x | ((x & 0x7f7f7f7fu) + 0x7f7f7f7fu)) & 0x80808080u;
-    const uint32_t e = ~(z | ((z & 0x7f7f7f7fu) + 0x7f7f7f7fu)) & 0x80808080u;
-    mism |= (((y >> 7) & 1u) | ((y >> 14) & 2u) | ((y >> 21) & 4u) | ((y >> 28) & 8u)) << (4 * d);
-    eos |= (((e >> 7) & 1u) | ((e >> 14) & 2u) | ((e >> 21) & 4u) | ((e >> 28) & 8u)) << (4 * d);
-  }
-  const uint32_t lenmask = L >= 32 ? 0xffffffffu : ((1u << L) - 1u);
-  mism &= lenmask;
-  if (a.eos_code >= 0 && (eos & lenmask)) return false;   // EOS inside the window: never a candidate
-  int ham = __popc(mism);                             // N (or any other code) = mismatch
-  if (ham > a.k) return false;
-  // exact-base constraints (pattern_alignment.cc:320-323: a substitution inside an exact zone is a
-  // constraint violation, the verify fails)
-  if (mism & a.pat_zone[pi]) {
-    if (a.viol_level <= 0) return false;
-    ham = a.viol_level;
-  }
-  const uint32_t tail = mism >> (L - 20);             // the 20 bases the plan looks at
-  uint32_t dirty = 0;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) if ((tail >> (5 * j)) & 31u) dirty |= 1u << j;
-  int first = -1;
-  for (int c = 0; c < a.ncombos && first < 0; ++c)
-    if (!((dirty >> a.fa[c]) & 1u) && !((dirty >> a.fb[c]) & 1u)) first = c;
-  if (first != combo) return false;
-  const int half = L / 2;
-  const bool left_clean = (mism & ((1u << half) - 1u)) == 0, right_clean = (mism >> half) == 0;
-  hh->end = p + 1; hh->pid = a.pat_id[pi]; hh->k = (uint8_t)ham;
-  hh->aux[0] = (uint8_t)((left_clean ? 1 : 0) | (right_clean ? 2 : 0)); hh->aux[1] = hh->aux[2] = 0;
-  return true;
-}
-
-// Output of the verify kernel.  The record list's end is ONE counter for the whole grid and same-address atomics
-// serialise (~10 ns each under load), so a workgroup collects its records in LDS and appends them in batches: one atomic
-// per ~1500 records instead of one per wave and call (hit-dense streams -- tandem repeats, 0.4 candidates per base --
-// spent most of this kernel waiting for that counter).  Called by whichever lanes of a wave are executing together.
-constexpr int VSTAGE = 2048;                                        // records a workgroup stages (32 KiB)
-struct VerifyStage { pm_hit *rec; uint32_t *fill, *valid; };        // LDS: records, reserved slots, first slot that was refused
-
-__device__ __forceinline__ void pair_emit(const PairArgs &a, const VerifyStage &vs, bool ok, const pm_hit &hh) {
-  const unsigned long long bal = __ballot(ok);
-  if (bal == 0) return;
-  const int leader = __ffsll((long long)bal) - 1;
-  const int lane = threadIdx.x & 63;
-  const uint32_t cnt = (uint32_t)__popcll(bal), mine = (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
-  uint32_t pos = 0;
-  if (lane == leader) pos = atomicAdd(vs.fill, cnt);
-  pos = __builtin_amdgcn_readlane(pos, leader);
-  if (pos + cnt <= (uint32_t)VSTAGE) {
-    if (ok) vs.rec[pos + mine] = hh;
-    return;
-  }
-  // no room (a workgroup whose suspects give thousands of records in one trip): this batch goes straight to the list;
-  // every later reservation of the trip is refused as well (fill stays above VSTAGE), the flush takes the slots in front
-  if (lane == leader) atomicMin(vs.valid, pos);
-  unsigned long long base = 0;
-  if (lane == leader) base = atomicAdd(a.counter, (unsigned long long)cnt);
-  const uint32_t blo = __builtin_amdgcn_readlane((uint32_t)base, leader), bhi = __builtin_amdgcn_readlane((uint32_t)(base >> 32), leader);
-  if (ok) {
-    const unsigned long long o = (((unsigned long long)bhi << 32) | blo) + (unsigned long long)mine;
-    if (o < a.cap) a.out[o] = hh;
-  }
-}
+// pair_verify<5> (the exact part of the verify), pair_emit and its LDS stage: pm_verify.h, shared with pm_short.hip
 
 // A suspect: a window whose slot says "within k on the other fields" for the key's first / second /
 // third pattern (what & 1, 2, 4), that the key has more than three (WHAT_REST: walk the rest of the
@@ -421,13 +320,13 @@ __device__ __forceinline__ void pair_resolve(const PairArgs &a, const VerifyStag
     pair_emit(a, vs, extra, hh);
   };
   for (uint32_t j = 0; j < 3; ++j)
-    take(((what >> j) & 1u) && t0 + j < t1 && pair_verify(a, combo, p, ord[t0 + j], &hh));   // (free slot fields repeat the first pattern)
+    take(((what >> j) & 1u) && t0 + j < t1 && pair_verify<5>(a, combo, p, ord[t0 + j], &hh));   // (free slot fields repeat the first pattern)
   if (what & (WHAT_REST | WHAT_ALL)) {
     // the rest of the key's run: its patterns' other fields lie next to each other (one or two cache lines for a run of
     // twenty; ord[] -> pat40[] was two dependent random loads per pattern -- keys shared by many primers are what a
     // skewed stream with primers cut from it is made of)
     for (uint32_t t = t0 + ((what & WHAT_ALL) ? 0u : 3u); t < t1; ++t)
-      take(sym_distance(ol[t] ^ wo) <= a.k && pair_verify(a, combo, p, ord[t], &hh));
+      take(sym_distance(ol[t] ^ wo) <= a.k && pair_verify<5>(a, combo, p, ord[t], &hh));
   }
 }
 

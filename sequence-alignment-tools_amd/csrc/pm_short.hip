@@ -1,4 +1,5 @@
-// pm_short.hip -- first stage of the edit-distance plan for patterns of 16..19 characters.
+// pm_short.hip -- patterns of 16..19 characters: the first stage of the edit-distance plan and, further
+// down, the substitution class beside the pair plan (pm_short_sub_scan).
 //
 // The edit plan of pm_seed.hip / pm_pair.hip seeds on the last 20 pattern bases, so a primer of 16..19 bases used to go
 // to the bit-parallel residue kernel.  Here the last SIXTEEN bases are four fields of four -- the four bytes of the 2-bit
@@ -20,6 +21,7 @@
 // pattern's is an edit of the alignment, and both the cover and the q-gram count argue about the bases no edit touches.
 #include "pm_internal.h"
 #include "pm_seed.h"
+#include "pm_verify.h"
 
 #include <algorithm>
 #include <cstring>
@@ -219,6 +221,202 @@ __global__ __launch_bounds__(SHORT_THREADS) void pm_short_edit_scan(ShortArgs a)
   for (int u = lane; u < ob_left; u += 64) if (ob_next + u < a.seed_cap) a.seed_out[ob_next + u] = ~0ull;
 }
 
+// ---- substitutions only: patterns of 16..19 characters beside a main class on the pair plan ------------
+//
+//   pm_short_sub_scan    <= 2 substitutions leave two of the four fields clean and in place: no displacement, so a test is a
+//                        field pair -- the pair plan's combos, six at k = 2, (0,1) and (2,3) at k = 1 -- and a window is the
+//                        16 bases that end at p.  Key hits go through the wave's queue as above; a key's run holds 8-byte
+//                        entries {pattern index, the pattern's last 16 bases}, so ONE read behind the offset table settles a
+//                        key hit: XOR + popcount against the window (the key fields are equal, what differs lies in the
+//                        other two).  What is within k leaves as an 8-byte suspect "combo, pattern, position".
+//   pm_short_sub_verify  pair_verify<4> of pm_verify.h per suspect -- the pair plan's exact stage on fields of four bases:
+//                        raw stream bytes (N = mismatch, EOS = reject), exact zones, "reported once, by the first clean field
+//                        pair of the plan", clean-half flags -- into the record list of the main class.
+//
+// As above, N, end-of-sequence and positions outside the stream pack to arbitrary bases: such a window can only gain
+// suspects.  It cannot lose a candidate either: a text character that is not the pattern's is one of its <= k mismatches,
+// and the two fields no mismatch touches are clean on the packed bases as well.
+constexpr int SUB_OUT_BLOCK = 64;                   // suspect slots a wave reserves per atomic
+constexpr int SUB_VERIFY_BLOCKS = 4096;
+constexpr uint64_t SUB_POS_MASK = 0xffffffffffull;  // suspect: combo << 61 | class index of the pattern (21 bits) << 40 | position
+constexpr size_t SUB_MAX_PATTERNS = (size_t)1 << 21;
+
+
+struct SubArgs {
+  const uint8_t *text;
+  int64_t n;
+  const uint32_t *packed;               // the stream, 2 bits per base, 16 bases per dword
+  int64_t npacked;
+  int64_t p_lo, p_hi;                   // window positions lo <= p < hi (hit ends p + 1)
+  int64_t chunk0, chunk_len;            // as ShortArgs
+  int k, eos_code, ncombos, viol_level;
+  int fa[SUB_MAX_COMBOS], fb[SUB_MAX_COMBOS];
+  const uint32_t *bitmap;               // the tile's: [combo][SHORT_BM_WORDS]
+  const uint32_t *rows;                 //             [combo][SHORT_ROWS]: first entry of the key's run in runs
+  const uint2 *runs;                    //             {pattern index inside the tile, its last 16 bases} by combo and key
+  uint32_t tile_base;
+  const uint8_t *pat_len;               // the class's (pair_verify)
+  const uint32_t *pat_id;
+  const uint8_t *pat_codes;
+  const uint32_t *pat_zone;
+  uint64_t *susp;
+  unsigned long long *susp_count;
+  unsigned long long susp_cap;
+  pm_hit *out;
+  unsigned long long *counter;
+  unsigned long long cap;
+};
+
+template <int K>
+__global__ __launch_bounds__(SHORT_THREADS) void pm_short_sub_scan(SubArgs a) {
+  constexpr int NC = sub_ncombos(K);
+  __shared__ uint32_t s_bm[NC * SHORT_BM_WORDS];
+  __shared__ uint16_t s_q[SHORT_WAVES][SHORT_QCAP];
+  {
+    const uint4 *src = reinterpret_cast<const uint4 *>(a.bitmap);
+    uint4 *dst = reinterpret_cast<uint4 *>(s_bm);
+    for (int i = threadIdx.x; i < NC * SHORT_BM_WORDS / 4; i += SHORT_THREADS) dst[i] = src[i];
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int64_t sub = a.chunk_len / SHORT_WAVES;
+  const int64_t ws = (a.chunk0 + (int64_t)blockIdx.x) * a.chunk_len + (int64_t)wave * sub;   // a multiple of 1024
+  const int64_t lo = ws > a.p_lo ? ws : a.p_lo, hi = ws + sub < a.p_hi ? ws + sub : a.p_hi;
+  if (lo >= hi) return;
+  uint16_t *q = s_q[wave];
+  int qn = 0;                                                       // wave-uniform: key hits queued
+  unsigned long long ob_next = 0;                                   // wave-uniform: next free slot of the wave's reserved run of the suspect list
+  int ob_left = 0;
+  uint32_t w1 = 0, w2 = 0;                                          // this lane's stream words of the block (sub_window)
+
+  // every queued key hit of block bb: the key's run of {pattern, last 16 bases}, the other two fields, suspects
+  auto drain = [&](int64_t bb) __attribute__((always_inline)) {
+    for (int base = 0; base < qn; base += 64) {
+      const bool valid = base + lane < qn;
+      const uint32_t e = valid ? (uint32_t)q[base + lane] : 0u;
+      const uint32_t win = (e >> 4) & 15u, c = e & 15u, from = e >> 8;
+      const uint32_t W = sub_window((uint32_t)__shfl((int)w1, (int)from), (uint32_t)__shfl((int)w2, (int)from), win);
+      // the combo's fields, a nibble each: (0,1) (0,2) (0,3) (1,2) (1,3) (2,3) / (0,1) (2,3)
+      const int fa = (int)(((K == 2 ? 0x211000u : 0x20u) >> (4u * c)) & 15u), fb = (int)(((K == 2 ? 0x332321u : 0x31u) >> (4u * c)) & 15u);
+      const uint32_t row = c * (uint32_t)SHORT_ROWS + sub_key(W, fa, fb);
+      uint32_t cur = 0, stop = 0;
+      if (valid) { cur = a.rows[row]; stop = a.rows[row + 1]; }
+      const int64_t p = bb + 16 * (int64_t)from + (int64_t)win;
+      while (__ballot(cur < stop)) {
+        bool pass = false;
+        uint32_t pi = 0;
+        if (cur < stop) {
+          const uint2 r = a.runs[cur];
+          pi = r.x;
+          pass = sub_others_within(W, r.y, K);
+          ++cur;
+        }
+        const unsigned long long bal = __ballot(pass);
+        if (bal == 0) continue;
+        const int n = __popcll(bal);
+        if (n > ob_left) {                                           // a fresh run of slots; what is left of the old one is marked unused
+          for (int u = lane; u < ob_left; u += 64) if (ob_next + u < a.susp_cap) a.susp[ob_next + u] = ~0ull;
+          unsigned long long got = 0;
+          if (lane == 0) got = atomicAdd(a.susp_count, (unsigned long long)SUB_OUT_BLOCK);
+          ob_next = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(got >> 32)) << 32) | __builtin_amdgcn_readfirstlane((uint32_t)got);
+          ob_left = SUB_OUT_BLOCK;
+        }
+        if (pass) {
+          const unsigned long long slot = ob_next + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0));
+          if (slot < a.susp_cap) a.susp[slot] = ((uint64_t)c << 61) | ((uint64_t)(a.tile_base + pi) << 40) | ((uint64_t)p & SUB_POS_MASK);
+        }
+        ob_next += n; ob_left -= n;
+      }
+    }
+    qn = 0;
+  };
+
+  for (int64_t bb = ws + (lo - ws) / 1024 * 1024; bb < hi; bb += 1024) {
+    const int64_t pbase = bb + 16 * lane;                            // this lane's windows: p = pbase .. pbase + 15
+    uint32_t own = 0xffffu;
+    {
+      const int64_t l = lo - pbase, h = hi - pbase;
+      const uint32_t lb = l <= 0 ? 0u : (l >= 16 ? 16u : (uint32_t)l), hb = h <= 0 ? 0u : (h >= 16 ? 16u : (uint32_t)h);
+      own = ((1u << hb) - 1u) & ~((1u << lb) - 1u);
+    }
+    w1 = 0; w2 = 0;
+    if (own) { w1 = load_words(a.packed, a.npacked, pbase - 16); w2 = load_words(a.packed, a.npacked, pbase); }   // (lanes outside the range read nothing)
+    // two combos per mask: bit j of the low / high half = window j has the key of combo 2r / 2r + 1 in that combo's bitmap
+    uint32_t m[NC / 2];
+#pragma unroll
+    for (int r = 0; r < NC / 2; ++r) m[r] = 0;
+    static_each(std::make_integer_sequence<int, 16>(), [&](auto J) __attribute__((always_inline)) {
+      constexpr int j = decltype(J)::value;
+      const uint32_t W = sub_window(w1, w2, j);
+      static_each(std::make_integer_sequence<int, NC>(), [&](auto C) __attribute__((always_inline)) {
+        constexpr int c = decltype(C)::value;
+        const uint32_t key = sub_key(W, sub_fa(K, c), sub_fb(K, c));
+        m[c / 2] |= ((s_bm[c * SHORT_BM_WORDS + (key >> 5)] >> (key & 31u)) & 1u) << (16 * (c & 1) + j);
+      });
+    });
+    static_each(std::make_integer_sequence<int, NC / 2>(), [&](auto R) __attribute__((always_inline)) {
+      constexpr int r = decltype(R)::value;
+      uint32_t mm = m[r] & (own | (own << 16));
+      const int cnt = __popc(mm);
+      if (__ballot(cnt != 0)) {
+        int x = cnt;                                                 // inclusive prefix sum over the wave
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(x, o); if (lane >= o) x += y; }
+        const int total = __shfl(x, 63);
+        if (qn + total > SHORT_QCAP) drain(bb);                      // (total <= SHORT_QCAP)
+        int at = qn + x - cnt;
+        while (mm) {
+          const int b = __builtin_ctz(mm);
+          mm &= mm - 1u;
+          q[at++] = (uint16_t)(((uint32_t)lane << 8) | ((uint32_t)(b & 15) << 4) | (uint32_t)(2 * r + (b >> 4)));
+        }
+        qn += total;
+      }
+    });
+    if (qn) drain(bb);
+  }
+  for (int u = lane; u < ob_left; u += 64) if (ob_next + u < a.susp_cap) a.susp[ob_next + u] = ~0ull;
+}
+
+// The scan's suspects, one per thread: the pair plan's exact stage with fields of four bases.  Records leave through the
+// workgroup's LDS stage (pair_emit), as in pm_pair_verify.
+__global__ __launch_bounds__(256) void pm_short_sub_verify(SubArgs a) {
+  __shared__ pm_hit s_rec[VSTAGE];
+  __shared__ unsigned long long s_base;
+  __shared__ uint32_t s_fill, s_valid, s_full;
+  const VerifyStage vs = {s_rec, &s_fill, &s_valid};
+  unsigned long long n = *a.susp_count;
+  if (n > a.susp_cap) n = a.susp_cap;
+  const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
+  if (threadIdx.x == 0) { s_fill = 0; s_valid = (uint32_t)VSTAGE; }
+  __syncthreads();
+  auto flush = [&]() __attribute__((always_inline)) {               // the staged records join the list: one atomic (block-uniform call)
+    const uint32_t cnt = min(s_fill, s_valid);
+    __syncthreads();
+    if (threadIdx.x == 0) { s_base = cnt ? atomicAdd(a.counter, (unsigned long long)cnt) : 0ull; s_fill = 0; s_valid = (uint32_t)VSTAGE; }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < cnt; i += blockDim.x) if (s_base + i < a.cap) a.out[s_base + i] = s_rec[i];
+    __syncthreads();
+  };
+  for (unsigned long long base = (unsigned long long)blockIdx.x * blockDim.x; base < n; base += stride) {   // block-uniform trip count
+    const unsigned long long i = base + threadIdx.x;
+    pm_hit hh;
+    bool have = false;
+    if (i < n) {
+      const uint64_t r = a.susp[i];
+      if (r != ~0ull)                                                 // (a slot its wave reserved and did not need)
+        have = pair_verify<4>(a, (int)(r >> 61), (int64_t)(r & SUB_POS_MASK), (uint32_t)(r >> 40) & (uint32_t)(SUB_MAX_PATTERNS - 1), &hh);
+    }
+    pair_emit(a, vs, have, hh);                                       // (every lane is here)
+    __syncthreads();
+    if (threadIdx.x == 0) s_full = s_fill > (uint32_t)(VSTAGE - 512);
+    __syncthreads();
+    if (s_full) flush();
+  }
+  flush();
+}
+
 }  // namespace
 
 std::string short_build(const std::vector<Pattern> &pats, const std::vector<uint32_t> &ids, const Alphabet &alpha, int k, int eos_code,
@@ -333,6 +531,132 @@ hipError_t short_launch(const ShortDevice &d, const uint8_t *d_text, const uint3
     if (e != hipSuccess) return e;
   }
   return edits_verify_launch(d.records, d.k, d.maxlen, d.ascii, d.eos_code, d_text, n, begin, end, d_seeds, d_seed_count, seed_cap, d_out, d_counter, cap, st);
+}
+
+// ---- the substitution class: tables, launch ------------------------------------------------------------------------
+
+std::string short_sub_build(const std::vector<Pattern> &pats, const std::vector<uint32_t> &ids, const Alphabet &alpha, int k, int eos_code,
+                            size_t tile, ShortSubTables *out) {
+  ShortSubTables &t = *out;
+  t = ShortSubTables();
+  if (k < 1 || k > 2) return "pm_short_sub_scan is built for k = 1 and k = 2";
+  const bool norm = alpha.nch['A'] == 0 && alpha.nch['C'] == 1 && alpha.nch['G'] == 2 && alpha.nch['T'] == 3;
+  const bool ascii = alpha.size == 256 && alpha.nch['A'] == 'A' && alpha.nch['C'] == 'C' && alpha.nch['G'] == 'G' && alpha.nch['T'] == 'T';
+  if (!norm && !ascii) return "stream alphabet is neither A,C,G,T-normalized nor raw ASCII";
+  t.k = k; t.ascii = ascii && !norm; t.eos_code = eos_code >= 0 && eos_code < 256 ? eos_code : -1;
+  t.ncombos = sub_ncombos(k);
+  for (int c = 0; c < t.ncombos; ++c) { t.fa[c] = sub_fa(k, c); t.fb[c] = sub_fb(k, c); }
+  auto base2 = [&](unsigned char ch) -> int {                       // the stream's packing (pm_seed.hip pack4)
+    switch (ch) { case 'A': return 0; case 'C': return 1; case 'G': return t.ascii ? 3 : 2; case 'T': return t.ascii ? 2 : 3; }
+    return -1;
+  };
+  const size_t np = pats.size();
+  if (np >= SUB_MAX_PATTERNS) return "too many patterns of 16..19 characters (21-bit pattern index)";
+  t.pat_len.resize(np); t.pat_id.resize(np); t.pat_codes.assign(np * 32, 0); t.pat_zone.assign(np, 0);
+  std::vector<uint32_t> p16(np);
+  for (size_t j = 0; j < np; ++j) {
+    const std::string &s = pats[j].s;
+    const int L = (int)s.size();
+    if (L < 16 || L > 19) return "pm_short_sub_scan takes patterns of 16..19 characters";
+    for (int i = 0; i < L; ++i) {
+      if (base2((unsigned char)s[i]) < 0) return "pattern with characters other than A,C,G,T";
+      t.pat_codes[j * 32 + i] = (uint8_t)alpha.nch[(unsigned char)s[i]];
+    }
+    t.maxlen = std::max(t.maxlen, L);
+    uint32_t w = 0;
+    for (int i = 0; i < 16; ++i) w |= (uint32_t)base2((unsigned char)s[L - 16 + i]) << (2 * i);
+    p16[j] = w;
+    t.pat_len[j] = (uint8_t)L; t.pat_id[j] = ids[j];
+    const int es = std::max(0, std::min(L, pats[j].esb)), ee = std::max(0, std::min(L, pats[j].eeb));
+    uint32_t z = 0;
+    for (int i = 0; i < L; ++i) if (i < es || i >= L - ee) z |= 1u << i;
+    t.pat_zone[j] = z;
+  }
+  if (tile == 0) tile = SHORT_TILE_DEFAULT;
+  const size_t ntile = np ? (np + tile - 1) / tile : 0, per = ntile ? (np + ntile - 1) / ntile : 0;
+  t.tiles.resize(ntile);
+  for (size_t ti = 0; ti < ntile; ++ti) {
+    ShortSubTables::Tile &tt = t.tiles[ti];
+    const size_t lo = ti * per, hi = std::min(np, lo + per), m = hi - lo;
+    tt.base = (uint32_t)lo;
+    tt.bitmap.assign((size_t)t.ncombos * SHORT_BM_WORDS, 0);
+    tt.rows.assign((size_t)t.ncombos * SHORT_ROWS, 0);
+    tt.runs.assign((size_t)t.ncombos * m, 0);
+    for (int c = 0; c < t.ncombos; ++c) {
+      uint32_t *rows = &tt.rows[(size_t)c * SHORT_ROWS];
+      for (size_t j = 0; j < m; ++j) {                               // counting sort by key: rows[key] = first entry of the key's run
+        const uint32_t key = sub_key(p16[lo + j], t.fa[c], t.fb[c]);
+        tt.bitmap[(size_t)c * SHORT_BM_WORDS + (key >> 5)] |= 1u << (key & 31u);
+        ++rows[key + 1];
+      }
+      rows[0] = (uint32_t)((size_t)c * m);
+      for (int key = 0; key < 65536; ++key) rows[key + 1] += rows[key];
+      std::vector<uint32_t> fill(rows, rows + 65536);
+      for (size_t j = 0; j < m; ++j) tt.runs[fill[sub_key(p16[lo + j], t.fa[c], t.fb[c])]++] = (uint64_t)j | ((uint64_t)p16[lo + j] << 32);
+    }
+  }
+  return "";
+}
+
+hipError_t short_sub_upload(const ShortSubTables &t, ShortSubDevice *d, hipStream_t st) {
+  short_sub_free(d);
+  d->k = t.k; d->maxlen = t.maxlen; d->ascii = t.ascii; d->eos_code = t.eos_code; d->ncombos = t.ncombos; d->npat = t.pat_len.size();
+  for (int c = 0; c < SUB_MAX_COMBOS; ++c) { d->fa[c] = t.fa[c]; d->fb[c] = t.fb[c]; }
+  auto up = [&](const void *src, size_t bytes, void **dst) -> hipError_t {
+    hipError_t e = hipMalloc(dst, bytes ? bytes : 16);
+    if (e != hipSuccess) return e;
+    return bytes ? hipMemcpyAsync(*dst, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
+  };
+  hipError_t e;
+  if ((e = up(t.pat_len.data(), t.pat_len.size(), (void **)&d->pat_len)) != hipSuccess) return e;
+  if ((e = up(t.pat_id.data(), t.pat_id.size() * 4, (void **)&d->pat_id)) != hipSuccess) return e;
+  if ((e = up(t.pat_codes.data(), t.pat_codes.size(), (void **)&d->pat_codes)) != hipSuccess) return e;
+  if ((e = up(t.pat_zone.data(), t.pat_zone.size() * 4, (void **)&d->pat_zone)) != hipSuccess) return e;
+  d->tiles.resize(t.tiles.size());
+  for (size_t i = 0; i < t.tiles.size(); ++i) {
+    const ShortSubTables::Tile &s = t.tiles[i];
+    ShortSubDevice::Tile &x = d->tiles[i];
+    x.base = s.base;
+    if ((e = up(s.bitmap.data(), s.bitmap.size() * 4, (void **)&x.bitmap)) != hipSuccess) return e;
+    if ((e = up(s.rows.data(), s.rows.size() * 4, (void **)&x.rows)) != hipSuccess) return e;
+    if ((e = up(s.runs.data(), s.runs.size() * 8, (void **)&x.runs)) != hipSuccess) return e;
+  }
+  return hipStreamSynchronize(st);                                   // (the host tables may go now)
+}
+
+void short_sub_free(ShortSubDevice *d) {
+  { void *ptrs[] = {d->pat_len, d->pat_id, d->pat_codes, d->pat_zone}; for (void *p : ptrs) if (p) (void)hipFree(p); }
+  for (ShortSubDevice::Tile &x : d->tiles) { void *ptrs[] = {x.bitmap, x.rows, x.runs}; for (void *p : ptrs) if (p) (void)hipFree(p); }
+  *d = ShortSubDevice();
+}
+
+hipError_t short_sub_launch(const ShortSubDevice &d, const uint8_t *d_text, const uint32_t *d_packed, int64_t n, int64_t begin, int64_t end,
+                            pm_hit *d_out, unsigned long long *d_counter, uint64_t cap, uint64_t *d_susp, unsigned long long *d_susp_count,
+                            uint64_t susp_cap, hipStream_t st) {
+  if (!d_packed || !d_susp || !d_susp_count) return hipErrorInvalidValue;
+  if (end > n) end = n;
+  if (end <= begin || d.tiles.empty()) return hipSuccess;
+  // a hit that ends at e (begin < e <= end) is the window whose last base is p = e - 1
+  const int64_t seg_len = end - begin >= ((int64_t)1 << 24) ? (int64_t)1 << 18 : (int64_t)1 << 16;
+  const int64_t c_lo = begin / seg_len, c_hi = (end - 1) / seg_len;
+  const int nseg = (int)(c_hi - c_lo + 1);
+  SubArgs a;
+  memset(&a, 0, sizeof(a));
+  a.text = d_text; a.n = n; a.packed = d_packed; a.npacked = (n + 15) / 16; a.p_lo = begin; a.p_hi = end; a.chunk0 = c_lo; a.chunk_len = seg_len;
+  a.k = d.k; a.eos_code = d.eos_code; a.ncombos = d.ncombos; a.viol_level = d.viol_level;
+  for (int c = 0; c < SUB_MAX_COMBOS; ++c) { a.fa[c] = d.fa[c]; a.fb[c] = d.fb[c]; }
+  a.pat_len = d.pat_len; a.pat_id = d.pat_id; a.pat_codes = d.pat_codes; a.pat_zone = d.pat_zone;
+  a.susp = d_susp; a.susp_count = d_susp_count; a.susp_cap = susp_cap;
+  a.out = d_out; a.counter = d_counter; a.cap = cap;
+  for (const ShortSubDevice::Tile &x : d.tiles) {
+    a.bitmap = x.bitmap; a.rows = x.rows; a.runs = reinterpret_cast<const uint2 *>(x.runs); a.tile_base = x.base;
+    if (d.k == 2) hipLaunchKernelGGL(pm_short_sub_scan<2>, dim3(nseg), dim3(SHORT_THREADS), 0, st, a);
+    else hipLaunchKernelGGL(pm_short_sub_scan<1>, dim3(nseg), dim3(SHORT_THREADS), 0, st, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(pm_short_sub_verify, dim3(SUB_VERIFY_BLOCKS), dim3(256), 0, st, a);
+  return hipGetLastError();
 }
 
 }  // namespace pm

@@ -1,0 +1,156 @@
+// pm_verify.h -- the exact stage of the substitution plans, shared by pm_pair.hip (patterns of 20..32 characters: tail of
+// 20 bases, four fields of five) and pm_short.hip (patterns of 16..19 characters: tail of 16 bases, four fields of four),
+// and the window arithmetic of pm_short_sub_scan.  All but pair_emit compiles with a plain C++ compiler as well:
+// tests/test_short_sub_host.py checks it against a plain restatement.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+#include "../../include/pm_gpu.h"
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define PM_VFN __device__ __host__ __forceinline__
+#else                                                 // a plain C++ compiler: the host check (tests/test_short_sub_host.py)
+#define PM_VFN inline
+namespace pm { struct uint4 { uint32_t x, y, z, w; }; }
+#endif
+
+namespace pm {
+
+namespace {
+
+PM_VFN int pop32(uint32_t x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __popc(x);
+#else
+  return __builtin_popcount(x);
+#endif
+}
+
+// substitutions between two strings of 2-bit symbols
+PM_VFN int sym_distance(uint32_t x) { return pop32((x | (x >> 1)) & 0x55555555u); }
+
+// Exact part of the verify (second kernel): (window ending at p, pattern pi) agree on this combo's key
+// and are within k substitutions on the rest of the packed window; count mismatches on the raw stream
+// codes over the whole pattern (N = mismatch, EOS = reject) and report -- once: only through the first
+// combo of the plan whose two fields are clean.
+// FW = bases per field: the plan looks at the pattern's last 4 * FW bases.  Args: the kernel's argument block (text, n, k,
+// eos_code, ncombos, fa, fb, pat_len, pat_id, pat_codes, pat_zone, viol_level).
+// Returns whether (p, pi) is a candidate this combo reports; *hh is then its record.
+template <int FW, typename Args>
+PM_VFN bool pair_verify(const Args &a, int combo, int64_t p, uint32_t pi, pm_hit *hh) {
+  static_assert(FW == 4 || FW == 5, "fields of four or five bases");
+  const int L = a.pat_len[pi];
+  const int64_t start = p + 1 - L;
+  if (start < 0) return false;
+  // all 32 pattern codes and the 32 stream bytes from `start` at once (every load independent of the
+  // others: this kernel is a chain of dependent loads as it is), per-byte verdicts by SWAR
+  const uint4 *pcv = reinterpret_cast<const uint4 *>(a.pat_codes + (size_t)pi * 32);
+  const uint4 pc0 = pcv[0], pc1 = pcv[1];
+  uint32_t tw[8];
+  if (start + 32 <= a.n) {
+    uint4 t0, t1;
+    __builtin_memcpy(&t0, a.text + start, 16);
+    __builtin_memcpy(&t1, a.text + start + 16, 16);
+    tw[0] = t0.x; tw[1] = t0.y; tw[2] = t0.z; tw[3] = t0.w; tw[4] = t1.x; tw[5] = t1.y; tw[6] = t1.z; tw[7] = t1.w;
+  } else {                                            // the last bytes of the stream
+#pragma unroll
+    for (int d = 0; d < 8; ++d) {
+      tw[d] = 0;
+      for (int b = 0; b < 4; ++b) { const int64_t q = start + 4 * d + b; if (q < a.n) tw[d] |= (uint32_t)a.text[q] << (8 * b); }
+    }
+  }
+  const uint32_t pcw[8] = {pc0.x, pc0.y, pc0.z, pc0.w, pc1.x, pc1.y, pc1.z, pc1.w};
+  const uint32_t eb = (uint32_t)(a.eos_code & 0xff) * 0x01010101u;
+  uint32_t mism = 0, eos = 0;                         // bit i: stream byte i differs from the pattern / is EOS
+#pragma unroll
+  for (int d = 0; d < 8; ++d) {
+    const uint32_t x = tw[d] ^ pcw[d], z = tw[d] ^ eb;
+    const uint32_t y = (x | ((x & 0x7f7f7f7fu) + 0x7f7f7f7fu)) & 0x80808080u;
+    const uint32_t e = ~(z | ((z & 0x7f7f7f7fu) + 0x7f7f7f7fu)) & 0x80808080u;
+    mism |= (((y >> 7) & 1u) | ((y >> 14) & 2u) | ((y >> 21) & 4u) | ((y >> 28) & 8u)) << (4 * d);
+    eos |= (((e >> 7) & 1u) | ((e >> 14) & 2u) | ((e >> 21) & 4u) | ((e >> 28) & 8u)) << (4 * d);
+  }
+  const uint32_t lenmask = L >= 32 ? 0xffffffffu : ((1u << L) - 1u);
+  mism &= lenmask;
+  if (a.eos_code >= 0 && (eos & lenmask)) return false;   // EOS inside the window: never a candidate
+  int ham = pop32(mism);                              // N (or any other code) = mismatch
+  if (ham > a.k) return false;
+  // exact-base constraints (pattern_alignment.cc:320-323: a substitution inside an exact zone is a
+  // constraint violation, the verify fails)
+  if (mism & a.pat_zone[pi]) {
+    if (a.viol_level <= 0) return false;
+    ham = a.viol_level;
+  }
+  const uint32_t tail = mism >> (L - 4 * FW);         // the bases the plan looks at
+  uint32_t dirty = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) if ((tail >> (FW * j)) & ((1u << FW) - 1u)) dirty |= 1u << j;
+  int first = -1;
+  for (int c = 0; c < a.ncombos && first < 0; ++c)
+    if (!((dirty >> a.fa[c]) & 1u) && !((dirty >> a.fb[c]) & 1u)) first = c;
+  if (first != combo) return false;
+  const int half = L / 2;
+  const bool left_clean = (mism & ((1u << half) - 1u)) == 0, right_clean = (mism >> half) == 0;
+  hh->end = p + 1; hh->pid = a.pat_id[pi]; hh->k = (uint8_t)ham;
+  hh->aux[0] = (uint8_t)((left_clean ? 1 : 0) | (right_clean ? 2 : 0)); hh->aux[1] = hh->aux[2] = 0;
+  return true;
+}
+
+// ---- window arithmetic of pm_short_sub_scan (pm_short.hip) ----------------------------------------
+// The plan's field pairs in the order that decides who reports: all six at k = 2, (0,1) and (2,3) at k = 1 (one
+// substitution leaves the first two or the last two fields clean) -- the pair plan's.
+constexpr int sub_ncombos(int k) { return k == 2 ? 6 : 2; }
+constexpr int sub_fa(int k, int c) { return k == 2 ? (c < 3 ? 0 : (c < 5 ? 1 : 2)) : 2 * c; }
+constexpr int sub_fb(int k, int c) { return k == 2 ? (c < 3 ? c + 1 : (c < 5 ? c - 1 : 3)) : 2 * c + 1; }
+// A lane's 16 windows end at the positions pbase + j, pbase a multiple of 16: window j = the 16 bases up to pbase + j,
+// 2 bits each, from the stream words w1 (bases pbase - 16 .. pbase - 1) and w2 (pbase .. pbase + 15).
+PM_VFN uint32_t sub_window(uint32_t w1, uint32_t w2, uint32_t j) {
+  return (uint32_t)((((uint64_t)w2 << 32) | w1) >> (2u * (j + 1u)));
+}
+// 16-bit key of field pair (a, b): the fields are the window word's bytes
+PM_VFN uint32_t sub_key(uint32_t W, int a, int b) { return ((W >> (8 * a)) & 0xffu) | (((W >> (8 * b)) & 0xffu) << 8); }
+// <= k substitutions on the two fields outside the key, P = the pattern's last 16 bases: the key fields of W and P are
+// equal (the run was found through the key), so the distance of the whole words is the distance of the other two fields
+PM_VFN bool sub_others_within(uint32_t W, uint32_t P, int k) { return sym_distance(W ^ P) <= k; }
+
+#if defined(__HIPCC__)
+// Output of the verify kernels.  The record list's end is ONE counter for the whole grid and same-address atomics
+// serialise (~10 ns each under load), so a workgroup collects its records in LDS and appends them in batches: one atomic
+// per ~1500 records instead of one per wave and call (hit-dense streams -- tandem repeats, 0.4 candidates per base --
+// spent most of this kernel waiting for that counter).  Called by whichever lanes of a wave are executing together.
+// Args: out, counter, cap.
+constexpr int VSTAGE = 2048;                                        // records a workgroup stages (32 KiB)
+struct VerifyStage { pm_hit *rec; uint32_t *fill, *valid; };        // LDS: records, reserved slots, first slot that was refused
+
+template <typename Args>
+__device__ __forceinline__ void pair_emit(const Args &a, const VerifyStage &vs, bool ok, const pm_hit &hh) {
+  const unsigned long long bal = __ballot(ok);
+  if (bal == 0) return;
+  const int leader = __ffsll((long long)bal) - 1;
+  const int lane = threadIdx.x & 63;
+  const uint32_t cnt = (uint32_t)__popcll(bal), mine = (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+  uint32_t pos = 0;
+  if (lane == leader) pos = atomicAdd(vs.fill, cnt);
+  pos = __builtin_amdgcn_readlane(pos, leader);
+  if (pos + cnt <= (uint32_t)VSTAGE) {
+    if (ok) vs.rec[pos + mine] = hh;
+    return;
+  }
+  // no room (a workgroup whose suspects give thousands of records in one trip): this batch goes straight to the list;
+  // every later reservation of the trip is refused as well (fill stays above VSTAGE), the flush takes the slots in front
+  if (lane == leader) atomicMin(vs.valid, pos);
+  unsigned long long base = 0;
+  if (lane == leader) base = atomicAdd(a.counter, (unsigned long long)cnt);
+  const uint32_t blo = __builtin_amdgcn_readlane((uint32_t)base, leader), bhi = __builtin_amdgcn_readlane((uint32_t)(base >> 32), leader);
+  if (ok) {
+    const unsigned long long o = (((unsigned long long)bhi << 32) | blo) + (unsigned long long)mine;
+    if (o < a.cap) a.out[o] = hh;
+  }
+}
+#endif
+
+}  // namespace
+
+}  // namespace pm
