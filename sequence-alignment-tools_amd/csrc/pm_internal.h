@@ -190,14 +190,19 @@ hipError_t tally_device(const AlignDevice &a, uint64_t *d_keys, uint64_t *d_keys
 constexpr int SHORT_NTESTS = 14;
 constexpr size_t SHORT_TILE_DEFAULT = 32768;
 
+// A tile's key index as both classes of 16..19 characters build it (pm_short_tables.h) and as it lies on the device
+struct ShortTileIndex {
+  uint32_t base = 0;               // class index of the tile's first pattern
+  std::vector<uint32_t> bitmap;    // [field pair][2048]: bit = 16-bit key of some pattern
+  std::vector<uint32_t> rows;      // [field pair][65537]: first entry of the key's run in runs
+};
+struct ShortTileDevice { uint32_t base = 0; uint32_t *bitmap = nullptr, *rows = nullptr; void *runs = nullptr; uint32_t *pat16 = nullptr; };
+
 struct ShortTables {               // host-built, then uploaded
   int k = 0, maxlen = 0, eos_code = -1;
   bool ascii = false;
   std::vector<uint8_t> records;    // 32-byte automaton record per pattern of the class (pm_seed.h edit_record_fill)
-  struct Tile {
-    uint32_t base = 0;             // class index of the tile's first pattern
-    std::vector<uint32_t> bitmap;  // [field pair][2048]: bit = 16-bit key of some pattern
-    std::vector<uint32_t> rows;    // [field pair][65537]: first entry of the key's run in runs
+  struct Tile : ShortTileIndex {
     std::vector<uint32_t> runs;    // [field pair][patterns of the tile]: pattern indices (inside the tile) by key
     std::vector<uint32_t> pat16;   // last 16 bases of every pattern, 2 bits each
   };
@@ -209,8 +214,7 @@ struct ShortDevice {
   bool ascii = false;
   size_t npat = 0;
   uint8_t *records = nullptr;
-  struct Tile { uint32_t base = 0; uint32_t *bitmap = nullptr, *rows = nullptr, *runs = nullptr, *pat16 = nullptr; };
-  std::vector<Tile> tiles;
+  std::vector<ShortTileDevice> tiles;
 };
 
 // Build the tables of the class (`tile` = patterns per tile, 0: SHORT_TILE_DEFAULT).  Returns "" or an error message.
@@ -243,10 +247,7 @@ struct ShortSubTables {            // host-built, then uploaded
   std::vector<uint32_t> pat_id;
   std::vector<uint8_t> pat_codes;  // 32 stream codes per pattern
   std::vector<uint32_t> pat_zone;  // bit i: pattern character i lies in an exact zone
-  struct Tile {
-    uint32_t base = 0;             // class index of the tile's first pattern
-    std::vector<uint32_t> bitmap;  // [combo][2048]: bit = 16-bit key of some pattern
-    std::vector<uint32_t> rows;    // [combo][65537]: first entry of the key's run in runs
+  struct Tile : ShortTileIndex {
     std::vector<uint64_t> runs;    // [combo][patterns of the tile] by key: pattern index inside the tile | last 16 bases << 32
   };
   std::vector<Tile> tiles;
@@ -259,8 +260,7 @@ struct ShortSubDevice {
   size_t npat = 0;
   uint8_t *pat_len = nullptr, *pat_codes = nullptr;
   uint32_t *pat_id = nullptr, *pat_zone = nullptr;
-  struct Tile { uint32_t base = 0; uint32_t *bitmap = nullptr, *rows = nullptr; uint64_t *runs = nullptr; };
-  std::vector<Tile> tiles;
+  std::vector<ShortTileDevice> tiles;            // (pat16 unused: the run entries hold the bases)
   int viol_level = 0;              // as PairDevice::viol_level (set by the caller after short_sub_upload)
 };
 

@@ -42,6 +42,7 @@
 // ~2 cycles and CU, 269 G lines/s for the chip, whatever the bytes asked for: 3.1e9 lines = 0.68 of it.
 // Round 2's form paid a second such line (rank-indexed exact table) for the 2.3 % of the windows its 2-byte
 // direct table could not settle, and did the rank / address / compare work branch-free for all windows.
+#include "pm_bits.h"
 #include "pm_internal.h"
 #include "pm_pair.h"
 #include "pm_verify.h"
@@ -114,27 +115,6 @@ typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) u32x4 lds_u128;
 __device__ __forceinline__ lds_u128 *lds128(uint32_t addr) { return reinterpret_cast<lds_u128 *>((uintptr_t)addr); }
 __device__ __forceinline__ lds_u32 *lds32(uint32_t addr) { return reinterpret_cast<lds_u32 *>((uintptr_t)addr); }
-
-__device__ __forceinline__ uint32_t load_packed(const uint32_t *packed, int64_t npacked, int64_t pos) {
-  const int64_t i = pos >> 4;
-  if (pos < 0 || i >= npacked) return 0u;
-  return packed[i];
-}
-
-// f(integral_constant<int, 0>()), f(integral_constant<int, 1>()), ... in order
-template <int... Is, typename F>
-__device__ __forceinline__ void for_windows(std::integer_sequence<int, Is...>, F &&f) { (f(std::integral_constant<int, Is>()), ...); }
-
-// 32 bits from bit O (compile time) of the 96-bit string prev2 : prev1 : cur (bit 0 = bit 0 of prev2)
-template <int O>
-__device__ __forceinline__ uint32_t bits_at(uint32_t p2, uint32_t p1, uint32_t cur) {
-  static_assert(O >= 0 && O < 96, "offset");
-  if constexpr (O == 0) return p2;
-  else if constexpr (O < 32) return __builtin_amdgcn_alignbit(p1, p2, O);
-  else if constexpr (O == 32) return p1;
-  else if constexpr (O < 64) return __builtin_amdgcn_alignbit(cur, p1, O - 32);
-  else return cur >> (O - 64);
-}
 
 // The 20-bit key of field pair (a, b) of a 40-bit window W and the other 20 bits (fields c < d).
 // Bit layout of the LDS bitmap: key bits 0..14 = word, bits 15..19 = bit inside the word.
@@ -337,32 +317,13 @@ __device__ __forceinline__ void pair_resolve(const PairArgs &a, const VerifyStag
 // 256 suspects -- one per wave and emit call, 10^5 to 10^6 per launch on one address at ~2 ns each, was 1.7 of
 // this kernel's 2.0 ms.
 __global__ __launch_bounds__(256) void pm_pair_verify(PairArgs a) {
-  __shared__ pm_hit s_rec[VSTAGE];
-  __shared__ unsigned long long s_base;
-  __shared__ uint32_t s_fill, s_valid, s_full;
-  const VerifyStage vs = {s_rec, &s_fill, &s_valid};
   unsigned long long n = *a.susp_count;
   if (n > a.susp_cap) n = a.susp_cap;
-  const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
-  if (threadIdx.x == 0) { s_fill = 0; s_valid = (uint32_t)VSTAGE; }
-  __syncthreads();
-  // the staged records join the list: one atomic for all of them (block-uniform call)
-  auto flush = [&]() __attribute__((always_inline)) {
-    const uint32_t cnt = min(s_fill, s_valid);
-    __syncthreads();
-    if (threadIdx.x == 0) { s_base = cnt ? atomicAdd(a.counter, (unsigned long long)cnt) : 0ull; s_fill = 0; s_valid = (uint32_t)VSTAGE; }
-    __syncthreads();
-    for (uint32_t i = threadIdx.x; i < cnt; i += blockDim.x) if (s_base + i < a.cap) a.out[s_base + i] = s_rec[i];
-    __syncthreads();
-  };
-  for (unsigned long long base = (unsigned long long)blockIdx.x * blockDim.x; base < n; base += stride) {   // block-uniform trip count
-    const unsigned long long i = base + threadIdx.x;
-    pm_hit first;
+  verify_staged(a, n, [&](unsigned long long i, const VerifyStage &vs, pm_hit *first) __attribute__((always_inline)) {
     bool have = false;
-    if (i < n) {
-      const uint4 r = a.susp[i];
-      const uint64_t pw = ((uint64_t)r.w << 32) | r.z;
-      if (r.x != 0xffffffffu) {                                       // (a slot its wave reserved and did not need)
+    const uint4 r = a.susp[i];
+    const uint64_t pw = ((uint64_t)r.w << 32) | r.z;
+    if (r.x != 0xffffffffu) {                                         // (a slot its wave reserved and did not need)
       const int combo = (int)((pw >> 40) & 7u);
       // the key's row of the bitmap (global copy) -> rank; its slot -> which of its patterns are within k on the other fields
       const uint32_t key = r.x, wo = r.y, row = key & 0x7fffu, bit = key >> 15;
@@ -377,18 +338,11 @@ __global__ __launch_bounds__(256) void pm_pair_verify(PairArgs a) {
           what = (sym_distance(((uint32_t)S ^ wo) & F20) <= a.k ? 1u : 0u) | (sym_distance(((uint32_t)(S >> 20) ^ wo) & F20) <= a.k ? 2u : 0u) |
                  (sym_distance(((uint32_t)(S >> 40) ^ wo) & F20) <= a.k ? 4u : 0u) | ((sl.y >> 31) ? WHAT_REST : 0u);
         }
-        pair_resolve(a, vs, combo, rank, what, wo, (int64_t)(pw & 0xffffffffffull), &first, &have);
-      }
+        pair_resolve(a, vs, combo, rank, what, wo, (int64_t)(pw & 0xffffffffffull), first, &have);
       }
     }
-    if (a.debug & 16) have = false;
-    pair_emit(a, vs, have, first);                                  // (every lane is here)
-    __syncthreads();
-    if (threadIdx.x == 0) s_full = s_fill > (uint32_t)(VSTAGE - 512);   // one thread decides: a wave that runs ahead into the next trip moves s_fill
-    __syncthreads();
-    if (s_full) flush();
-  }
-  flush();
+    return have && !(a.debug & 16);
+  });
 }
 
 // One (field pair, chunk) of the scan.  A, B: key fields (compile time: every window offset of pass A is an
@@ -397,9 +351,7 @@ __global__ __launch_bounds__(256) void pm_pair_verify(PairArgs a) {
 // ring of register entries: pick the window and re-read its bitmap row; rank in the row, slot address, 8-byte
 // load; compare the slot's three patterns).  What the compare cannot dismiss (1e-3 of the windows) is queued in LDS
 // and leaves in batches for pm_pair_verify.  See the file comment and the comments at the stages.
-template <typename F>
-__device__ __forceinline__ void static_for5(F &&f) { for_windows(std::make_integer_sequence<int, 5>(), f); }
-
+//
 // DSP, FLOOR: measurement instantiations (pm_pair_edit_scan below): the pair geometry as the first stage of an
 // EDIT-distance plan tests field A displaced by DSP bases against field B (two clean fields of a match with <= 2 edits sit
 // 5 (B - A) + d bases apart, |d| <= 2; 14 (pair, d) tests cover every placement, scripts/edit_pair_cover.py).  FLOOR = 1
@@ -568,10 +520,10 @@ __device__ __forceinline__ void pair_scan_body(const PairArgs &a, const int comb
       constexpr int OC = 4 + 10 * C;
       const uint32_t lo = e_wo[PH], hi = e_hi[PH];
       uint32_t T[5];
-      static_for5([&](auto SI) __attribute__((always_inline)) { constexpr int si = decltype(SI)::value; T[si] = __builtin_amdgcn_alignbit(hi, lo, OC + 2 * (si - 2)) & f20v; });
+      static_for<5>([&](auto SI) __attribute__((always_inline)) { constexpr int si = decltype(SI)::value; T[si] = __builtin_amdgcn_alignbit(hi, lo, OC + 2 * (si - 2)) & f20v; });
       auto score = [&](uint32_t o) __attribute__((always_inline)) -> int {
         uint32_t m[5];
-        static_for5([&](auto SI) __attribute__((always_inline)) { constexpr int si = decltype(SI)::value; const uint32_t x = o ^ T[si]; m[si] = (x | (x >> 1)) & m5v; });
+        static_for<5>([&](auto SI) __attribute__((always_inline)) { constexpr int si = decltype(SI)::value; const uint32_t x = o ^ T[si]; m[si] = (x | (x >> 1)) & m5v; });
         const int c0 = __popc(m[2]), c1 = __popc(m[2] & m[3]) + 1, c1n = __popc(m[2] & m[1]) + 1;
         const int c2 = __popc(m[2] & m[3] & m[4]) + 2, c2n = __popc(m[2] & m[1] & m[0]) + 2;
         return min(min(c0, min(c1, c1n)), min(c2, c2n)) - 3;          // negative = within two edits as far as this test can tell
@@ -630,7 +582,7 @@ __device__ __forceinline__ void pair_scan_body(const PairArgs &a, const int comb
   int quiet = NR + 1;                                               // wave-uniform: rounds run since a lane last had a hit pending (> NR: the pipeline is empty)
   auto two_rounds = [&]() __attribute__((always_inline)) {
     bool done = false;
-    for_windows(std::make_integer_sequence<int, NR / 2>(), [&](auto Q) __attribute__((always_inline)) {
+    static_for<NR / 2>([&](auto Q) __attribute__((always_inline)) {
       constexpr int q = decltype(Q)::value;
       if (!done && ph == q) {
         round(std::integral_constant<int, 2 * q>()); round(std::integral_constant<int, 2 * q + 1>());
@@ -665,12 +617,12 @@ __device__ __forceinline__ void pair_scan_body(const PairArgs &a, const int comb
     uint32_t acc = 0;
     {
       uint32_t ks[16], wd[16];
-      for_windows(std::make_integer_sequence<int, 16>(), [&](auto WIN) __attribute__((always_inline)) {
+      static_for<16>([&](auto WIN) __attribute__((always_inline)) {
         constexpr int I = decltype(WIN)::value;
         ks[I] = key_of(WIN, prev2, prev1, cur);
         wd[I] = *lds32(ks[I] & 0x1fffcu);
       });
-      for_windows(std::make_integer_sequence<int, 16>(), [&](auto WIN) __attribute__((always_inline)) {
+      static_for<16>([&](auto WIN) __attribute__((always_inline)) {
         constexpr int I = decltype(WIN)::value;
         acc = __builtin_amdgcn_alignbit(wd[I] >> ((ks[I] >> 17) & 31u), acc, 1);   // bits 15..19 of the key pick the bit; window 0 ends up at bit 16
       });

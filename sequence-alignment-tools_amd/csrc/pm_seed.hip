@@ -32,6 +32,7 @@
 // edit-distance plan: tabulated piece hashes, key map in L2), pm_half_scan (exact_halves -k on a key
 // bitmap + rank directory), the dense second kernels pm_edits_verify / pm_half_verify / pm_bases_verify,
 // pm_pack_stream, and the host side (edit_cover, seed_build, seed_upload, seed_launch).
+#include "pm_bits.h"
 #include "pm_internal.h"
 #include "pm_seed.h"
 
@@ -136,15 +137,6 @@ __device__ __forceinline__ uint4 load16(const uint8_t *text, int64_t off, int64_
     return *reinterpret_cast<const uint4 *>(text + off);
   }
   return load16_edge(text, off, n);
-}
-
-// One dword of the 2-bit packed stream = the 16 bases from `pos` (a multiple of 16) on; zero
-// outside the stream, like the bytes load16_edge hands out.
-template <bool NT>
-__device__ __forceinline__ uint32_t load_packed(const uint32_t *packed, int64_t npacked, int64_t pos) {
-  const int64_t i = pos >> 4;
-  if (pos < 0 || i >= npacked) return 0u;
-  return NT ? __builtin_nontemporal_load(packed + i) : packed[i];
 }
 
 // Hash of the combo's part of a window.  MODE 0: any piece layout (mask + fold + multiply);
@@ -1072,22 +1064,6 @@ constexpr uint32_t edit_cover_of(int qa, int qb, int qc) {
          c == 123 ? 0x1u : c == 124 ? 0x19u : c == 134 ? 0x7u : c == 234 ? 0x1u : 0u;
 }
 
-template <int N, class Fn, int... I>
-__device__ __forceinline__ void static_for_impl(Fn &&f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, class Fn>
-__device__ __forceinline__ void static_for(Fn &&f) { static_for_impl<N>(f, std::make_integer_sequence<int, N>{}); }
-
-// 32 bits from bit O (compile time) of the 96-bit string p2 : p1 : cur (bit 0 = bit 0 of p2)
-template <int O>
-__device__ __forceinline__ uint32_t bits_at(uint32_t p2, uint32_t p1, uint32_t cur) {
-  static_assert(O >= 0 && O < 96, "offset");
-  if constexpr (O == 0) return p2;
-  else if constexpr (O < 32) return __builtin_amdgcn_alignbit(p1, p2, O);
-  else if constexpr (O == 32) return p1;
-  else if constexpr (O < 64) return __builtin_amdgcn_alignbit(cur, p1, O - 32);
-  else if constexpr (O == 64) return cur;
-  else return cur >> (O - 64);
-}
 // F of the byte at bit B of p2 : p1 : cur: the byte is picked by the multiply's operand selector
 template <int B>
 __device__ __forceinline__ uint32_t piece_hash_at(uint32_t p2, uint32_t p1, uint32_t cur, uint32_t mul) {

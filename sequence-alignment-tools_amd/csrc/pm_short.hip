@@ -1,5 +1,8 @@
-// pm_short.hip -- patterns of 16..19 characters: the first stage of the edit-distance plan and, further
-// down, the substitution class beside the pair plan (pm_short_sub_scan).
+// pm_short.hip -- patterns of 16..19 characters: the first stage of the edit-distance plan (pm_short_edit_scan, DESIGN.md
+// 4.7) and the substitution class beside the pair plan (pm_short_sub_scan + pm_short_sub_verify).  The two
+// scan kernels are ONE scan (short_scan: bitmaps in LDS, the wave's range, the key-hit queue, its drain, reserved slot
+// blocks) around a struct each -- EditTests, SubCombos -- that says how windows become masks, how a run entry is judged
+// and how a record is packed; their host tables come from one builder (pm_short_tables.h), one upload and one free.
 //
 // The edit plan of pm_seed.hip / pm_pair.hip seeds on the last 20 pattern bases, so a primer of 16..19 bases used to go
 // to the bit-parallel residue kernel.  Here the last SIXTEEN bases are four fields of four -- the four bytes of the 2-bit
@@ -19,13 +22,15 @@
 // N, end-of-sequence and positions outside the stream pack to arbitrary bases: a window that holds one can only gain key
 // hits (the automaton decides on the real characters), and it cannot lose a true one -- a text character that is not the
 // pattern's is an edit of the alignment, and both the cover and the q-gram count argue about the bases no edit touches.
+#include "pm_bits.h"
 #include "pm_internal.h"
 #include "pm_seed.h"
+#include "pm_short_tables.h"
 #include "pm_verify.h"
 
 #include <algorithm>
 #include <cstring>
-#include <utility>
+#include <initializer_list>
 
 namespace pm {
 
@@ -34,58 +39,162 @@ namespace {
 constexpr int SHORT_THREADS = 256;                  // 4 waves share the bitmaps; 48 KiB + 16 KiB of queues: two workgroups per CU
 constexpr int SHORT_WAVES = SHORT_THREADS / 64;
 constexpr int SHORT_PAIRS = 6;
-constexpr int SHORT_BM_WORDS = 2048;                // 2^16 key bits per field pair
-constexpr int SHORT_ROWS = 65536 + 1;               // offset table rows per field pair (+ the end of the last run)
 constexpr int SHORT_QCAP = 2048;                    // 2-byte key-hit entries per wave: two tests of a block (2 x 1024 windows) fit behind a drain
 constexpr int SHORT_OUT_BLOCK = 256;                // seed list slots a wave reserves per atomic
+constexpr int SUB_OUT_BLOCK = 64;                   // suspect slots a wave reserves per atomic
+constexpr uint64_t SHORT_POS_MASK = 0xffffffffffull;   // both lists: position in the low 40 bits, class index of the pattern from bit 40 on
 
-// the tests in table order (the pair-edit plan's): (0,1,0); (0,2,-1..1); (0,3,-2..2); (1,2,0); (1,3,-1..1); (2,3,0)
-constexpr int t_a(int v) { const int t[SHORT_NTESTS] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2}; return t[v]; }
-constexpr int t_b(int v) { const int t[SHORT_NTESTS] = {1, 2, 2, 2, 3, 3, 3, 3, 3, 2, 3, 3, 3, 3}; return t[v]; }
+// ---- the scan both kernels are ------------------------------------------------------------------------------------------
+// A workgroup holds the tile's key bitmaps in LDS; each of its waves walks its share of the workgroup's chunk in blocks of
+// 1024 positions, 16 windows per lane.  Per block and round, a lane's windows become a mask (bit j / 16 + j: window j has
+// the key of the round's first / second test in that test's bitmap); the set bits are queued in the wave's LDS queue and
+// resolved with every lane busy: the key's run behind the offset table, one verdict per run entry, and what passes goes
+// to slots of the output list that the wave reserves a block at a time.
+//
+// What a kernel supplies (EditTests, SubCombos below):
+//   NBM, ROUNDS, OUT_BLOCK   bitmaps in LDS, masks per block, list slots per reservation
+//   test(r, half)            the test a bit of round r's low / high half stands for (< 16)
+//   load(pbase, own, s_bm)   the lane's stream words of a block (pbase = its first window; own = false: it has none)
+//   mask<R>(s_bm)            the mask of round R
+//   hit(bb, from, win, v)    a queued key hit -- window win of lane from in block bb, test v -- as the row of its key
+//                            in the offset table and whatever judge needs of the window (called by the whole wave)
+//   judge(h, cur, &pi)       run entry cur: its pattern (index inside the tile), and whether it leaves as a record
+//   record(v, pi, p)         the 8-byte record of pattern pi at window position p
+struct ShortScanArgs {
+  const uint32_t *packed;               // the stream, 2 bits per base, 16 bases per dword
+  int64_t npacked;
+  int64_t p_lo, p_hi;                   // window positions lo <= p < hi (p = the window's last base)
+  int64_t chunk0, chunk_len;            // first chunk (absolute, chunk_len aligned); positions per workgroup, a multiple of 1024 * SHORT_WAVES
+  const uint32_t *bitmap;               // the tile's: [field pair][SHORT_BM_WORDS]
+  const uint32_t *rows;                 //             [field pair][SHORT_ROWS]: first entry of the key's run in runs
+  uint32_t tile_base;                   // index of the tile's first pattern in the class (records carry class indices)
+  uint64_t *list;                       // seed records / suspects for the kernel behind the scan
+  unsigned long long *list_count;
+  unsigned long long list_cap;
+};
+
+// A wave's slots of an output list: reserved BLOCK at a time with one atomic on the list's counter; the slots of a block
+// the wave does not fill are marked ~0 (the reader skips them), and nothing is written beyond the list's capacity (the
+// counter goes on counting: the caller grows the list and scans again).  All members are wave-uniform.
+template <int BLOCK>
+struct SlotBlocks {
+  uint64_t *list;
+  unsigned long long *count;
+  unsigned long long cap;
+  unsigned long long next = 0;          // next free slot of the reserved block
+  int left = 0;
+
+  __device__ __forceinline__ void mark_unused(int lane) const {
+    for (int u = lane; u < left; u += 64) if (next + u < cap) list[next + u] = ~0ull;
+  }
+  // the records of the lanes with `pass`, in lane order (called by the whole wave)
+  __device__ __forceinline__ void put(int lane, bool pass, uint64_t rec) {
+    const unsigned long long bal = __ballot(pass);
+    if (bal == 0) return;
+    const int c = __popcll(bal);
+    if (c > left) {                                                  // a fresh block; what is left of the old one is marked unused
+      mark_unused(lane);
+      unsigned long long got = 0;
+      if (lane == 0) got = atomicAdd(count, (unsigned long long)BLOCK);
+      next = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(got >> 32)) << 32) | __builtin_amdgcn_readfirstlane((uint32_t)got);
+      left = BLOCK;
+    }
+    if (pass) {
+      const unsigned long long slot = next + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0));
+      if (slot < cap) list[slot] = rec;
+    }
+    next += c; left -= c;
+  }
+};
+
+// s_bm: P::NBM * SHORT_BM_WORDS words, s_q: SHORT_WAVES * SHORT_QCAP entries of the workgroup's LDS
+template <typename P>
+__device__ __forceinline__ void short_scan(const ShortScanArgs &a, P &pol, uint32_t *s_bm, uint16_t *s_q) {
+  {
+    const uint4 *src = reinterpret_cast<const uint4 *>(a.bitmap);
+    uint4 *dst = reinterpret_cast<uint4 *>(s_bm);
+    for (int i = threadIdx.x; i < P::NBM * SHORT_BM_WORDS / 4; i += SHORT_THREADS) dst[i] = src[i];
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int64_t sub = a.chunk_len / SHORT_WAVES;
+  const int64_t ws = (a.chunk0 + (int64_t)blockIdx.x) * a.chunk_len + (int64_t)wave * sub;   // a multiple of 1024
+  const int64_t lo = ws > a.p_lo ? ws : a.p_lo, hi = ws + sub < a.p_hi ? ws + sub : a.p_hi;
+  if (lo >= hi) return;
+  uint16_t *q = s_q + wave * SHORT_QCAP;                             // entries: lane << 8 | window << 4 | test
+  int qn = 0;                                                       // wave-uniform: key hits queued
+  SlotBlocks<P::OUT_BLOCK> out = {a.list, a.list_count, a.list_cap};
+
+  // every queued key hit of block bb: the key's run, a verdict per entry, records
+  auto drain = [&](int64_t bb) __attribute__((always_inline)) {
+    for (int base = 0; base < qn; base += 64) {
+      const bool valid = base + lane < qn;
+      const uint32_t e = valid ? (uint32_t)q[base + lane] : 0u;
+      const uint32_t from = e >> 8, win = (e >> 4) & 15u, v = e & 15u;
+      const auto h = pol.hit(bb, from, win, v);
+      uint32_t cur = 0, stop = 0;
+      if (valid) { cur = a.rows[h.row]; stop = a.rows[h.row + 1]; }
+      const int64_t p = bb + 16 * (int64_t)from + (int64_t)win;
+      while (__ballot(cur < stop)) {
+        bool pass = false;
+        uint32_t pi = 0;
+        if (cur < stop) { pass = pol.judge(h, cur, &pi); ++cur; }
+        out.put(lane, pass, pol.record(v, pi, p));
+      }
+    }
+    qn = 0;
+  };
+
+  for (int64_t bb = ws + (lo - ws) / 1024 * 1024; bb < hi; bb += 1024) {
+    const int64_t pbase = bb + 16 * lane;                            // this lane's windows: p = pbase .. pbase + 15
+    uint32_t own = 0xffffu;
+    {
+      const int64_t l = lo - pbase, h = hi - pbase;
+      const uint32_t lb = l <= 0 ? 0u : (l >= 16 ? 16u : (uint32_t)l), hb = h <= 0 ? 0u : (h >= 16 ? 16u : (uint32_t)h);
+      own = ((1u << hb) - 1u) & ~((1u << lb) - 1u);
+    }
+    pol.load(pbase, own != 0, s_bm);                                 // (lanes outside the range read nothing: the range's halo bounds every load)
+    static_for<P::ROUNDS>([&](auto R) __attribute__((always_inline)) {
+      constexpr int r = decltype(R)::value;
+      uint32_t m = pol.template mask<r>(s_bm) & (own | (own << 16));
+      const int cnt = __popc(m);
+      if (__ballot(cnt != 0)) {
+        int x = cnt;                                                 // inclusive prefix sum over the wave
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(x, o); if (lane >= o) x += y; }
+        const int total = __shfl(x, 63);
+        if (qn + total > SHORT_QCAP) drain(bb);                      // (total <= SHORT_QCAP; the block's words stay where load put them)
+        int at = qn + x - cnt;
+        while (m) {
+          const int b = __builtin_ctz(m);
+          m &= m - 1u;
+          q[at++] = (uint16_t)(((uint32_t)lane << 8) | ((uint32_t)(b & 15) << 4) | (uint32_t)(b < 16 ? P::test(r, 0) : P::test(r, 1)));
+        }
+        qn += total;
+      }
+    });
+    if (qn) drain(bb);
+  }
+  out.mark_unused(lane);
+}
+
+// ---- edits: 14 tests (field pair, displacement) on four stream words, a q-gram count per run entry ------------------------
+// the tests in table order (the pair-edit plan's): (0,1,0); (0,2,-1..1); (0,3,-2..2); (1,2,0); (1,3,-1..1); (2,3,0) -- the
+// field pairs in the order of sub_fa(2, c) / sub_fb(2, c) (pm_verify.h)
+constexpr int t_pair(int v) { const int t[SHORT_NTESTS] = {0, 1, 1, 1, 2, 2, 2, 2, 2, 3, 4, 4, 4, 5}; return t[v]; }
 constexpr int t_d(int v) { const int t[SHORT_NTESTS] = {0, -1, 0, 1, -2, -1, 0, 1, 2, 0, -1, 0, 1, 0}; return t[v]; }
-constexpr int pair_of(int a, int b) { return a == 0 ? b - 1 : (a == 1 ? b + 1 : 5); }   // (0,1) (0,2) (0,3) (1,2) (1,3) (2,3)
 // A window's text: 20 bases from p - 17 on, base t at bits 2t of a 40-bit string; window base i (0..15) = t = i + 2.
-constexpr int off_a(int v) { return 4 + 8 * t_a(v) - 2 * t_d(v); }   // field A, d bases early
-constexpr int off_b(int v) { return 4 + 8 * t_b(v); }
-constexpr uint32_t test_word(int v) { return (uint32_t)off_a(v) | ((uint32_t)off_b(v) << 8) | ((uint32_t)pair_of(t_a(v), t_b(v)) << 16); }
+constexpr int off_a(int v) { return 4 + 8 * sub_fa(2, t_pair(v)) - 2 * t_d(v); }   // field A, d bases early
+constexpr int off_b(int v) { return 4 + 8 * sub_fb(2, t_pair(v)); }
+constexpr uint32_t test_word(int v) { return (uint32_t)off_a(v) | ((uint32_t)off_b(v) << 8) | ((uint32_t)t_pair(v) << 16); }
 __constant__ uint32_t SHORT_TEST[16] = {test_word(0), test_word(1), test_word(2), test_word(3), test_word(4), test_word(5), test_word(6),
                                         test_word(7), test_word(8), test_word(9), test_word(10), test_word(11), test_word(12), test_word(13), 0, 0};
 
-struct ShortArgs {
-  const uint32_t *packed;               // the stream, 2 bits per base, 16 bases per dword
-  int64_t npacked;
-  int64_t p_lo, p_hi;                   // window positions lo <= p < hi
-  int64_t chunk0, chunk_len;            // first chunk (absolute, chunk_len aligned); positions per workgroup, a multiple of 1024 * SHORT_WAVES
-  const uint32_t *bitmap;               // [pair][SHORT_BM_WORDS]
-  const uint32_t *rows;                 // [pair][SHORT_ROWS]: first entry of the key's run in runs
+struct ShortArgs : ShortScanArgs {
   const uint32_t *runs;                 // pattern indices (inside the tile) by pair and key
   const uint32_t *pat16;                // the patterns' last 16 bases, 2 bits each
-  uint32_t tile_base;                   // index of the tile's first pattern in the class (seed records carry class indices)
-  uint64_t *seed_out;
-  unsigned long long *seed_count;
-  unsigned long long seed_cap;
 };
-
-__device__ __forceinline__ uint32_t load_words(const uint32_t *packed, int64_t npacked, int64_t pos) {
-  const int64_t i = pos >> 4;
-  return (pos < 0 || i >= npacked) ? 0u : packed[i];
-}
-
-template <int... Is, typename F>
-__device__ __forceinline__ void static_each(std::integer_sequence<int, Is...>, F &&f) { (f(std::integral_constant<int, Is>()), ...); }
-
-// 32 bits from bit O (compile time) of the 128-bit string w0 : w1 : w2 : w3 (bit 0 = bit 0 of w0)
-template <int O>
-__device__ __forceinline__ uint32_t bits128(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3) {
-  static_assert(O >= 0 && O < 128, "offset");
-  if constexpr (O == 0) return w0;
-  else if constexpr (O < 32) return __builtin_amdgcn_alignbit(w1, w0, O);
-  else if constexpr (O == 32) return w1;
-  else if constexpr (O < 64) return __builtin_amdgcn_alignbit(w2, w1, O - 32);
-  else if constexpr (O == 64) return w2;
-  else if constexpr (O < 96) return __builtin_amdgcn_alignbit(w3, w2, O - 64);
-  else return w3 >> (O - 96);
-}
 
 // q-gram lemma with positions over the pattern's last 16 bases P (base i at bits 2i), field B in place: an edit touches at
 // most four of the 13 four-base words and three of the 14 three-base words; every untouched word sits in the text within
@@ -104,121 +213,63 @@ __device__ __forceinline__ bool short_plausible(uint32_t P, uint32_t xlo, uint32
 }
 
 template <int K>
+struct EditTests {
+  static constexpr int NBM = SHORT_PAIRS, ROUNDS = (K == 2 ? SHORT_NTESTS : 2) / 2, OUT_BLOCK = SHORT_OUT_BLOCK;
+  static constexpr int test(int r, int half) { return K == 2 ? 2 * r + half : (half ? SHORT_NTESTS - 1 : 0); }   // (k = 1: the tests (0,1,0) and (2,3,0))
+  struct Hit { uint32_t row, xlo, xhi; };                           // xlo : xhi as short_plausible takes them
+  const ShortArgs &a;
+  uint32_t w0, w1, w2, w3;                                          // the 64 bases from pbase - 32 on
+
+  __device__ __forceinline__ void load(int64_t pbase, bool own, const uint32_t *) {
+    w0 = w1 = w2 = w3 = 0;
+    if (own) {
+      w0 = load_packed(a.packed, a.npacked, pbase - 32); w1 = load_packed(a.packed, a.npacked, pbase - 16);
+      w2 = load_packed(a.packed, a.npacked, pbase); w3 = load_packed(a.packed, a.npacked, pbase + 16);
+    }
+  }
+  template <int R>
+  __device__ __forceinline__ uint32_t mask(const uint32_t *s_bm) const {
+    uint32_t m = 0;
+    static_for<16>([&](auto J) __attribute__((always_inline)) {
+      constexpr int j = decltype(J)::value, O = 30 + 2 * j;
+      auto in_bitmap = [&](auto VV) __attribute__((always_inline)) -> uint32_t {
+        constexpr int v = decltype(VV)::value, OA = O + off_a(v), OB = O + off_b(v), BM = t_pair(v) * SHORT_BM_WORDS;
+        const uint32_t key = (bits_at<OA>(w0, w1, w2, w3) & 0xffu) | ((bits_at<OB>(w0, w1, w2, w3) & 0xffu) << 8);
+        return (s_bm[BM + (key >> 5)] >> (key & 31u)) & 1u;
+      };
+      m |= in_bitmap(std::integral_constant<int, test(R, 0)>()) << j;
+      m |= in_bitmap(std::integral_constant<int, test(R, 1)>()) << (16 + j);
+    });
+    return m;
+  }
+  __device__ __forceinline__ Hit hit(int64_t bb, uint32_t from, uint32_t win, uint32_t v) const {
+    const uint32_t tw = SHORT_TEST[v];
+    const int64_t pb = bb + 16 * (int64_t)from;
+    const uint32_t x0 = load_packed(a.packed, a.npacked, pb - 32), x1 = load_packed(a.packed, a.npacked, pb - 16);
+    const uint32_t x2 = load_packed(a.packed, a.npacked, pb), x3 = load_packed(a.packed, a.npacked, pb + 16);
+    // the window's 40 bits start at bit 30 + 2 win of x0 : x1 : x2 : x3
+    const bool up = win != 0;                                        // (bit 30 + 2 win >= 32)
+    const uint32_t sh = (30u + 2u * win) & 31u;
+    const uint32_t b0 = up ? x1 : x0, b1 = up ? x2 : x1, b2 = up ? x3 : x2;
+    const uint32_t xlo = __builtin_amdgcn_alignbit(b1, b0, sh), xhi = __builtin_amdgcn_alignbit(b2, b1, sh);
+    const uint32_t ka = __builtin_amdgcn_alignbit(xhi, xlo, tw & 31u) & 0xffu, kb = __builtin_amdgcn_alignbit(xhi, xlo, (tw >> 8) & 31u) & 0xffu;
+    return {(tw >> 16) * (uint32_t)SHORT_ROWS + (ka | (kb << 8)), xlo, xhi};
+  }
+  __device__ __forceinline__ bool judge(const Hit &h, uint32_t cur, uint32_t *pi) const {
+    *pi = a.runs[cur];
+    return short_plausible<K>(a.pat16[*pi], h.xlo, h.xhi);
+  }
+  __device__ __forceinline__ uint64_t record(uint32_t, uint32_t pi, int64_t p) const {   // a seed: pattern i, position p
+    return ((uint64_t)(a.tile_base + pi) << 40) | ((uint64_t)p & SHORT_POS_MASK);
+  }
+};
+
+template <int K>
 __global__ __launch_bounds__(SHORT_THREADS) void pm_short_edit_scan(ShortArgs a) {
   __shared__ uint32_t s_bm[SHORT_PAIRS * SHORT_BM_WORDS];
   __shared__ uint16_t s_q[SHORT_WAVES][SHORT_QCAP];
-  {
-    const uint4 *src = reinterpret_cast<const uint4 *>(a.bitmap);
-    uint4 *dst = reinterpret_cast<uint4 *>(s_bm);
-    for (int i = threadIdx.x; i < SHORT_PAIRS * SHORT_BM_WORDS / 4; i += SHORT_THREADS) dst[i] = src[i];
-  }
-  __syncthreads();
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int64_t sub = a.chunk_len / SHORT_WAVES;
-  const int64_t ws = (a.chunk0 + (int64_t)blockIdx.x) * a.chunk_len + (int64_t)wave * sub;   // a multiple of 1024
-  const int64_t lo = ws > a.p_lo ? ws : a.p_lo, hi = ws + sub < a.p_hi ? ws + sub : a.p_hi;
-  if (lo >= hi) return;
-  uint16_t *q = s_q[wave];
-  int qn = 0;                                                       // wave-uniform: key hits queued
-  unsigned long long ob_next = 0;                                   // wave-uniform: next free slot of the wave's reserved run of the seed list
-  int ob_left = 0;
-
-  // every queued key hit of block bb: its run of patterns, the q-gram count, seed records
-  auto drain = [&](int64_t bb) __attribute__((always_inline)) {
-    for (int base = 0; base < qn; base += 64) {
-      const bool valid = base + lane < qn;
-      const uint32_t e = valid ? (uint32_t)q[base + lane] : 0u;
-      const uint32_t win = (e >> 4) & 15u, tw = SHORT_TEST[e & 15u];
-      const int64_t pb = bb + 16 * (int64_t)(e >> 8);
-      const uint32_t w0 = load_words(a.packed, a.npacked, pb - 32), w1 = load_words(a.packed, a.npacked, pb - 16);
-      const uint32_t w2 = load_words(a.packed, a.npacked, pb), w3 = load_words(a.packed, a.npacked, pb + 16);
-      // the window's 40 bits start at bit 30 + 2 win of w0 : w1 : w2 : w3
-      const bool up = win != 0;                                      // (bit 30 + 2 win >= 32)
-      const uint32_t sh = (30u + 2u * win) & 31u;
-      const uint32_t b0 = up ? w1 : w0, b1 = up ? w2 : w1, b2 = up ? w3 : w2;
-      const uint32_t xlo = __builtin_amdgcn_alignbit(b1, b0, sh), xhi = __builtin_amdgcn_alignbit(b2, b1, sh);
-      const uint32_t ka = __builtin_amdgcn_alignbit(xhi, xlo, tw & 31u) & 0xffu, kb = __builtin_amdgcn_alignbit(xhi, xlo, (tw >> 8) & 31u) & 0xffu;
-      const uint32_t row = (tw >> 16) * (uint32_t)SHORT_ROWS + (ka | (kb << 8));
-      uint32_t cur = 0, stop = 0;
-      if (valid) { cur = a.rows[row]; stop = a.rows[row + 1]; }
-      const int64_t p = pb + (int64_t)win;
-      while (__ballot(cur < stop)) {
-        bool pass = false;
-        uint32_t pi = 0;
-        if (cur < stop) {
-          pi = a.runs[cur];
-          pass = short_plausible<K>(a.pat16[pi], xlo, xhi);
-          ++cur;
-        }
-        const unsigned long long bal = __ballot(pass);
-        if (bal == 0) continue;
-        const int c = __popcll(bal);
-        if (c > ob_left) {                                           // a fresh run of slots; what is left of the old one is marked unused
-          for (int u = lane; u < ob_left; u += 64) if (ob_next + u < a.seed_cap) a.seed_out[ob_next + u] = ~0ull;
-          unsigned long long got = 0;
-          if (lane == 0) got = atomicAdd(a.seed_count, (unsigned long long)SHORT_OUT_BLOCK);
-          ob_next = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(got >> 32)) << 32) | __builtin_amdgcn_readfirstlane((uint32_t)got);
-          ob_left = SHORT_OUT_BLOCK;
-        }
-        if (pass) {
-          const unsigned long long slot = ob_next + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0));
-          if (slot < a.seed_cap) a.seed_out[slot] = ((uint64_t)(a.tile_base + pi) << 40) | ((uint64_t)p & 0xffffffffffull);
-        }
-        ob_next += c; ob_left -= c;
-      }
-    }
-    qn = 0;
-  };
-
-  for (int64_t bb = ws + (lo - ws) / 1024 * 1024; bb < hi; bb += 1024) {
-    const int64_t pbase = bb + 16 * lane;                            // this lane's windows: p = pbase .. pbase + 15
-    uint32_t own = 0xffffu;
-    {
-      const int64_t l = lo - pbase, h = hi - pbase;
-      const uint32_t lb = l <= 0 ? 0u : (l >= 16 ? 16u : (uint32_t)l), hb = h <= 0 ? 0u : (h >= 16 ? 16u : (uint32_t)h);
-      own = ((1u << hb) - 1u) & ~((1u << lb) - 1u);
-    }
-    uint32_t w0 = 0, w1 = 0, w2 = 0, w3 = 0;
-    if (own) {                                                       // (lanes outside the range read nothing: the range's halo bounds every load)
-      w0 = load_words(a.packed, a.npacked, pbase - 32); w1 = load_words(a.packed, a.npacked, pbase - 16);
-      w2 = load_words(a.packed, a.npacked, pbase); w3 = load_words(a.packed, a.npacked, pbase + 16);
-    }
-    // two tests per round: bit j of the low / high half = window j has the key of test v / v + 1 in the pair's bitmap
-    static_each(std::make_integer_sequence<int, (K == 2 ? SHORT_NTESTS : 2) / 2>(), [&](auto R) __attribute__((always_inline)) {
-      constexpr int r = decltype(R)::value;
-      constexpr int V0 = K == 2 ? 2 * r : 0, V1 = K == 2 ? 2 * r + 1 : SHORT_NTESTS - 1;   // (k = 1: the tests (0,1,0) and (2,3,0))
-      uint32_t m = 0;
-      static_each(std::make_integer_sequence<int, 16>(), [&](auto J) __attribute__((always_inline)) {
-        constexpr int j = decltype(J)::value, O = 30 + 2 * j;
-        auto hit = [&](auto VV) __attribute__((always_inline)) -> uint32_t {
-          constexpr int v = decltype(VV)::value, OA = O + off_a(v), OB = O + off_b(v), BM = pair_of(t_a(v), t_b(v)) * SHORT_BM_WORDS;
-          const uint32_t key = (bits128<OA>(w0, w1, w2, w3) & 0xffu) | ((bits128<OB>(w0, w1, w2, w3) & 0xffu) << 8);
-          return (s_bm[BM + (key >> 5)] >> (key & 31u)) & 1u;
-        };
-        m |= hit(std::integral_constant<int, V0>()) << j;
-        m |= hit(std::integral_constant<int, V1>()) << (16 + j);
-      });
-      m &= own | (own << 16);
-      const int cnt = __popc(m);
-      if (__ballot(cnt != 0)) {
-        int x = cnt;                                                 // inclusive prefix sum over the wave
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(x, o); if (lane >= o) x += y; }
-        const int total = __shfl(x, 63);
-        if (qn + total > SHORT_QCAP) drain(bb);                      // (total <= SHORT_QCAP)
-        int at = qn + x - cnt;
-        while (m) {
-          const int b = __builtin_ctz(m);
-          m &= m - 1u;
-          q[at++] = (uint16_t)(((uint32_t)lane << 8) | ((uint32_t)(b & 15) << 4) | (uint32_t)(b < 16 ? V0 : V1));
-        }
-        qn += total;
-      }
-    });
-    if (qn) drain(bb);
-  }
-  for (int u = lane; u < ob_left; u += 64) if (ob_next + u < a.seed_cap) a.seed_out[ob_next + u] = ~0ull;
+  EditTests<K> tests = {a, 0, 0, 0, 0};
+  short_scan(a, tests, s_bm, s_q[0]);
 }
 
 // ---- substitutions only: patterns of 16..19 characters beside a main class on the pair plan ------------
@@ -236,185 +287,168 @@ __global__ __launch_bounds__(SHORT_THREADS) void pm_short_edit_scan(ShortArgs a)
 // As above, N, end-of-sequence and positions outside the stream pack to arbitrary bases: such a window can only gain
 // suspects.  It cannot lose a candidate either: a text character that is not the pattern's is one of its <= k mismatches,
 // and the two fields no mismatch touches are clean on the packed bases as well.
-constexpr int SUB_OUT_BLOCK = 64;                   // suspect slots a wave reserves per atomic
 constexpr int SUB_VERIFY_BLOCKS = 4096;
-constexpr uint64_t SUB_POS_MASK = 0xffffffffffull;  // suspect: combo << 61 | class index of the pattern (21 bits) << 40 | position
-constexpr size_t SUB_MAX_PATTERNS = (size_t)1 << 21;
+constexpr int SUB_INDEX_BITS = 21;                  // suspect: combo << 61 | class index of the pattern (21 bits) << 40 | position
 
-
-struct SubArgs {
-  const uint8_t *text;
+struct SubArgs : ShortScanArgs {
+  const uint2 *runs;                    // {pattern index inside the tile, its last 16 bases} by combo and key
+  const uint8_t *text;                  // from here on: what pair_verify and pair_emit read (pm_verify.h)
   int64_t n;
-  const uint32_t *packed;               // the stream, 2 bits per base, 16 bases per dword
-  int64_t npacked;
-  int64_t p_lo, p_hi;                   // window positions lo <= p < hi (hit ends p + 1)
-  int64_t chunk0, chunk_len;            // as ShortArgs
   int k, eos_code, ncombos, viol_level;
   int fa[SUB_MAX_COMBOS], fb[SUB_MAX_COMBOS];
-  const uint32_t *bitmap;               // the tile's: [combo][SHORT_BM_WORDS]
-  const uint32_t *rows;                 //             [combo][SHORT_ROWS]: first entry of the key's run in runs
-  const uint2 *runs;                    //             {pattern index inside the tile, its last 16 bases} by combo and key
-  uint32_t tile_base;
-  const uint8_t *pat_len;               // the class's (pair_verify)
+  const uint8_t *pat_len;               // the class's
   const uint32_t *pat_id;
   const uint8_t *pat_codes;
   const uint32_t *pat_zone;
-  uint64_t *susp;
-  unsigned long long *susp_count;
-  unsigned long long susp_cap;
   pm_hit *out;
   unsigned long long *counter;
   unsigned long long cap;
 };
 
+// the first (second) field of every combo, a nibble each: a lane looks up the fields of its own combo with a shift
 template <int K>
-__global__ __launch_bounds__(SHORT_THREADS) void pm_short_sub_scan(SubArgs a) {
-  constexpr int NC = sub_ncombos(K);
-  __shared__ uint32_t s_bm[NC * SHORT_BM_WORDS];
-  __shared__ uint16_t s_q[SHORT_WAVES][SHORT_QCAP];
-  {
-    const uint4 *src = reinterpret_cast<const uint4 *>(a.bitmap);
-    uint4 *dst = reinterpret_cast<uint4 *>(s_bm);
-    for (int i = threadIdx.x; i < NC * SHORT_BM_WORDS / 4; i += SHORT_THREADS) dst[i] = src[i];
-  }
-  __syncthreads();
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int64_t sub = a.chunk_len / SHORT_WAVES;
-  const int64_t ws = (a.chunk0 + (int64_t)blockIdx.x) * a.chunk_len + (int64_t)wave * sub;   // a multiple of 1024
-  const int64_t lo = ws > a.p_lo ? ws : a.p_lo, hi = ws + sub < a.p_hi ? ws + sub : a.p_hi;
-  if (lo >= hi) return;
-  uint16_t *q = s_q[wave];
-  int qn = 0;                                                       // wave-uniform: key hits queued
-  unsigned long long ob_next = 0;                                   // wave-uniform: next free slot of the wave's reserved run of the suspect list
-  int ob_left = 0;
-  uint32_t w1 = 0, w2 = 0;                                          // this lane's stream words of the block (sub_window)
+constexpr uint32_t combo_fields(bool second) {
+  uint32_t x = 0;
+  for (int c = 0; c < sub_ncombos(K); ++c) x |= (uint32_t)(second ? sub_fb(K, c) : sub_fa(K, c)) << (4 * c);
+  return x;
+}
 
-  // every queued key hit of block bb: the key's run of {pattern, last 16 bases}, the other two fields, suspects
-  auto drain = [&](int64_t bb) __attribute__((always_inline)) {
-    for (int base = 0; base < qn; base += 64) {
-      const bool valid = base + lane < qn;
-      const uint32_t e = valid ? (uint32_t)q[base + lane] : 0u;
-      const uint32_t win = (e >> 4) & 15u, c = e & 15u, from = e >> 8;
-      const uint32_t W = sub_window((uint32_t)__shfl((int)w1, (int)from), (uint32_t)__shfl((int)w2, (int)from), win);
-      // the combo's fields, a nibble each: (0,1) (0,2) (0,3) (1,2) (1,3) (2,3) / (0,1) (2,3)
-      const int fa = (int)(((K == 2 ? 0x211000u : 0x20u) >> (4u * c)) & 15u), fb = (int)(((K == 2 ? 0x332321u : 0x31u) >> (4u * c)) & 15u);
-      const uint32_t row = c * (uint32_t)SHORT_ROWS + sub_key(W, fa, fb);
-      uint32_t cur = 0, stop = 0;
-      if (valid) { cur = a.rows[row]; stop = a.rows[row + 1]; }
-      const int64_t p = bb + 16 * (int64_t)from + (int64_t)win;
-      while (__ballot(cur < stop)) {
-        bool pass = false;
-        uint32_t pi = 0;
-        if (cur < stop) {
-          const uint2 r = a.runs[cur];
-          pi = r.x;
-          pass = sub_others_within(W, r.y, K);
-          ++cur;
-        }
-        const unsigned long long bal = __ballot(pass);
-        if (bal == 0) continue;
-        const int n = __popcll(bal);
-        if (n > ob_left) {                                           // a fresh run of slots; what is left of the old one is marked unused
-          for (int u = lane; u < ob_left; u += 64) if (ob_next + u < a.susp_cap) a.susp[ob_next + u] = ~0ull;
-          unsigned long long got = 0;
-          if (lane == 0) got = atomicAdd(a.susp_count, (unsigned long long)SUB_OUT_BLOCK);
-          ob_next = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(got >> 32)) << 32) | __builtin_amdgcn_readfirstlane((uint32_t)got);
-          ob_left = SUB_OUT_BLOCK;
-        }
-        if (pass) {
-          const unsigned long long slot = ob_next + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0));
-          if (slot < a.susp_cap) a.susp[slot] = ((uint64_t)c << 61) | ((uint64_t)(a.tile_base + pi) << 40) | ((uint64_t)p & SUB_POS_MASK);
-        }
-        ob_next += n; ob_left -= n;
-      }
-    }
-    qn = 0;
-  };
+template <int K>
+struct SubCombos {
+  static constexpr int NC = sub_ncombos(K), NBM = NC, ROUNDS = NC / 2, OUT_BLOCK = SUB_OUT_BLOCK;
+  static constexpr int test(int r, int half) { return 2 * r + half; }   // a test is a combo
+  struct Hit { uint32_t row, W; };                                   // W: the window (sub_window)
+  const SubArgs &a;
+  uint32_t w1, w2;                                                  // the 32 bases from pbase - 16 on
+  uint32_t m[ROUNDS];
 
-  for (int64_t bb = ws + (lo - ws) / 1024 * 1024; bb < hi; bb += 1024) {
-    const int64_t pbase = bb + 16 * lane;                            // this lane's windows: p = pbase .. pbase + 15
-    uint32_t own = 0xffffu;
-    {
-      const int64_t l = lo - pbase, h = hi - pbase;
-      const uint32_t lb = l <= 0 ? 0u : (l >= 16 ? 16u : (uint32_t)l), hb = h <= 0 ? 0u : (h >= 16 ? 16u : (uint32_t)h);
-      own = ((1u << hb) - 1u) & ~((1u << lb) - 1u);
-    }
+  // all masks at once: every window is cut out of the words once, for all combos
+  __device__ __forceinline__ void load(int64_t pbase, bool own, const uint32_t *s_bm) {
     w1 = 0; w2 = 0;
-    if (own) { w1 = load_words(a.packed, a.npacked, pbase - 16); w2 = load_words(a.packed, a.npacked, pbase); }   // (lanes outside the range read nothing)
-    // two combos per mask: bit j of the low / high half = window j has the key of combo 2r / 2r + 1 in that combo's bitmap
-    uint32_t m[NC / 2];
+    if (own) { w1 = load_packed(a.packed, a.npacked, pbase - 16); w2 = load_packed(a.packed, a.npacked, pbase); }
 #pragma unroll
-    for (int r = 0; r < NC / 2; ++r) m[r] = 0;
-    static_each(std::make_integer_sequence<int, 16>(), [&](auto J) __attribute__((always_inline)) {
+    for (int r = 0; r < ROUNDS; ++r) m[r] = 0;
+    static_for<16>([&](auto J) __attribute__((always_inline)) {
       constexpr int j = decltype(J)::value;
       const uint32_t W = sub_window(w1, w2, j);
-      static_each(std::make_integer_sequence<int, NC>(), [&](auto C) __attribute__((always_inline)) {
+      static_for<NC>([&](auto C) __attribute__((always_inline)) {
         constexpr int c = decltype(C)::value;
         const uint32_t key = sub_key(W, sub_fa(K, c), sub_fb(K, c));
         m[c / 2] |= ((s_bm[c * SHORT_BM_WORDS + (key >> 5)] >> (key & 31u)) & 1u) << (16 * (c & 1) + j);
       });
     });
-    static_each(std::make_integer_sequence<int, NC / 2>(), [&](auto R) __attribute__((always_inline)) {
-      constexpr int r = decltype(R)::value;
-      uint32_t mm = m[r] & (own | (own << 16));
-      const int cnt = __popc(mm);
-      if (__ballot(cnt != 0)) {
-        int x = cnt;                                                 // inclusive prefix sum over the wave
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(x, o); if (lane >= o) x += y; }
-        const int total = __shfl(x, 63);
-        if (qn + total > SHORT_QCAP) drain(bb);                      // (total <= SHORT_QCAP)
-        int at = qn + x - cnt;
-        while (mm) {
-          const int b = __builtin_ctz(mm);
-          mm &= mm - 1u;
-          q[at++] = (uint16_t)(((uint32_t)lane << 8) | ((uint32_t)(b & 15) << 4) | (uint32_t)(2 * r + (b >> 4)));
-        }
-        qn += total;
-      }
-    });
-    if (qn) drain(bb);
   }
-  for (int u = lane; u < ob_left; u += 64) if (ob_next + u < a.susp_cap) a.susp[ob_next + u] = ~0ull;
+  template <int R>
+  __device__ __forceinline__ uint32_t mask(const uint32_t *) const { return m[R]; }
+  __device__ __forceinline__ Hit hit(int64_t, uint32_t from, uint32_t win, uint32_t c) const {
+    const uint32_t W = sub_window((uint32_t)__shfl((int)w1, (int)from), (uint32_t)__shfl((int)w2, (int)from), win);
+    const int fa = (int)((combo_fields<K>(false) >> (4u * c)) & 15u), fb = (int)((combo_fields<K>(true) >> (4u * c)) & 15u);
+    return {c * (uint32_t)SHORT_ROWS + sub_key(W, fa, fb), W};
+  }
+  __device__ __forceinline__ bool judge(const Hit &h, uint32_t cur, uint32_t *pi) const {
+    const uint2 r = a.runs[cur];
+    *pi = r.x;
+    return sub_others_within(h.W, r.y, K);
+  }
+  __device__ __forceinline__ uint64_t record(uint32_t c, uint32_t pi, int64_t p) const {
+    return ((uint64_t)c << 61) | ((uint64_t)(a.tile_base + pi) << 40) | ((uint64_t)p & SHORT_POS_MASK);
+  }
+};
+
+template <int K>
+__global__ __launch_bounds__(SHORT_THREADS) void pm_short_sub_scan(SubArgs a) {
+  __shared__ uint32_t s_bm[sub_ncombos(K) * SHORT_BM_WORDS];
+  __shared__ uint16_t s_q[SHORT_WAVES][SHORT_QCAP];
+  SubCombos<K> combos = {a, 0, 0, {}};
+  short_scan(a, combos, s_bm, s_q[0]);
 }
 
 // The scan's suspects, one per thread: the pair plan's exact stage with fields of four bases.  Records leave through the
-// workgroup's LDS stage (pair_emit), as in pm_pair_verify.
+// workgroup's LDS stage (verify_staged), as in pm_pair_verify.
 __global__ __launch_bounds__(256) void pm_short_sub_verify(SubArgs a) {
-  __shared__ pm_hit s_rec[VSTAGE];
-  __shared__ unsigned long long s_base;
-  __shared__ uint32_t s_fill, s_valid, s_full;
-  const VerifyStage vs = {s_rec, &s_fill, &s_valid};
-  unsigned long long n = *a.susp_count;
-  if (n > a.susp_cap) n = a.susp_cap;
-  const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
-  if (threadIdx.x == 0) { s_fill = 0; s_valid = (uint32_t)VSTAGE; }
-  __syncthreads();
-  auto flush = [&]() __attribute__((always_inline)) {               // the staged records join the list: one atomic (block-uniform call)
-    const uint32_t cnt = min(s_fill, s_valid);
-    __syncthreads();
-    if (threadIdx.x == 0) { s_base = cnt ? atomicAdd(a.counter, (unsigned long long)cnt) : 0ull; s_fill = 0; s_valid = (uint32_t)VSTAGE; }
-    __syncthreads();
-    for (uint32_t i = threadIdx.x; i < cnt; i += blockDim.x) if (s_base + i < a.cap) a.out[s_base + i] = s_rec[i];
-    __syncthreads();
+  unsigned long long n = *a.list_count;
+  if (n > a.list_cap) n = a.list_cap;
+  verify_staged(a, n, [&](unsigned long long i, const VerifyStage &, pm_hit *hh) __attribute__((always_inline)) {
+    const uint64_t r = a.list[i];
+    return r != ~0ull &&                                              // (a slot its wave reserved and did not need)
+           pair_verify<4>(a, (int)(r >> 61), (int64_t)(r & SHORT_POS_MASK), (uint32_t)(r >> 40) & ((1u << SUB_INDEX_BITS) - 1u), hh);
+  });
+}
+
+// ---- host: tables ------------------------------------------------------------------------------------------------------
+// What the two classes' builds share: the option and alphabet checks, the patterns' last 16 bases in the stream's packing,
+// the split into tiles.
+struct ShortClassPlan {
+  bool ascii = false;
+  int eos_code = -1, maxlen = 0;
+  std::vector<uint32_t> tail;           // per pattern: its last 16 bases, 2 bits each
+  size_t ntile = 0, per = 0;            // tiles of `per` patterns (the last one may hold fewer)
+};
+
+// index_bits: what a record of the kernel has for the pattern's class index
+std::string short_class_plan(const std::string &kernel, const std::vector<Pattern> &pats, const Alphabet &alpha, int k, int eos_code, int index_bits,
+                             size_t tile, ShortClassPlan *c) {
+  if (k < 1 || k > 2) return kernel + " is built for k = 1 and k = 2";
+  const bool norm = alpha.nch['A'] == 0 && alpha.nch['C'] == 1 && alpha.nch['G'] == 2 && alpha.nch['T'] == 3;
+  const bool ascii = alpha.size == 256 && alpha.nch['A'] == 'A' && alpha.nch['C'] == 'C' && alpha.nch['G'] == 'G' && alpha.nch['T'] == 'T';
+  if (!norm && !ascii) return "stream alphabet is neither A,C,G,T-normalized nor raw ASCII";
+  c->ascii = ascii && !norm; c->eos_code = eos_code >= 0 && eos_code < 256 ? eos_code : -1;
+  auto base2 = [&](unsigned char ch) -> int {                       // the stream's packing (pm_seed.hip pack4)
+    switch (ch) { case 'A': return 0; case 'C': return 1; case 'G': return c->ascii ? 3 : 2; case 'T': return c->ascii ? 2 : 3; }
+    return -1;
   };
-  for (unsigned long long base = (unsigned long long)blockIdx.x * blockDim.x; base < n; base += stride) {   // block-uniform trip count
-    const unsigned long long i = base + threadIdx.x;
-    pm_hit hh;
-    bool have = false;
-    if (i < n) {
-      const uint64_t r = a.susp[i];
-      if (r != ~0ull)                                                 // (a slot its wave reserved and did not need)
-        have = pair_verify<4>(a, (int)(r >> 61), (int64_t)(r & SUB_POS_MASK), (uint32_t)(r >> 40) & (uint32_t)(SUB_MAX_PATTERNS - 1), &hh);
-    }
-    pair_emit(a, vs, have, hh);                                       // (every lane is here)
-    __syncthreads();
-    if (threadIdx.x == 0) s_full = s_fill > (uint32_t)(VSTAGE - 512);
-    __syncthreads();
-    if (s_full) flush();
+  const size_t np = pats.size();
+  if (np >= ((size_t)1 << index_bits)) return "too many patterns of 16..19 characters (" + std::to_string(index_bits) + "-bit pattern index)";
+  c->tail.resize(np);
+  for (size_t j = 0; j < np; ++j) {
+    const std::string &s = pats[j].s;
+    const int L = (int)s.size();
+    if (L < 16 || L > 19) return kernel + " takes patterns of 16..19 characters";
+    for (unsigned char ch : s) if (base2(ch) < 0) return "pattern with characters other than A,C,G,T";
+    c->maxlen = std::max(c->maxlen, L);
+    uint32_t w = 0;
+    for (int i = 0; i < 16; ++i) w |= (uint32_t)base2((unsigned char)s[L - 16 + i]) << (2 * i);
+    c->tail[j] = w;
   }
-  flush();
+  if (tile == 0) tile = SHORT_TILE_DEFAULT;
+  c->ntile = np ? (np + tile - 1) / tile : 0; c->per = c->ntile ? (np + c->ntile - 1) / c->ntile : 0;
+  return "";
+}
+
+// The tiles' key indices (pm_short_tables.h) over the field pairs (fa[c], fb[c]); runs(tile, tails of the tile's patterns,
+// their order by pair and key) makes the kernel's run entries of the order.
+template <typename Tile, typename Runs>
+void short_tiles(const ShortClassPlan &c, int npairs, const int *fa, const int *fb, std::vector<Tile> *tiles, Runs &&runs) {
+  tiles->resize(c.ntile);
+  for (size_t ti = 0; ti < c.ntile; ++ti) {
+    Tile &tt = (*tiles)[ti];
+    const size_t lo = ti * c.per, hi = std::min(c.tail.size(), lo + c.per);
+    ShortKeyIndex x = short_key_index(c.tail.data() + lo, hi - lo, npairs, fa, fb);
+    tt.base = (uint32_t)lo;
+    tt.bitmap = std::move(x.bitmap); tt.rows = std::move(x.rows);
+    runs(tt, c.tail.data() + lo, hi - lo, x.order);
+  }
+}
+
+// hipMalloc + copy of one table after the other; the first error stays
+struct Upload {
+  hipStream_t st;
+  hipError_t err = hipSuccess;
+  template <typename T, typename D>
+  void operator()(const std::vector<T> &src, D **dst) {
+    if (err != hipSuccess) return;
+    const size_t bytes = src.size() * sizeof(T);
+    err = hipMalloc((void **)dst, bytes ? bytes : 16);
+    if (err == hipSuccess && bytes) err = hipMemcpyAsync(*dst, src.data(), bytes, hipMemcpyHostToDevice, st);
+  }
+  template <typename Tile>
+  void tile(const Tile &s, ShortTileDevice *x) { x->base = s.base; (*this)(s.bitmap, &x->bitmap); (*this)(s.rows, &x->rows); (*this)(s.runs, &x->runs); }
+  hipError_t done() const { return err != hipSuccess ? err : hipStreamSynchronize(st); }   // (the host tables may go now)
+};
+
+void free_tables(std::initializer_list<void *> ptrs, std::vector<ShortTileDevice> *tiles) {
+  for (void *p : ptrs) if (p) (void)hipFree(p);
+  for (ShortTileDevice &x : *tiles) for (void *p : {(void *)x.bitmap, (void *)x.rows, x.runs, (void *)x.pat16}) if (p) (void)hipFree(p);
 }
 
 }  // namespace
@@ -423,85 +457,33 @@ std::string short_build(const std::vector<Pattern> &pats, const std::vector<uint
                         size_t tile, ShortTables *out) {
   ShortTables &t = *out;
   t = ShortTables();
-  if (k < 1 || k > 2) return "pm_short_edit_scan is built for k = 1 and k = 2";
-  const bool norm = alpha.nch['A'] == 0 && alpha.nch['C'] == 1 && alpha.nch['G'] == 2 && alpha.nch['T'] == 3;
-  const bool ascii = alpha.size == 256 && alpha.nch['A'] == 'A' && alpha.nch['C'] == 'C' && alpha.nch['G'] == 'G' && alpha.nch['T'] == 'T';
-  if (!norm && !ascii) return "stream alphabet is neither A,C,G,T-normalized nor raw ASCII";
-  t.k = k; t.ascii = ascii && !norm; t.eos_code = eos_code >= 0 && eos_code < 256 ? eos_code : -1;
-  auto base2 = [&](unsigned char ch) -> int {                       // the stream's packing (pm_seed.hip pack4)
-    switch (ch) { case 'A': return 0; case 'C': return 1; case 'G': return t.ascii ? 3 : 2; case 'T': return t.ascii ? 2 : 3; }
-    return -1;
-  };
-  const size_t np = pats.size();
-  if (np >= ((size_t)1 << 22)) return "too many patterns of 16..19 characters (22-bit pattern index)";
-  t.records.assign(np * 32, 0);
-  std::vector<uint32_t> p16(np);
-  for (size_t j = 0; j < np; ++j) {
-    const std::string &s = pats[j].s;
-    const int L = (int)s.size();
-    if (L < 16 || L > 19) return "pm_short_edit_scan takes patterns of 16..19 characters";
-    for (unsigned char ch : s) if (base2(ch) < 0) return "pattern with characters other than A,C,G,T";
-    t.maxlen = std::max(t.maxlen, L);
-    uint32_t w = 0;
-    for (int i = 0; i < 16; ++i) w |= (uint32_t)base2((unsigned char)s[L - 16 + i]) << (2 * i);
-    p16[j] = w;
-    edit_record_fill(s, ids[j], &t.records[j * 32]);
-  }
-  if (tile == 0) tile = SHORT_TILE_DEFAULT;
-  const size_t ntile = np ? (np + tile - 1) / tile : 0, per = ntile ? (np + ntile - 1) / ntile : 0;
-  t.tiles.resize(ntile);
-  for (size_t ti = 0; ti < ntile; ++ti) {
-    ShortTables::Tile &tt = t.tiles[ti];
-    const size_t lo = ti * per, hi = std::min(np, lo + per), m = hi - lo;
-    tt.base = (uint32_t)lo;
-    tt.pat16.assign(p16.begin() + lo, p16.begin() + hi);
-    tt.bitmap.assign((size_t)SHORT_PAIRS * SHORT_BM_WORDS, 0);
-    tt.rows.assign((size_t)SHORT_PAIRS * SHORT_ROWS, 0);
-    tt.runs.assign((size_t)SHORT_PAIRS * m, 0);
-    for (int a = 0; a < 4; ++a) for (int b = a + 1; b < 4; ++b) {
-      const int pr = pair_of(a, b);
-      auto key_of = [&](uint32_t w) { return ((w >> (8 * a)) & 0xffu) | (((w >> (8 * b)) & 0xffu) << 8); };
-      uint32_t *rows = &tt.rows[(size_t)pr * SHORT_ROWS];
-      for (size_t j = 0; j < m; ++j) {                               // counting sort by key: rows[key] = first entry of the key's run
-        const uint32_t key = key_of(tt.pat16[j]);
-        tt.bitmap[(size_t)pr * SHORT_BM_WORDS + (key >> 5)] |= 1u << (key & 31u);
-        ++rows[key + 1];
-      }
-      rows[0] = (uint32_t)((size_t)pr * m);
-      for (int key = 0; key < 65536; ++key) rows[key + 1] += rows[key];
-      std::vector<uint32_t> fill(rows, rows + 65536);
-      for (size_t j = 0; j < m; ++j) tt.runs[fill[key_of(tt.pat16[j])]++] = (uint32_t)j;
-    }
-  }
+  ShortClassPlan c;
+  const std::string why = short_class_plan("pm_short_edit_scan", pats, alpha, k, eos_code, 22, tile, &c);
+  if (!why.empty()) return why;
+  t.k = k; t.ascii = c.ascii; t.eos_code = c.eos_code; t.maxlen = c.maxlen;
+  t.records.assign(pats.size() * 32, 0);
+  for (size_t j = 0; j < pats.size(); ++j) edit_record_fill(pats[j].s, ids[j], &t.records[j * 32]);
+  int fa[SHORT_PAIRS], fb[SHORT_PAIRS];                              // all six pairs, in the substitution plan's order at k = 2
+  for (int p = 0; p < SHORT_PAIRS; ++p) { fa[p] = sub_fa(2, p); fb[p] = sub_fb(2, p); }
+  short_tiles(c, SHORT_PAIRS, fa, fb, &t.tiles, [](ShortTables::Tile &tt, const uint32_t *tail, size_t m, std::vector<uint32_t> &order) {
+    tt.runs = std::move(order);
+    tt.pat16.assign(tail, tail + m);
+  });
   return "";
 }
 
 hipError_t short_upload(const ShortTables &t, ShortDevice *d, hipStream_t st) {
   short_free(d);
   d->k = t.k; d->maxlen = t.maxlen; d->ascii = t.ascii; d->eos_code = t.eos_code; d->npat = t.records.size() / 32;
-  auto up = [&](const void *src, size_t bytes, void **dst) -> hipError_t {
-    hipError_t e = hipMalloc(dst, bytes ? bytes : 16);
-    if (e != hipSuccess) return e;
-    return bytes ? hipMemcpyAsync(*dst, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
-  };
-  hipError_t e;
-  if ((e = up(t.records.data(), t.records.size(), (void **)&d->records)) != hipSuccess) return e;
+  Upload up = {st};
+  up(t.records, &d->records);
   d->tiles.resize(t.tiles.size());
-  for (size_t i = 0; i < t.tiles.size(); ++i) {
-    const ShortTables::Tile &s = t.tiles[i];
-    ShortDevice::Tile &x = d->tiles[i];
-    x.base = s.base;
-    if ((e = up(s.bitmap.data(), s.bitmap.size() * 4, (void **)&x.bitmap)) != hipSuccess) return e;
-    if ((e = up(s.rows.data(), s.rows.size() * 4, (void **)&x.rows)) != hipSuccess) return e;
-    if ((e = up(s.runs.data(), s.runs.size() * 4, (void **)&x.runs)) != hipSuccess) return e;
-    if ((e = up(s.pat16.data(), s.pat16.size() * 4, (void **)&x.pat16)) != hipSuccess) return e;
-  }
-  return hipStreamSynchronize(st);                                   // (the host tables may go now)
+  for (size_t i = 0; i < t.tiles.size(); ++i) { up.tile(t.tiles[i], &d->tiles[i]); up(t.tiles[i].pat16, &d->tiles[i].pat16); }
+  return up.done();
 }
 
 void short_free(ShortDevice *d) {
-  if (d->records) (void)hipFree(d->records);
-  for (ShortDevice::Tile &x : d->tiles) { void *ptrs[] = {x.bitmap, x.rows, x.runs, x.pat16}; for (void *p : ptrs) if (p) (void)hipFree(p); }
+  free_tables({d->records}, &d->tiles);
   *d = ShortDevice();
 }
 
@@ -520,11 +502,11 @@ hipError_t short_launch(const ShortDevice &d, const uint8_t *d_text, const uint3
   g.threads = SHORT_THREADS; g.blocks = g.nseg;
   if (geo_out) *geo_out = g;
   if (g.nseg <= 0 || d.tiles.empty()) return hipSuccess;
-  for (const ShortDevice::Tile &x : d.tiles) {
+  for (const ShortTileDevice &x : d.tiles) {
     ShortArgs a;
     a.packed = d_packed; a.npacked = (n + 15) / 16; a.p_lo = p_lo; a.p_hi = p_hi; a.chunk0 = c_lo; a.chunk_len = g.seg_len;
-    a.bitmap = x.bitmap; a.rows = x.rows; a.runs = x.runs; a.pat16 = x.pat16; a.tile_base = x.base;
-    a.seed_out = d_seeds; a.seed_count = d_seed_count; a.seed_cap = seed_cap;
+    a.bitmap = x.bitmap; a.rows = x.rows; a.runs = static_cast<const uint32_t *>(x.runs); a.pat16 = x.pat16; a.tile_base = x.base;
+    a.list = d_seeds; a.list_count = d_seed_count; a.list_cap = seed_cap;
     if (d.k == 2) hipLaunchKernelGGL(pm_short_edit_scan<2>, dim3(g.nseg), dim3(SHORT_THREADS), 0, st, a);
     else hipLaunchKernelGGL(pm_short_edit_scan<1>, dim3(g.nseg), dim3(SHORT_THREADS), 0, st, a);
     const hipError_t e = hipGetLastError();
@@ -539,62 +521,28 @@ std::string short_sub_build(const std::vector<Pattern> &pats, const std::vector<
                             size_t tile, ShortSubTables *out) {
   ShortSubTables &t = *out;
   t = ShortSubTables();
-  if (k < 1 || k > 2) return "pm_short_sub_scan is built for k = 1 and k = 2";
-  const bool norm = alpha.nch['A'] == 0 && alpha.nch['C'] == 1 && alpha.nch['G'] == 2 && alpha.nch['T'] == 3;
-  const bool ascii = alpha.size == 256 && alpha.nch['A'] == 'A' && alpha.nch['C'] == 'C' && alpha.nch['G'] == 'G' && alpha.nch['T'] == 'T';
-  if (!norm && !ascii) return "stream alphabet is neither A,C,G,T-normalized nor raw ASCII";
-  t.k = k; t.ascii = ascii && !norm; t.eos_code = eos_code >= 0 && eos_code < 256 ? eos_code : -1;
+  ShortClassPlan c;
+  const std::string why = short_class_plan("pm_short_sub_scan", pats, alpha, k, eos_code, SUB_INDEX_BITS, tile, &c);
+  if (!why.empty()) return why;
+  t.k = k; t.ascii = c.ascii; t.eos_code = c.eos_code; t.maxlen = c.maxlen;
   t.ncombos = sub_ncombos(k);
-  for (int c = 0; c < t.ncombos; ++c) { t.fa[c] = sub_fa(k, c); t.fb[c] = sub_fb(k, c); }
-  auto base2 = [&](unsigned char ch) -> int {                       // the stream's packing (pm_seed.hip pack4)
-    switch (ch) { case 'A': return 0; case 'C': return 1; case 'G': return t.ascii ? 3 : 2; case 'T': return t.ascii ? 2 : 3; }
-    return -1;
-  };
+  for (int p = 0; p < t.ncombos; ++p) { t.fa[p] = sub_fa(k, p); t.fb[p] = sub_fb(k, p); }
   const size_t np = pats.size();
-  if (np >= SUB_MAX_PATTERNS) return "too many patterns of 16..19 characters (21-bit pattern index)";
   t.pat_len.resize(np); t.pat_id.resize(np); t.pat_codes.assign(np * 32, 0); t.pat_zone.assign(np, 0);
-  std::vector<uint32_t> p16(np);
   for (size_t j = 0; j < np; ++j) {
     const std::string &s = pats[j].s;
     const int L = (int)s.size();
-    if (L < 16 || L > 19) return "pm_short_sub_scan takes patterns of 16..19 characters";
-    for (int i = 0; i < L; ++i) {
-      if (base2((unsigned char)s[i]) < 0) return "pattern with characters other than A,C,G,T";
-      t.pat_codes[j * 32 + i] = (uint8_t)alpha.nch[(unsigned char)s[i]];
-    }
-    t.maxlen = std::max(t.maxlen, L);
-    uint32_t w = 0;
-    for (int i = 0; i < 16; ++i) w |= (uint32_t)base2((unsigned char)s[L - 16 + i]) << (2 * i);
-    p16[j] = w;
+    for (int i = 0; i < L; ++i) t.pat_codes[j * 32 + i] = (uint8_t)alpha.nch[(unsigned char)s[i]];
     t.pat_len[j] = (uint8_t)L; t.pat_id[j] = ids[j];
     const int es = std::max(0, std::min(L, pats[j].esb)), ee = std::max(0, std::min(L, pats[j].eeb));
     uint32_t z = 0;
     for (int i = 0; i < L; ++i) if (i < es || i >= L - ee) z |= 1u << i;
     t.pat_zone[j] = z;
   }
-  if (tile == 0) tile = SHORT_TILE_DEFAULT;
-  const size_t ntile = np ? (np + tile - 1) / tile : 0, per = ntile ? (np + ntile - 1) / ntile : 0;
-  t.tiles.resize(ntile);
-  for (size_t ti = 0; ti < ntile; ++ti) {
-    ShortSubTables::Tile &tt = t.tiles[ti];
-    const size_t lo = ti * per, hi = std::min(np, lo + per), m = hi - lo;
-    tt.base = (uint32_t)lo;
-    tt.bitmap.assign((size_t)t.ncombos * SHORT_BM_WORDS, 0);
-    tt.rows.assign((size_t)t.ncombos * SHORT_ROWS, 0);
-    tt.runs.assign((size_t)t.ncombos * m, 0);
-    for (int c = 0; c < t.ncombos; ++c) {
-      uint32_t *rows = &tt.rows[(size_t)c * SHORT_ROWS];
-      for (size_t j = 0; j < m; ++j) {                               // counting sort by key: rows[key] = first entry of the key's run
-        const uint32_t key = sub_key(p16[lo + j], t.fa[c], t.fb[c]);
-        tt.bitmap[(size_t)c * SHORT_BM_WORDS + (key >> 5)] |= 1u << (key & 31u);
-        ++rows[key + 1];
-      }
-      rows[0] = (uint32_t)((size_t)c * m);
-      for (int key = 0; key < 65536; ++key) rows[key + 1] += rows[key];
-      std::vector<uint32_t> fill(rows, rows + 65536);
-      for (size_t j = 0; j < m; ++j) tt.runs[fill[sub_key(p16[lo + j], t.fa[c], t.fb[c])]++] = (uint64_t)j | ((uint64_t)p16[lo + j] << 32);
-    }
-  }
+  short_tiles(c, t.ncombos, t.fa, t.fb, &t.tiles, [](ShortSubTables::Tile &tt, const uint32_t *tail, size_t, const std::vector<uint32_t> &order) {
+    tt.runs.resize(order.size());
+    for (size_t i = 0; i < order.size(); ++i) tt.runs[i] = (uint64_t)order[i] | ((uint64_t)tail[order[i]] << 32);
+  });
   return "";
 }
 
@@ -602,31 +550,15 @@ hipError_t short_sub_upload(const ShortSubTables &t, ShortSubDevice *d, hipStrea
   short_sub_free(d);
   d->k = t.k; d->maxlen = t.maxlen; d->ascii = t.ascii; d->eos_code = t.eos_code; d->ncombos = t.ncombos; d->npat = t.pat_len.size();
   for (int c = 0; c < SUB_MAX_COMBOS; ++c) { d->fa[c] = t.fa[c]; d->fb[c] = t.fb[c]; }
-  auto up = [&](const void *src, size_t bytes, void **dst) -> hipError_t {
-    hipError_t e = hipMalloc(dst, bytes ? bytes : 16);
-    if (e != hipSuccess) return e;
-    return bytes ? hipMemcpyAsync(*dst, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
-  };
-  hipError_t e;
-  if ((e = up(t.pat_len.data(), t.pat_len.size(), (void **)&d->pat_len)) != hipSuccess) return e;
-  if ((e = up(t.pat_id.data(), t.pat_id.size() * 4, (void **)&d->pat_id)) != hipSuccess) return e;
-  if ((e = up(t.pat_codes.data(), t.pat_codes.size(), (void **)&d->pat_codes)) != hipSuccess) return e;
-  if ((e = up(t.pat_zone.data(), t.pat_zone.size() * 4, (void **)&d->pat_zone)) != hipSuccess) return e;
+  Upload up = {st};
+  up(t.pat_len, &d->pat_len); up(t.pat_id, &d->pat_id); up(t.pat_codes, &d->pat_codes); up(t.pat_zone, &d->pat_zone);
   d->tiles.resize(t.tiles.size());
-  for (size_t i = 0; i < t.tiles.size(); ++i) {
-    const ShortSubTables::Tile &s = t.tiles[i];
-    ShortSubDevice::Tile &x = d->tiles[i];
-    x.base = s.base;
-    if ((e = up(s.bitmap.data(), s.bitmap.size() * 4, (void **)&x.bitmap)) != hipSuccess) return e;
-    if ((e = up(s.rows.data(), s.rows.size() * 4, (void **)&x.rows)) != hipSuccess) return e;
-    if ((e = up(s.runs.data(), s.runs.size() * 8, (void **)&x.runs)) != hipSuccess) return e;
-  }
-  return hipStreamSynchronize(st);                                   // (the host tables may go now)
+  for (size_t i = 0; i < t.tiles.size(); ++i) up.tile(t.tiles[i], &d->tiles[i]);
+  return up.done();
 }
 
 void short_sub_free(ShortSubDevice *d) {
-  { void *ptrs[] = {d->pat_len, d->pat_id, d->pat_codes, d->pat_zone}; for (void *p : ptrs) if (p) (void)hipFree(p); }
-  for (ShortSubDevice::Tile &x : d->tiles) { void *ptrs[] = {x.bitmap, x.rows, x.runs}; for (void *p : ptrs) if (p) (void)hipFree(p); }
+  free_tables({d->pat_len, d->pat_id, d->pat_codes, d->pat_zone}, &d->tiles);
   *d = ShortSubDevice();
 }
 
@@ -646,10 +578,10 @@ hipError_t short_sub_launch(const ShortSubDevice &d, const uint8_t *d_text, cons
   a.k = d.k; a.eos_code = d.eos_code; a.ncombos = d.ncombos; a.viol_level = d.viol_level;
   for (int c = 0; c < SUB_MAX_COMBOS; ++c) { a.fa[c] = d.fa[c]; a.fb[c] = d.fb[c]; }
   a.pat_len = d.pat_len; a.pat_id = d.pat_id; a.pat_codes = d.pat_codes; a.pat_zone = d.pat_zone;
-  a.susp = d_susp; a.susp_count = d_susp_count; a.susp_cap = susp_cap;
+  a.list = d_susp; a.list_count = d_susp_count; a.list_cap = susp_cap;
   a.out = d_out; a.counter = d_counter; a.cap = cap;
-  for (const ShortSubDevice::Tile &x : d.tiles) {
-    a.bitmap = x.bitmap; a.rows = x.rows; a.runs = reinterpret_cast<const uint2 *>(x.runs); a.tile_base = x.base;
+  for (const ShortTileDevice &x : d.tiles) {
+    a.bitmap = x.bitmap; a.rows = x.rows; a.runs = static_cast<const uint2 *>(x.runs); a.tile_base = x.base;
     if (d.k == 2) hipLaunchKernelGGL(pm_short_sub_scan<2>, dim3(nseg), dim3(SHORT_THREADS), 0, st, a);
     else hipLaunchKernelGGL(pm_short_sub_scan<1>, dim3(nseg), dim3(SHORT_THREADS), 0, st, a);
     const hipError_t e = hipGetLastError();

@@ -1,6 +1,7 @@
 // pm_verify.h -- the exact stage of the substitution plans, shared by pm_pair.hip (patterns of 20..32 characters: tail of
 // 20 bases, four fields of five) and pm_short.hip (patterns of 16..19 characters: tail of 16 bases, four fields of four),
-// and the window arithmetic of pm_short_sub_scan.  All but pair_emit compiles with a plain C++ compiler as well:
+// the window arithmetic of pm_short_sub_scan, and the way records leave a verify kernel (pair_emit, verify_staged: the
+// loop both pm_pair_verify and pm_short_sub_verify are).  All but those two compiles with a plain C++ compiler as well:
 // tests/test_short_sub_host.py checks it against a plain restatement.
 #pragma once
 #include <cstddef>
@@ -148,6 +149,41 @@ __device__ __forceinline__ void pair_emit(const Args &a, const VerifyStage &vs, 
     const unsigned long long o = (((unsigned long long)bhi << 32) | blo) + (unsigned long long)mine;
     if (o < a.cap) a.out[o] = hh;
   }
+}
+
+// The loop of a verify kernel: suspect i of n to thread i of the grid, trip by trip, and the records through the
+// workgroup's stage.  body(i, vs, &hh) judges suspect i (i < n) and returns whether hh is a record of it; it may hand
+// further records of the same suspect to pair_emit itself.  Called by every thread of the workgroup.
+// Args: out, counter, cap.
+template <typename Args, typename Body>
+__device__ __forceinline__ void verify_staged(const Args &a, unsigned long long n, Body &&body) {
+  __shared__ pm_hit s_rec[VSTAGE];
+  __shared__ unsigned long long s_base;
+  __shared__ uint32_t s_fill, s_valid, s_full;
+  const VerifyStage vs = {s_rec, &s_fill, &s_valid};
+  const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
+  if (threadIdx.x == 0) { s_fill = 0; s_valid = (uint32_t)VSTAGE; }
+  __syncthreads();
+  // the staged records join the list: one atomic for all of them (block-uniform call)
+  auto flush = [&]() __attribute__((always_inline)) {
+    const uint32_t cnt = min(s_fill, s_valid);
+    __syncthreads();
+    if (threadIdx.x == 0) { s_base = cnt ? atomicAdd(a.counter, (unsigned long long)cnt) : 0ull; s_fill = 0; s_valid = (uint32_t)VSTAGE; }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < cnt; i += blockDim.x) if (s_base + i < a.cap) a.out[s_base + i] = s_rec[i];
+    __syncthreads();
+  };
+  for (unsigned long long base = (unsigned long long)blockIdx.x * blockDim.x; base < n; base += stride) {   // block-uniform trip count
+    const unsigned long long i = base + threadIdx.x;
+    pm_hit hh;
+    const bool have = i < n && body(i, vs, &hh);
+    pair_emit(a, vs, have, hh);                                       // (every lane is here)
+    __syncthreads();
+    if (threadIdx.x == 0) s_full = s_fill > (uint32_t)(VSTAGE - 512);   // one thread decides: a wave that runs ahead into the next trip moves s_fill
+    __syncthreads();
+    if (s_full) flush();
+  }
+  flush();
 }
 #endif
 

@@ -249,6 +249,37 @@ def test_stream_edges(L):
                 assert got == want, (L, with_main, k, sem, chunk, got, want)
 
 
+DENSE_UNIT = PATTERNS[16]
+
+
+def dense_case():
+    """a stream where one wave queues more key hits than its queue holds: a homopolymer (every window of it has every
+    test's key, and one key's run holds four patterns) and a tandem repeat of a 16-mer, about 10,000 bases"""
+    raw = ("T" * 50 + "A" * 5000 + "\n" + DENSE_UNIT * 300 + "C" * 40).encode()
+    u = DENSE_UNIT
+    pats = ["A" * 16, "A" * 17, "A" * 18, "A" * 19, u, u[3:] + u[:3], u + "ACG", "A" * 22, u + u[:6]]
+    return synth.normalize(raw, TABLE), pats
+
+
+def test_dense_stream():
+    """the wave's queue fills between two rounds of one block (k = 2: one round queues exactly the queue's capacity inside
+    the homopolymer, the next one drains mid-block) and at a block's end (k = 1); a range edge inside the homopolymer"""
+    codes, pats = dense_case()
+    for k, sem in ((2, sat_amd.SEM_AUTO), (2, sat_amd.SEM_SHIFT_AND_INEXACT), (1, sat_amd.SEM_SHIFT_AND_INEXACT)):
+        want = oracle_hits(codes, TABLE, pats, k, sem)
+        assert {pid for _, pid, _ in want} == set(range(1, len(pats) + 1))   # every pattern has hits
+        for chunk in (1 << 26, 1500):
+            pm = engine(pats, k, sem)
+            try:
+                pm.init(codes, TABLE)
+                d = pm.describe()
+                assert pm.selected()[1] == sat_amd.KERNEL_SEED and "pm_short_edit_scan for 7 patterns of 16..19 characters" in d, d
+                got = sat_amd.sorted_tuples(pm.find_all(chunk=chunk))
+            finally:
+                pm.close()
+            assert got == want, (k, sem, chunk, len(got), len(want))
+
+
 @pytest.mark.parametrize("L", [16, 19])
 def test_tiny_streams(L):
     rng = np.random.default_rng(600 + L)

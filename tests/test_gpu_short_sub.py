@@ -20,6 +20,7 @@ import sat_amd
 import synth
 from oracle import pmoracle as O
 from test_gpu_exhaustive import TABLE, entry_bounds, stream_of, substitution_variants
+from test_gpu_short_primers import dense_case
 from test_gpu_windowed import min_window
 
 pytestmark = pytest.mark.gpu
@@ -359,6 +360,26 @@ def test_stream_edges(L):
                 pm.close()
             assert got == want, (L, k, sem, chunk, got, want)
         assert sum(few) > 0
+
+
+def test_dense_stream():
+    """test_gpu_short_primers.dense_case: the wave's queue fills between two rounds of one block (k = 2: one round queues
+    exactly the queue's capacity inside the homopolymer, the next one drains mid-block and the windows are then taken
+    from the queuing lanes' words) and at a block's end (k = 1); a range edge inside the homopolymer"""
+    codes, pats = dense_case()
+    for k, sem, selected, eng in (BITVEC2, INEXACT2, BITVEC1, HALVES1):
+        want = oracle_hits(codes, TABLE, pats, k, eng)
+        assert {pid for _, pid, _ in want} == set(range(1, len(pats) + 1))   # every pattern has hits
+        for chunk in (1 << 26, 1500):
+            pm = engine(pats, k, sem)
+            try:
+                pm.init(codes, TABLE)
+                d = pm.describe()
+                assert pm.selected() == (selected, sat_amd.KERNEL_SEED) and "pm_short_sub_scan for 7 patterns of 16..19 characters" in d, d
+                got = sat_amd.sorted_tuples(pm.find_all(chunk=chunk))
+            finally:
+                pm.close()
+            assert got == want, (k, sem, chunk, len(got), len(want))
 
 
 @pytest.mark.parametrize("L", [16, 19])
