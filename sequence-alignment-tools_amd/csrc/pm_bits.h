@@ -1,5 +1,7 @@
 // pm_bits.h -- what the scan kernels of pm_seed.hip, pm_pair.hip and pm_short.hip share below the level of a plan: the
-// compile-time loop, bit fields at compile-time offsets of a string of stream words, and the load of one stream word.
+// compile-time loop, bit fields at compile-time offsets of a string of stream words, the load of one stream word, the two
+// words a wave carries in from in front of its range, and the mask of a lane's 16 windows that lie inside a range.  (The
+// writer of their output lists is pm_slots.h.)
 #pragma once
 #include <cstdint>
 #include <utility>
@@ -39,6 +41,22 @@ __device__ __forceinline__ uint32_t load_packed(const uint32_t *packed, int64_t 
   const int64_t i = pos >> 4;
   if (pos < 0 || i >= npacked) return 0u;
   return NT ? __builtin_nontemporal_load(packed + i) : packed[i];
+}
+
+// The two dwords in front of a wave's range (ws a multiple of 16): carry2 = the bases ws - 32 .. ws - 17, carry1 = the
+// bases ws - 16 .. ws - 1, both wave-uniform -- what lane 0 and lane 1 of the range's first block borrow.
+template <bool NT = false>
+__device__ __forceinline__ void load_carry(const uint32_t *packed, int64_t npacked, int64_t ws, int lane, uint32_t &carry1, uint32_t &carry2) {
+  const uint32_t pk = load_packed<NT>(packed, npacked, ws - 32 + 16 * (lane & 1));
+  carry2 = __builtin_amdgcn_readlane(pk, 0);
+  carry1 = __builtin_amdgcn_readlane(pk, 1);
+}
+
+// A lane's 16 windows end at pbase .. pbase + 15: bit j is set iff lo <= pbase + j < hi
+__device__ __forceinline__ uint32_t own_mask16(int64_t pbase, int64_t lo, int64_t hi) {
+  const int64_t l = lo - pbase, h = hi - pbase;
+  const uint32_t lb = l <= 0 ? 0u : (l >= 16 ? 16u : (uint32_t)l), hb = h <= 0 ? 0u : (h >= 16 ? 16u : (uint32_t)h);
+  return ((1u << hb) - 1u) & ~((1u << lb) - 1u);
 }
 
 }  // namespace

@@ -35,6 +35,7 @@
 #include "pm_bits.h"
 #include "pm_internal.h"
 #include "pm_seed.h"
+#include "pm_slots.h"
 
 #include <algorithm>
 #include <cstring>
@@ -689,11 +690,7 @@ __global__ __launch_bounds__(SEED_THREADS) void pm_seed_scan(SeedArgs a) {
   const uint32_t *bitmap2 = a.bitmap2 + (size_t)combo * ((size_t)1 << (a.lb2 - 5));
   // the 32 bases in front of the wave's range
   uint32_t carry1, carry2;
-  {
-    const uint32_t pk = load_packed<MODE == 2>(a.packed, a.npacked, ws - 32 + 16 * (lane & 1));
-    carry2 = __builtin_amdgcn_readlane(pk, 0);
-    carry1 = __builtin_amdgcn_readlane(pk, 1);
-  }
+  load_carry<MODE == 2>(a.packed, a.npacked, ws, lane, carry1, carry2);
   const int wbits = 2 * Lw;
   const uint32_t lo_mask = wbits >= 32 ? 0xffffffffu : ((1u << wbits) - 1u);
   const uint32_t hi_mask = wbits > 32 ? ((1u << (wbits - 32)) - 1u) : 0u;
@@ -718,45 +715,11 @@ __global__ __launch_bounds__(SEED_THREADS) void pm_seed_scan(SeedArgs a) {
   //   mostly idle one per Q1 batch.
   uint2 *queue2 = reinterpret_cast<uint2 *>(lds + SEED_BLOOM_STRIDE) + WAVES * QCAP + wave * SEED_Q2CAP;
   int q2n = 0;
-  // HALVES: records go to slots reserved SEED_OUT_BLOCK at a time (wave-uniform state)
-  unsigned long long ob_next = 0;
-  int ob_left = 0;
-  auto emit_half = [&](bool pass, int64_t p, uint32_t pid) __attribute__((always_inline)) {
-    const unsigned long long bal = __ballot(pass);
-    if (bal == 0) return;
-    const int c = __popcll(bal);
-    if (c > ob_left) {
-      if (lane < ob_left && ob_next + lane < a.cap) a.out[ob_next + lane].pid = PM_SEED_HOLE;
-      unsigned long long base = 0;
-      if (lane == 0) base = atomicAdd(a.counter, (unsigned long long)SEED_OUT_BLOCK);
-      ob_next = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32) |
-                __builtin_amdgcn_readfirstlane((uint32_t)base);
-      ob_left = SEED_OUT_BLOCK;
-    }
-    if (pass) {
-      const unsigned long long slot = ob_next + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0));
-      if (slot < a.cap) a.out[slot] = half_seed_record(p, pid);
-    }
-    ob_next += c; ob_left -= c;
-  };
-  auto emit_edit = [&](bool pass, int64_t p, uint32_t pi) __attribute__((always_inline)) {
-    const unsigned long long bal = __ballot(pass);
-    if (bal == 0) return;
-    const int c = __popcll(bal);
-    if (c > ob_left) {
-      if (lane < ob_left && ob_next + lane < a.cap) a.seed_out[ob_next + lane] = ~0ull;
-      unsigned long long base = 0;
-      if (lane == 0) base = atomicAdd(a.counter, (unsigned long long)SEED_OUT_BLOCK);
-      ob_next = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32) |
-                __builtin_amdgcn_readfirstlane((uint32_t)base);
-      ob_left = SEED_OUT_BLOCK;
-    }
-    if (pass) {
-      const unsigned long long slot = ob_next + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0));
-      if (slot < a.cap) a.seed_out[slot] = edit_seed_record(p, pi);
-    }
-    ob_next += c; ob_left -= c;
-  };
+  // the one list an instance writes in reserved blocks: seed records for pm_edits_verify (EDITS), else pm_hit records (HALVES)
+  using OutRec = std::conditional_t<EDITS, uint64_t, pm_hit>;
+  OutRec *out_list;
+  if constexpr (EDITS) out_list = a.seed_out; else out_list = a.out;
+  SlotBlocks<SEED_OUT_BLOCK, OutRec> out = {out_list, a.counter, a.cap};
   auto process_q2 = [&]() __attribute__((always_inline)) {
     if (a.debug & 2) { q2n = 0; return; }
     for (int base = 0; base < q2n; base += 64) {
@@ -784,12 +747,12 @@ __global__ __launch_bounds__(SEED_THREADS) void pm_seed_scan(SeedArgs a) {
         pidx = slot & imask;
         if (!HALVES && !EDITS) pp = a.pat40[pidx];                   // halves / edits: their own record decides
       }
-      if (EDITS) {                                                 // wave-uniform: three-base-word test, seeds out in reserved blocks
+      if constexpr (EDITS) {                                       // three-base-word test, seeds out in reserved blocks
         bool pass = false;
         if ((mm & 255u) && !(a.debug & 4)) pass = edits_plausible(a, p, pidx);
-        emit_edit(pass, p, pidx);
+        out.put(lane, pass, edit_seed_record(p, pidx));
       }
-      if (HALVES) {                                                // wave-uniform: block-reserved output
+      if constexpr (HALVES) {                                      // block-reserved output
         uint32_t pid = 0;
         bool pass = false;
         if ((mm & 255u) && !(a.debug & 4)) {
@@ -813,7 +776,7 @@ __global__ __launch_bounds__(SEED_THREADS) void pm_seed_scan(SeedArgs a) {
             pass = half_seed_ok(a, p, pidx, &pid);
           }
         }
-        emit_half(pass, p, pid);
+        out.put(lane, pass, half_seed_record(p, pid));
       }
       if ((mm & 511u) && !(a.debug & 4)) {
         const uint64_t W = ((uint64_t)whi << 32) | wlo;
@@ -892,11 +855,7 @@ __global__ __launch_bounds__(SEED_THREADS) void pm_seed_scan(SeedArgs a) {
     const int64_t pbase = bb + 16 * lane;
     // positions of this lane that this wave owns (all 16 except in the first/last block)
     uint32_t own = 0xffffu;
-    if (bb < own_lo || bb + 1024 > own_hi) {                       // wave-uniform: edge blocks only
-      const int64_t lo = own_lo - pbase, hi = own_hi - pbase;
-      const uint32_t l = lo <= 0 ? 0u : (lo >= 16 ? 16u : (uint32_t)lo), hh = hi <= 0 ? 0u : (hi >= 16 ? 16u : (uint32_t)hi);
-      own = ((1u << hh) - 1u) & ~((1u << l) - 1u);
-    }
+    if (bb < own_lo || bb + 1024 > own_hi) own = own_mask16(pbase, own_lo, own_hi);   // wave-uniform: edge blocks only
     // 32 window bits at base offset d from window i's first base (EDITS: displaced pieces; they only
     // ever come from the low word, the last piece is never displaced)
     auto wlo_at = [&](int i, int d) __attribute__((always_inline)) -> uint32_t {
@@ -998,8 +957,7 @@ __global__ __launch_bounds__(SEED_THREADS) void pm_seed_scan(SeedArgs a) {
   drain();
   finish();
   process_q2();
-  if (HALVES && lane < ob_left && ob_next + lane < a.cap) a.out[ob_next + lane].pid = PM_SEED_HOLE;
-  if (EDITS && lane < ob_left && ob_next + lane < a.cap) a.seed_out[ob_next + lane] = ~0ull;
+  if (HALVES || EDITS) out.mark_unused(lane);
 }
 
 // ---- edit-distance plan, first stage: pm_edit_scan ------------------------------------------------
@@ -1160,32 +1118,9 @@ __device__ __forceinline__ void edit_scan_body(const SeedArgs &a, const int comb
   const uint8_t *etable = a.etable + ((size_t)combo << a.et_bytes_log);
   const int jshift = a.et_shift;
   uint32_t carry1, carry2;
-  {
-    const uint32_t pk = load_packed<false>(a.packed, a.npacked, ws - 32 + 16 * (lane & 1));
-    carry2 = __builtin_amdgcn_readlane(pk, 0);
-    carry1 = __builtin_amdgcn_readlane(pk, 1);
-  }
+  load_carry(a.packed, a.npacked, ws, lane, carry1, carry2);
   int qn = 0;                                                     // wave-uniform queue fill
-  unsigned long long ob_next = 0;                                 // seed records go to slots reserved SEED_OUT_BLOCK at a time
-  int ob_left = 0;
-  auto emit = [&](bool pass, int64_t p, uint32_t slot_at) __attribute__((always_inline)) {
-    const unsigned long long bal = __ballot(pass);
-    if (bal == 0) return;
-    const int c = __popcll(bal);
-    if (c > ob_left) {
-      if (lane < ob_left && ob_next + lane < a.cap) a.seed_out[ob_next + lane] = ~0ull;
-      unsigned long long base = 0;
-      if (lane == 0) base = atomicAdd(a.counter, (unsigned long long)SEED_OUT_BLOCK);
-      ob_next = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32) |
-                __builtin_amdgcn_readfirstlane((uint32_t)base);
-      ob_left = SEED_OUT_BLOCK;
-    }
-    if (pass) {
-      const unsigned long long slot = ob_next + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0));
-      if (slot < a.cap) a.seed_out[slot] = edit_seed_record(p, ((uint32_t)combo << 20) | slot_at);   // (combo, slot): pm_edits_verify looks the pattern up
-    }
-    ob_next += c; ob_left -= c;
-  };
+  SlotBlocks<SEED_OUT_BLOCK> out = {a.seed_out, a.counter, a.cap};   // seed records, in reserved blocks
   // bucket probe + q-gram test of whole batches of 64 queued windows (all: of what is left, too)
   auto process = [&](bool all) __attribute__((always_inline)) {
     while (qn >= 64 || (all && qn > 0)) {
@@ -1254,7 +1189,7 @@ __device__ __forceinline__ void edit_scan_body(const SeedArgs &a, const int comb
             pass = (m1 | m2 | m3) == ((1u << QA) | (1u << QB) | (1u << QC));
           }
         }
-        if (first) { emit(pass, p, at); first = false; }
+        if (first) { out.put(lane, pass, edit_seed_record(p, ((uint32_t)combo << 20) | at)); first = false; }   // (combo, slot): pm_edits_verify looks the pattern up
         else if (pass) {
           const unsigned long long o = atomicAdd(a.counter, 1ull);
           if (o < a.cap) a.seed_out[o] = edit_seed_record(p, ((uint32_t)combo << 20) | at);
@@ -1280,11 +1215,7 @@ __device__ __forceinline__ void edit_scan_body(const SeedArgs &a, const int comb
     carry1 = __builtin_amdgcn_readlane(cur, 63);
     const int64_t pbase = bb + 16 * lane;
     uint32_t own = 0xffffu;
-    if (bb < own_lo || bb + 1024 > own_hi) {                       // wave-uniform: edge blocks only
-      const int64_t lo = own_lo - pbase, hi = own_hi - pbase;
-      const uint32_t l = lo <= 0 ? 0u : (lo >= 16 ? 16u : (uint32_t)lo), hh = hi <= 0 ? 0u : (hi >= 16 ? 16u : (uint32_t)hi);
-      own = ((1u << hh) - 1u) & ~((1u << l) - 1u);
-    }
+    if (bb < own_lo || bb + 1024 > own_hi) own = own_mask16(pbase, own_lo, own_hi);   // wave-uniform: edge blocks only
     uint32_t sus[NV];                                              // per displacement pattern: the lane's suspicious windows
     static_for<NV>([&](auto V) __attribute__((always_inline)) { sus[decltype(V)::value] = 0; });
 
@@ -1386,7 +1317,7 @@ __device__ __forceinline__ void edit_scan_body(const SeedArgs &a, const int comb
     if (qn >= 128) process(false);
   }
   process(true);
-  if (lane < ob_left && ob_next + lane < a.cap) a.seed_out[ob_next + lane] = ~0ull;
+  out.mark_unused(lane);
 }
 
 __global__ __launch_bounds__(SEED_THREADS) void pm_edit_scan(SeedArgs a) {
@@ -1488,32 +1419,9 @@ __global__ __launch_bounds__(SEED_THREADS) void pm_half_scan(SeedArgs a) {
   if (own_lo < 9) own_lo = 9;                                      // the ten key bases must fit in the stream
   if (own_lo >= own_hi) return;
   uint32_t carry1, carry2;
-  {
-    const uint32_t pk = load_packed<false>(a.packed, a.npacked, ws - 32 + 16 * (lane & 1));
-    carry2 = __builtin_amdgcn_readlane(pk, 0);
-    carry1 = __builtin_amdgcn_readlane(pk, 1);
-  }
+  load_carry(a.packed, a.npacked, ws, lane, carry1, carry2);
   int qn = 0;
-  unsigned long long ob_next = 0;
-  int ob_left = 0;
-  auto emit = [&](bool pass, int64_t p, uint32_t rank) __attribute__((always_inline)) {
-    const unsigned long long bal = __ballot(pass);
-    if (bal == 0) return;
-    const int c = __popcll(bal);
-    if (c > ob_left) {
-      if (lane < ob_left && ob_next + lane < a.cap) a.seed_out[ob_next + lane] = ~0ull;
-      unsigned long long base = 0;
-      if (lane == 0) base = atomicAdd(a.counter, (unsigned long long)SEED_OUT_BLOCK);
-      ob_next = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32) |
-                __builtin_amdgcn_readfirstlane((uint32_t)base);
-      ob_left = SEED_OUT_BLOCK;
-    }
-    if (pass) {
-      const unsigned long long slot = ob_next + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0));
-      if (slot < a.cap) a.seed_out[slot] = edit_seed_record(p, rank);
-    }
-    ob_next += c; ob_left -= c;
-  };
+  SlotBlocks<SEED_OUT_BLOCK> out = {a.seed_out, a.counter, a.cap};
   // whole batches of 64 key hits (all: what is left, too): rank -> slot -> partner test on the carried bases
   auto process = [&](bool all) __attribute__((always_inline)) {
     while (qn >= 64 || (all && qn > 0)) {
@@ -1559,7 +1467,7 @@ __global__ __launch_bounds__(SEED_THREADS) void pm_half_scan(SeedArgs a) {
           if (half_partner_fast(a, mv.x, mv.y, d0, d1, d2, p)) { pass = true; more = 0; }
         }
       }
-      emit(pass, p, rank);
+      out.put(lane, pass, edit_seed_record(p, rank));
     }
   };
 
@@ -1577,11 +1485,7 @@ __global__ __launch_bounds__(SEED_THREADS) void pm_half_scan(SeedArgs a) {
     carry1 = __builtin_amdgcn_readlane(cur, 63);
     const int64_t pbase = bb + 16 * lane;
     uint32_t own = 0xffffu;
-    if (bb < own_lo || bb + 1024 > own_hi) {                       // wave-uniform: edge blocks only
-      const int64_t lo = own_lo - pbase, hi = own_hi - pbase;
-      const uint32_t l = lo <= 0 ? 0u : (lo >= 16 ? 16u : (uint32_t)lo), hh = hi <= 0 ? 0u : (hi >= 16 ? 16u : (uint32_t)hi);
-      own = ((1u << hh) - 1u) & ~((1u << l) - 1u);
-    }
+    if (bb < own_lo || bb + 1024 > own_hi) own = own_mask16(pbase, own_lo, own_hi);   // wave-uniform: edge blocks only
     // the key of window i (its last ten bases) sits at bits 2i + 46 .. 2i + 65 of prev2 : prev1 : cur
     uint32_t acc = 0;
     static_for<2>([&](auto HH) __attribute__((always_inline)) {
@@ -1622,7 +1526,7 @@ __global__ __launch_bounds__(SEED_THREADS) void pm_half_scan(SeedArgs a) {
     }
   }
   process(true);
-  if (lane < ob_left && ob_next + lane < a.cap) a.seed_out[ob_next + lane] = ~0ull;
+  out.mark_unused(lane);
 }
 
 // Second kernel of the edit-distance plan: the seed list is dense (every lane has work), one seed
@@ -1641,51 +1545,41 @@ __device__ __forceinline__ uint32_t seed_pattern(const SeedArgs &a, uint32_t cod
   return a.eidx ? a.eidx[(size_t)(code >> 20) * ((size_t)EDIT_BUCKET << (32 - a.bucket_shift)) + (code & 0xfffffu)] : code;
 }
 
-__global__ __launch_bounds__(256) void pm_edits_verify(EditVerifyArgs v) {
-  const SeedArgs &a = v.a;
+// The loop of the second kernels: seed record i of the list (what the list holds of the scan's count) to thread i of the
+// grid, trip by trip.  body(live, p, code) is called by every lane on every trip -- the trip count is the same on every
+// lane, so ballots inside body stay whole-wave; live = false: the lane has no record (beyond the list's end, or a hole),
+// p and code then mean nothing.  A record is code << 40 | position.
+template <typename Body>
+__device__ __forceinline__ void seed_list_each(const EditVerifyArgs &v, Body &&body) {
   unsigned long long n = *v.nseeds;
   if (n > v.seed_cap) n = v.seed_cap;
   const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
-  const unsigned long long rounds = (n + stride - 1) / stride;     // same trip count for every lane: ballots below stay whole-wave
-  const int lane = threadIdx.x & 63;
-  // output slots are reserved 64 at a time per wave (one counter serves every wave of the grid and
-  // same-address atomics serialise); what a wave leaves unused is marked PM_SEED_HOLE, which the
-  // dedup that follows drops
-  unsigned long long ob_next = 0;
-  int ob_left = 0;
+  const unsigned long long rounds = (n + stride - 1) / stride;
   for (unsigned long long it = 0; it < rounds; ++it) {
     const unsigned long long i = it * stride + (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t sd = i < n ? v.seeds[i] : ~0ull;
+    body(sd != ~0ull, (int64_t)(sd & 0xffffffffffull), (uint32_t)(sd >> 40));
+  }
+}
+
+// The records of all three leave in blocks of SEED_OUT_BLOCK slots (pm_slots.h); the holes are dropped by the dedup
+// (edits, bases) or by pm_seed_extend (halves) that follows.
+__global__ __launch_bounds__(256) void pm_edits_verify(EditVerifyArgs v) {
+  const SeedArgs &a = v.a;
+  const int lane = threadIdx.x & 63;
+  SlotBlocks<SEED_OUT_BLOCK, pm_hit> out = {a.out, a.counter, a.cap};
+  seed_list_each(v, [&](bool live, int64_t p, uint32_t code) __attribute__((always_inline)) {
     uint32_t res = 0, pid = 0;
-    int64_t p = 0;
-    if (i < n) {
-      const uint64_t sd = v.seeds[i];
-      if (sd != ~0ull) { p = (int64_t)(sd & 0xffffffffffull); res = edits_verify(a, p, seed_pattern(a, (uint32_t)(sd >> 40)), &pid); }
-    }
-    if (__ballot(res != 0) == 0) continue;
+    if (live) res = edits_verify(a, p, seed_pattern(a, code), &pid);
+    if (__ballot(res != 0) == 0) return;
 #pragma unroll 1
     for (int d = 0; d < 5; ++d) {
       const uint32_t lvl1 = (res >> (4 * d)) & 15u;
       const int64_t e = p - 1 + d;
-      const bool pass = lvl1 != 0 && e > a.begin && e <= a.end;
-      const unsigned long long bal = __ballot(pass);
-      if (bal == 0) continue;
-      const int c = __popcll(bal);
-      if (c > ob_left) {
-        if (lane < ob_left && ob_next + lane < a.cap) a.out[ob_next + lane].pid = PM_SEED_HOLE;
-        unsigned long long base = 0;
-        if (lane == 0) base = atomicAdd(a.counter, (unsigned long long)SEED_OUT_BLOCK);
-        ob_next = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32) |
-                  __builtin_amdgcn_readfirstlane((uint32_t)base);
-        ob_left = SEED_OUT_BLOCK;
-      }
-      if (pass) {
-        const unsigned long long slot = ob_next + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0));
-        if (slot < a.cap) a.out[slot] = edit_record(e, pid, lvl1);
-      }
-      ob_next += c; ob_left -= c;
+      out.put(lane, lvl1 != 0 && e > a.begin && e <= a.end, edit_record(e, pid, lvl1));
     }
-  }
-  if (lane < ob_left && ob_next + lane < a.cap) a.out[ob_next + lane].pid = PM_SEED_HOLE;
+  });
+  out.mark_unused(lane);
 }
 
 // Second kernel of the ranked exact_halves -k plan: every record (rank of a key, position) is resolved
@@ -1693,44 +1587,19 @@ __global__ __launch_bounds__(256) void pm_edits_verify(EditVerifyArgs v) {
 // records go out in reserved blocks.
 __global__ __launch_bounds__(256) void pm_half_verify(EditVerifyArgs v) {
   const SeedArgs &a = v.a;
-  unsigned long long n = *v.nseeds;
-  if (n > v.seed_cap) n = v.seed_cap;
-  const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
-  const unsigned long long rounds = (n + stride - 1) / stride;     // same trip count for every lane: ballots stay whole-wave
   const int lane = threadIdx.x & 63;
-  unsigned long long ob_next = 0;
-  int ob_left = 0;
-  for (unsigned long long it = 0; it < rounds; ++it) {
-    const unsigned long long i = it * stride + (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-    int64_t p = 0;
+  SlotBlocks<SEED_OUT_BLOCK, pm_hit> out = {a.out, a.counter, a.cap};
+  seed_list_each(v, [&](bool live, int64_t p, uint32_t rank) __attribute__((always_inline)) {
     uint32_t t = 0, t1 = 0;
-    if (i < n) {
-      const uint64_t sd = v.seeds[i];
-      if (sd != ~0ull) { p = (int64_t)(sd & 0xffffffffffull); const uint32_t rank = (uint32_t)(sd >> 40); t = a.hr_first[rank]; t1 = a.hr_first[rank + 1]; }
-    }
+    if (live) { t = a.hr_first[rank]; t1 = a.hr_first[rank + 1]; }
     while (__ballot(t < t1)) {
       uint32_t pid = 0;
       bool pass = false;
       if (t < t1) { pass = half_seed_ok(a, p, a.hr_order[t], &pid); ++t; }
-      const unsigned long long bal = __ballot(pass);
-      if (bal == 0) continue;
-      const int c = __popcll(bal);
-      if (c > ob_left) {
-        if (lane < ob_left && ob_next + lane < a.cap) a.out[ob_next + lane].pid = PM_SEED_HOLE;
-        unsigned long long base = 0;
-        if (lane == 0) base = atomicAdd(a.counter, (unsigned long long)SEED_OUT_BLOCK);
-        ob_next = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32) |
-                  __builtin_amdgcn_readfirstlane((uint32_t)base);
-        ob_left = SEED_OUT_BLOCK;
-      }
-      if (pass) {
-        const unsigned long long slot = ob_next + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0));
-        if (slot < a.cap) a.out[slot] = half_seed_record(p, pid);
-      }
-      ob_next += c; ob_left -= c;
+      out.put(lane, pass, half_seed_record(p, pid));
     }
-  }
-  if (lane < ob_left && ob_next + lane < a.cap) a.out[ob_next + lane].pid = PM_SEED_HOLE;
+  });
+  out.mark_unused(lane);
 }
 
 // exact_bases with edits on the seed family.  exact_bases (exact_bases.cc:69-129) reports, for every
@@ -1751,34 +1620,21 @@ struct BasesArgs {
 
 __global__ __launch_bounds__(256) void pm_bases_verify(EditVerifyArgs v, BasesArgs b) {
   const SeedArgs &a = v.a;
-  unsigned long long n = *v.nseeds;
-  if (n > v.seed_cap) n = v.seed_cap;
-  const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
-  const unsigned long long rounds = (n + stride - 1) / stride;     // same trip count for every lane: ballots stay whole-wave
   const int lane = threadIdx.x & 63;
   const int k = a.edits;
-  unsigned long long ob_next = 0;
-  int ob_left = 0;
-  for (unsigned long long it = 0; it < rounds; ++it) {
-    const unsigned long long i = it * stride + (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-    bool live = false;
-    int64_t p = 0;
+  SlotBlocks<SEED_OUT_BLOCK, pm_hit> out = {a.out, a.counter, a.cap};
+  seed_list_each(v, [&](bool live, int64_t p, uint32_t code) __attribute__((always_inline)) {
     uint32_t pid = 0;
     int L = 0, blk = 0;
     bool prefix = true;
     const uint8_t *pc = nullptr;
-    if (i < n) {
-      const uint64_t sd = v.seeds[i];
-      if (sd != ~0ull) {
-        live = true;
-        p = (int64_t)(sd & 0xffffffffffull);
-        pid = a.pat_id[seed_pattern(a, (uint32_t)(sd >> 40))];        // 1-based index into the whole pattern list
-        L = b.len[pid - 1];
-        const int es = b.esb[pid - 1], ee = b.eeb[pid - 1];
-        prefix = es >= ee;                                           // exact_bases.cc:139-150: the larger block decides
-        blk = prefix ? es : ee;
-        pc = b.codes + (size_t)(pid - 1) * 32 + (prefix ? 0 : L - blk);
-      }
+    if (live) {
+      pid = a.pat_id[seed_pattern(a, code)];                          // 1-based index into the whole pattern list
+      L = b.len[pid - 1];
+      const int es = b.esb[pid - 1], ee = b.eeb[pid - 1];
+      prefix = es >= ee;                                             // exact_bases.cc:139-150: the larger block decides
+      blk = prefix ? es : ee;
+      pc = b.codes + (size_t)(pid - 1) * 32 + (prefix ? 0 : L - blk);
     }
     // pattern end e in p+1-k .. p+1+k; prefix block: the pattern starts at e - L - d, |d| <= k
     for (int t = -2 * k; t <= 2 * k; ++t) {
@@ -1788,25 +1644,12 @@ __global__ __launch_bounds__(256) void pm_bases_verify(EditVerifyArgs v, BasesAr
       const int64_t send = b0 + blk;
       ok = ok && send > b.own_lo && send <= b.own_hi;
       for (int q = 0; q < blk && ok; ++q) ok = a.text[b0 + q] == pc[q];
-      const unsigned long long bal = __ballot(ok);
-      if (bal == 0) continue;
-      const int c = __popcll(bal);
-      if (c > ob_left) {
-        if (lane < ob_left && ob_next + lane < a.cap) a.out[ob_next + lane].pid = PM_SEED_HOLE;
-        unsigned long long base = 0;
-        if (lane == 0) base = atomicAdd(a.counter, (unsigned long long)SEED_OUT_BLOCK);
-        ob_next = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32) |
-                  __builtin_amdgcn_readfirstlane((uint32_t)base);
-        ob_left = SEED_OUT_BLOCK;
-      }
-      if (ok) {
-        const unsigned long long slot = ob_next + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0));
-        if (slot < a.cap) { pm_hit hh; hh.end = send; hh.pid = pid; hh.k = 0; hh.aux[0] = hh.aux[1] = hh.aux[2] = 0; a.out[slot] = hh; }
-      }
-      ob_next += c; ob_left -= c;
+      pm_hit hh;
+      hh.end = send; hh.pid = pid; hh.k = 0; hh.aux[0] = hh.aux[1] = hh.aux[2] = 0;
+      out.put(lane, ok, hh);
     }
-  }
-  if (lane < ob_left && ob_next + lane < a.cap) a.out[ob_next + lane].pid = PM_SEED_HOLE;
+  });
+  out.mark_unused(lane);
 }
 
 // The stream at 2 bits per base, made once per pm_init (a re-encoding of the database like the
@@ -2311,31 +2154,33 @@ hipError_t seed_launch(const SeedDevice &d, const uint8_t *d_text, const uint32_
   a.pat_codes = d.pat_codes; a.cmap = d.cmap; a.out = d_out; a.counter = d_counter; a.cap = cap;
   a.etable = nullptr; a.eidx = nullptr; a.seed_out = nullptr; a.et_shift = 0; a.et_bytes_log = 0; a.et_mask = 0;
   a.hr_image = d.hr_image; a.hr_slots = reinterpret_cast<const uint2 *>(d.hr_slots); a.hr_more = reinterpret_cast<const uint2 *>(d.hr_more); a.hr_first = d.hr_first; a.hr_order = d.hr_order;
-  // the rare out-of-line paths read their parameters from a device copy of the argument block
   if (!d.d_args) return hipErrorInvalidValue;
   a.self = reinterpret_cast<const SeedArgs *>(d.d_args);
-  hipError_t ce = hipMemcpyAsync(d.d_args, &a, sizeof(a), hipMemcpyHostToDevice, st);
+  // Two-kernel plans: the scan writes 8-byte seed records into es->d_seeds under the counter *es->d_seed_count (zeroed by
+  // the caller, stream order) and a second kernel turns that dense list into the records of d_out.  The scan kernels see
+  // `sa`, the second kernels `a` (by value, in v) -- and only that: `self` points at the device copy of `sa`, whose list,
+  // counter and capacity are the scan's, so a second kernel must not read through it.
+  const bool two = d.edits || (d.halves && d.half_ranked);
+  if (two && (!es || !es->d_seeds || !es->d_seed_count)) return hipErrorInvalidValue;
+  SeedArgs sa = a;
+  EditVerifyArgs v{};
+  if (two) {
+    sa.seed_out = es->d_seeds; sa.counter = es->d_seed_count; sa.cap = es->seed_cap;
+    if (d.edits) { sa.etable = d.etable; sa.eidx = d.eidx; sa.et_shift = 32 - d.etable_log + 3; sa.et_mask = ((1u << (d.etable_log - 3)) - 1u) & ~3u; sa.et_bytes_log = d.etable_log - 3; }
+    v.a = a;
+    v.seeds = es->d_seeds; v.nseeds = es->d_seed_count; v.seed_cap = es->seed_cap;
+  }
+  // the rare out-of-line paths read their parameters from a device copy of the argument block: the view the scan kernel has
+  hipError_t ce = hipMemcpyAsync(d.d_args, &sa, sizeof(sa), hipMemcpyHostToDevice, st);
   if (ce != hipSuccess) return ce;
   const dim3 grid(g.blocks), block(SEED_THREADS);
   if (d.edits) {
-    // two kernels: the scan writes seed records (pattern, position) that passed the three-base-word
-    // test into es->d_seeds; pm_edits_verify runs the automaton over that dense list and writes
-    // the candidates to d_out.  *es->d_seed_count is zeroed by the caller (stream order).
-    if (!es || !es->d_seeds || !es->d_seed_count) return hipErrorInvalidValue;
-    SeedArgs sa = a;
-    sa.seed_out = es->d_seeds; sa.counter = es->d_seed_count; sa.cap = es->seed_cap;
-    sa.etable = d.etable; sa.eidx = d.eidx; sa.et_shift = 32 - d.etable_log + 3; sa.et_mask = ((1u << (d.etable_log - 3)) - 1u) & ~3u; sa.et_bytes_log = d.etable_log - 3;
-    // the rare out-of-line paths read the scan's view of the argument block
-    ce = hipMemcpyAsync(d.d_args, &sa, sizeof(sa), hipMemcpyHostToDevice, st);
-    if (ce != hipSuccess) return ce;
+    // the scan's records (pattern, position) passed the three-base-word test; pm_edits_verify runs the automaton over them
     if (es->skip_scan) {}
     else if (d.edit_tabulated) hipLaunchKernelGGL(pm_edit_scan, grid, block, SEED_LDS_BYTES, st, sa);
     else hipLaunchKernelGGL((pm_seed_scan<20, 1, false, true>), grid, block, SEED_LDS_BYTES, st, sa);
     if ((ce = hipGetLastError()) != hipSuccess) return ce;
-    EditVerifyArgs v;
-    v.a = a;
     if (d.edit_tabulated && !es->skip_scan) v.a.eidx = d.eidx;
-    v.seeds = es->d_seeds; v.nseeds = es->d_seed_count; v.seed_cap = es->seed_cap;
     if (es->bases) {
       BasesArgs b;
       b.codes = es->b_codes; b.len = es->b_len; b.esb = es->b_esb; b.eeb = es->b_eeb; b.own_lo = es->own_lo; b.own_hi = es->own_hi;
@@ -2343,17 +2188,11 @@ hipError_t seed_launch(const SeedDevice &d, const uint8_t *d_text, const uint32_
     } else
     hipLaunchKernelGGL(pm_edits_verify, dim3(256 * 16), dim3(256), 0, st, v);
   }
-  else if (d.halves && d.half_ranked) {
-    // two kernels: pm_half_scan writes (rank of the key, position) records of the key hits whose partner test passes
-    // into es->d_seeds, pm_half_verify resolves them on the raw stream into seed records.  *es->d_seed_count zeroed by the caller.
-    if (!es || !es->d_seeds || !es->d_seed_count) return hipErrorInvalidValue;
-    SeedArgs sa = a;
-    sa.seed_out = es->d_seeds; sa.counter = es->d_seed_count; sa.cap = es->seed_cap;
+  else if (two) {
+    // pm_half_scan's records (rank of the key, position) are the key hits whose partner test passes; pm_half_verify resolves
+    // them on the raw stream into seed records
     hipLaunchKernelGGL(pm_half_scan, dim3(g.nseg), block, SEED_LDS_BYTES, st, sa);
     if ((ce = hipGetLastError()) != hipSuccess) return ce;
-    EditVerifyArgs v;
-    v.a = a;
-    v.seeds = es->d_seeds; v.nseeds = es->d_seed_count; v.seed_cap = es->seed_cap;
     hipLaunchKernelGGL(pm_half_verify, dim3(256 * 16), dim3(256), 0, st, v);
   }
   else if (d.halves) hipLaunchKernelGGL((pm_seed_scan<0, 0, true>), grid, block, SEED_LDS_BYTES, st, a);

@@ -26,6 +26,7 @@
 #include "pm_internal.h"
 #include "pm_seed.h"
 #include "pm_short_tables.h"
+#include "pm_slots.h"
 #include "pm_verify.h"
 
 #include <algorithm>
@@ -73,40 +74,6 @@ struct ShortScanArgs {
   unsigned long long list_cap;
 };
 
-// A wave's slots of an output list: reserved BLOCK at a time with one atomic on the list's counter; the slots of a block
-// the wave does not fill are marked ~0 (the reader skips them), and nothing is written beyond the list's capacity (the
-// counter goes on counting: the caller grows the list and scans again).  All members are wave-uniform.
-template <int BLOCK>
-struct SlotBlocks {
-  uint64_t *list;
-  unsigned long long *count;
-  unsigned long long cap;
-  unsigned long long next = 0;          // next free slot of the reserved block
-  int left = 0;
-
-  __device__ __forceinline__ void mark_unused(int lane) const {
-    for (int u = lane; u < left; u += 64) if (next + u < cap) list[next + u] = ~0ull;
-  }
-  // the records of the lanes with `pass`, in lane order (called by the whole wave)
-  __device__ __forceinline__ void put(int lane, bool pass, uint64_t rec) {
-    const unsigned long long bal = __ballot(pass);
-    if (bal == 0) return;
-    const int c = __popcll(bal);
-    if (c > left) {                                                  // a fresh block; what is left of the old one is marked unused
-      mark_unused(lane);
-      unsigned long long got = 0;
-      if (lane == 0) got = atomicAdd(count, (unsigned long long)BLOCK);
-      next = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(got >> 32)) << 32) | __builtin_amdgcn_readfirstlane((uint32_t)got);
-      left = BLOCK;
-    }
-    if (pass) {
-      const unsigned long long slot = next + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0));
-      if (slot < cap) list[slot] = rec;
-    }
-    next += c; left -= c;
-  }
-};
-
 // s_bm: P::NBM * SHORT_BM_WORDS words, s_q: SHORT_WAVES * SHORT_QCAP entries of the workgroup's LDS
 template <typename P>
 __device__ __forceinline__ void short_scan(const ShortScanArgs &a, P &pol, uint32_t *s_bm, uint16_t *s_q) {
@@ -148,12 +115,7 @@ __device__ __forceinline__ void short_scan(const ShortScanArgs &a, P &pol, uint3
 
   for (int64_t bb = ws + (lo - ws) / 1024 * 1024; bb < hi; bb += 1024) {
     const int64_t pbase = bb + 16 * lane;                            // this lane's windows: p = pbase .. pbase + 15
-    uint32_t own = 0xffffu;
-    {
-      const int64_t l = lo - pbase, h = hi - pbase;
-      const uint32_t lb = l <= 0 ? 0u : (l >= 16 ? 16u : (uint32_t)l), hb = h <= 0 ? 0u : (h >= 16 ? 16u : (uint32_t)h);
-      own = ((1u << hb) - 1u) & ~((1u << lb) - 1u);
-    }
+    const uint32_t own = own_mask16(pbase, lo, hi);
     pol.load(pbase, own != 0, s_bm);                                 // (lanes outside the range read nothing: the range's halo bounds every load)
     static_for<P::ROUNDS>([&](auto R) __attribute__((always_inline)) {
       constexpr int r = decltype(R)::value;

@@ -46,11 +46,17 @@ def oracle_hits(name, ids, n):
 
 def expected(name, ids, n):
     """closed form of oracle_hits(name, ids, n) for even n >= N0"""
-    assert n % 2 == 0 and n >= N0
     key = (name, tuple(ids))
     if key not in _BASE:
         _BASE[key] = oracle_hits(name, ids, N0)
-    end, pid, k = _BASE[key]
+    return extend(_BASE[key], n)
+
+
+def extend(base, n):
+    """a list (end, pid, k) of the stream of N0 characters, in (end, pid, k) order and of period 2 between its edges, on the
+    stream of n characters (even, >= N0): head, one period repeated, tail"""
+    assert n % 2 == 0 and n >= N0
+    end, pid, k = base
     head, unit, tail = end <= EDGE, (end > EDGE) & (end <= EDGE + 2), end > N0 - EDGE
     periods = (n - 2 * EDGE) // 2
     shift = 2 * np.arange(periods, dtype=np.int64)[:, None]
