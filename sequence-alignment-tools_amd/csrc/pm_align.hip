@@ -105,6 +105,42 @@ __global__ __launch_bounds__(AL_THREADS) void pm_align_hits_kernel(AlignDevice a
     }
     r.start = st; r.editdist = subs;
     done = true;
+  } else if (!done && !a.indels && k <= AL_MAXK && L > AL_MAXL && L <= AL_MAXL_SUB) {
+    // Substitutions only (-K) and a pattern of 33..64 characters: the band has width zero (b = 0 below), the DP is the one
+    // diagonal (p, p), and this lane walks it without the LDS arrays of the banded DP -- the cell rules of the loop below
+    // with !indels: equal, wildcard-equal, violation (end of sequence, a substitution in an exact zone), substitution; a
+    // row above k ends the DP with no alignment at all, and so does a window that does not fit in front of the hit's end.
+    const int viol = 5 * k + 1, eos = a.eos;
+    const int lconst = a.esb[idx], rconst = a.eeb[idx];
+    int lbexact = 0, rbexact = L + 1;
+    if (lconst > 0) rbexact = L + 1 - lconst;
+    if (rconst > 0) lbexact = rconst;
+    const int64_t st = h.end - L;
+    bool alive = st >= 0;                                           // (buflen < L: row buflen + 1 has no cell)
+    int v = 0;
+    for (int p = 1; p <= L && alive; ++p) {                         // row p = the last p pattern characters, as in the banded DP
+      const int tc = tchar(h.end - p), pc = pat[L - p];
+      const bool zone_sub = (p <= lbexact || p >= rbexact);
+      if (tc == pc) {}
+      else if (a.wc && iupac_pair(mask, pc, tc) && (tc != 'N' || a.tn)) {}
+      else if (tc == eos || pc == eos || zone_sub) v = viol;
+      else v = v + 1;
+      if (viol < v) v = viol;
+      if (v > k) alive = false;
+    }
+    if (alive) {
+      int nsub = 0;
+      for (int q = 0; q < L; ++q) {                                 // the traceback runs from the pattern's first character on
+        const int tc = tchar(st + q), pc = pat[q];
+        char op;
+        if (tc == pc) op = '|';
+        else if (a.wc && iupac_pair(mask, pc, tc) && (tc != 'N' || a.tn)) op = '+';
+        else { op = '*'; ++nsub; }
+        put_op(op); put_tx((char)tc);
+      }
+      r.start = st; r.end = h.end; r.value = v; r.editdist = nsub;
+    }
+    done = true;
   } else if (!done && (L > AL_MAXL || k > AL_MAXK || L == 0)) {     // beyond the device limit: the host aligns this record
     to_host = true; done = true;
   }

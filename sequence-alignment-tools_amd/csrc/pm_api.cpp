@@ -186,6 +186,7 @@ struct pm_handle {
   uint32_t *d_vals = nullptr, *d_vals_alt = nullptr;
   void *d_htemp = nullptr;
   size_t vals_cap = 0, htemp_bytes = 0;
+  size_t nlong = 0;                   // patterns of 33..64 characters on the pair plan (pm_config.long_patterns); 0: no pattern beyond 32 on the seed family
   std::vector<uint8_t> in_rest;       // per inner pattern: 1 = scanned by the bit-parallel residue engine beside the seed family
   size_t nrest = 0;
   // edit-distance plan, patterns of 16..19 characters: a class of their own beside the 20..32 character main class and the
@@ -414,6 +415,7 @@ static void read_knobs(Knobs *k) {
   k->dense_bound = num("PM_DENSE_BOUND");
   k->short_bitpar = is("PM_SHORT_SCAN", "bitpar"); k->short_tile = (long)num("PM_SHORT_TILE");
   k->short_sub_off = is("PM_SHORT_SUB", "off");
+  k->long_sub_off = is("PM_LONG_SUB", "off");
   k->debug = getenv("PM_DEBUG") != nullptr;
 }
 
@@ -666,13 +668,13 @@ static bool seed_eligible(pm_handle *h, std::string *why) {
   }
   if (h->cfg.k > 0 && h->cfg.indels && sem != PM_SEM_KEYWORD_TREE && sem != PM_SEM_SHIFT_AND) { *why = "edit-distance search (-k) runs on the bit-parallel family"; return false; }
   // substitution-only search of 20..32 character A,C,G,T patterns with k = 1, 2 runs on the pair plan
-  // (pm_pair.hip), whose exact verify knows the patterns' exact zones: a substitution there fails
+  // (pm_pair.hip; 20..64 where the long route applies, long_route_allowed), whose exact verify knows the patterns' exact zones: a substitution there fails
   // the reference's constrained verifies (pattern_alignment.cc:320-323, primer_alignment.cc:155)
   bool pair_ok = !h->cfg.indels && (h->cfg.k == 1 || h->cfg.k == 2) && !h->pats.empty();
   for (size_t i = 0; i < h->pats.size(); ++i) {
     const Pattern &p = h->pats[i];
     const bool sub = i < h->in_ssub.size() && h->in_ssub[i];        // 16..19 characters beside the pair plan: pm_short_sub_scan, the same exact verify
-    pair_ok = pair_ok && p.s.size() >= (sub ? 16u : 20u) && p.s.size() <= 32;
+    pair_ok = pair_ok && p.s.size() >= (sub ? 16u : 20u) && p.s.size() <= (h->nlong ? 64u : 32u);
     for (unsigned char ch : p.s) pair_ok = pair_ok && (ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T');
   }
   if (h->knobs.pair >= 0) pair_ok = pair_ok && h->knobs.pair != 0;
@@ -682,28 +684,47 @@ static bool seed_eligible(pm_handle *h, std::string *why) {
   return true;
 }
 
+// the stream is one the pair plan takes
+static bool stream_for_pair_plan(const pm_handle *h) {
+  const Alphabet &A = h->alpha;
+  const bool norm = A.nch['A'] == 0 && A.nch['C'] == 1 && A.nch['G'] == 2 && A.nch['T'] == 3;
+  const bool ascii = A.size == 256 && A.nch['A'] == 'A' && A.nch['C'] == 'C' && A.nch['G'] == 'G' && A.nch['T'] == 'T';
+  return norm || ascii;                                             // (what pair_build asks of the stream)
+}
+
+// -K 1 / -K 2 with primers of 33..64 characters: the caller allows them on the pair plan
+// (pm_config.long_patterns) and the option set is one whose records the plan's exact stage makes -- substitutions only,
+// k = 1 or 2, filter_bitvec, bare shift_and_inexact or exact_halves, no kernel asked for by name, a stream the pair plan
+// takes.  Anything else, PM_LONG_SUB=off included, leaves every handle as it was built before the route existed.
+// Called with wild_seed decided.
+static bool long_route_allowed(const pm_handle *h) {
+  if (!h->cfg.long_patterns || h->knobs.long_sub_off || h->knobs.pair == 0 || h->kern != PM_KERNEL_AUTO) return false;
+  if (h->cfg.indels || (h->cfg.k != 1 && h->cfg.k != 2)) return false;
+  if (h->sem != PM_SEM_FILTER_BITVEC && h->sem != PM_SEM_SHIFT_AND_INEXACT && h->sem != PM_SEM_EXACT_HALVES) return false;
+  if (h->cfg.wildcards && !h->wild_seed) return false;
+  return stream_for_pair_plan(h);
+}
+
 // -K 1 / -K 2 on a list of mixed lengths: the primers of 16..19 characters become a class of their own
 // (in_ssub) when the list also holds a primer of 20..32 characters the pair plan takes and every other primer the seed
 // family could take has 16..19.  Anything else -- a primer of 10..15 characters, no long or no short primer, more short
 // primers than SHORT_SUB_MAX_PATTERNS, exact_bases, a kernel on request, -k, k = 0, PM_SHORT_SUB=off -- leaves the list on
-// the route it had.  Called with in_rest decided.
-static void short_sub_route(pm_handle *h) {
+// the route it had.  Called with in_rest decided.  maxL: the longest primer the main class takes, 32 or -- the long route,
+// long_route_allowed -- 64; a primer of 33..64 characters then counts as one of the main class like one of 20..32.
+static void short_sub_route(pm_handle *h, size_t maxL) {
   h->in_ssub.assign(h->pats.size(), 0);
   h->nssub = 0;
   if (h->knobs.short_sub_off || h->knobs.pair == 0 || h->cfg.indels || (h->cfg.k != 1 && h->cfg.k != 2) || h->kern != PM_KERNEL_AUTO) return;
   if (h->sem != PM_SEM_FILTER_BITVEC && h->sem != PM_SEM_SHIFT_AND_INEXACT && h->sem != PM_SEM_EXACT_HALVES) return;
   if (h->cfg.wildcards && !h->wild_seed) return;
-  const Alphabet &A = h->alpha;
-  const bool norm = A.nch['A'] == 0 && A.nch['C'] == 1 && A.nch['G'] == 2 && A.nch['T'] == 3;
-  const bool ascii = A.size == 256 && A.nch['A'] == 'A' && A.nch['C'] == 'C' && A.nch['G'] == 'G' && A.nch['T'] == 'T';
-  if (!norm && !ascii) return;                                      // (what pair_build asks of the stream)
+  if (!stream_for_pair_plan(h)) return;
   size_t nmain = 0, nsub = 0;
   std::vector<uint8_t> sub(h->pats.size(), 0);
   std::vector<std::string> variants;
   for (size_t i = 0; i < h->pats.size(); ++i) {
     const Pattern &p = h->pats[i];
     const size_t L = p.s.size();
-    bool ok = L >= 10 && L <= 32;                                   // the main class's conditions (init_common)
+    bool ok = L >= 10 && L <= maxL;                                 // the main class's conditions (init_common)
     if (h->wild_seed) ok = ok && expand_iupac(p.s, 16, &variants) && !(h->sem == PM_SEM_FILTER_BITVEC && pattern_n_quirk(h, p));
     else for (unsigned char ch : p.s) ok = ok && (ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T');
     if (!ok) {
@@ -717,6 +738,53 @@ static void short_sub_route(pm_handle *h) {
   if (!nmain || !nsub || nsub > SHORT_SUB_MAX_PATTERNS) return;     // (above the cap the key runs outgrow what the Bloom plan costs)
   h->in_ssub.swap(sub);
   h->nssub = nsub;
+}
+
+// Which engine and class every pattern of the list goes to: in_rest (the bit-parallel residue beside the seed family),
+// in_short (16..19 characters under -k: pm_short_edit_scan), short_only, and -- short_sub_route -- in_ssub.  A pattern set is
+// rarely uniform: a few primers with an ambiguity letter, one that is too short or too long for the seed plan.  Where the
+// engines' records mean the same (one inner pattern per pattern: keyword_tree, shift_and, shift_and_inexact,
+// filter_bitvec) those few are scanned by the bit-parallel kernels into the same record buffer and the rest stays on the
+// seed family.  maxL: the longest pattern the main class takes -- 32, or 64 where the long route applies (init_common
+// classifies for 64 first and again for 32 when the long route does not hold for the list: every call starts afresh).
+// Called with wild_seed decided.
+static void classify_patterns(pm_handle *h, bool want_seed, size_t maxL) {
+  const bool edits_plan = h->cfg.indels && h->cfg.k > 0 && (h->sem == PM_SEM_FILTER_BITVEC || h->sem == PM_SEM_SHIFT_AND_INEXACT);
+  const bool short_class = edits_plan && h->cfg.k <= 2 && !h->knobs.short_bitpar;   // patterns of 16..19 characters: pm_short_edit_scan
+  h->in_rest.assign(h->inner.size(), 0);
+  h->nrest = 0;
+  h->in_short.assign(h->inner.size(), 0);
+  h->nshort = 0; h->short_only = false;
+  if (want_seed && (!h->cfg.wildcards || h->wild_seed) && h->kern == PM_KERNEL_AUTO &&
+      (h->sem == PM_SEM_KEYWORD_TREE || h->sem == PM_SEM_SHIFT_AND || h->sem == PM_SEM_SHIFT_AND_INEXACT || h->sem == PM_SEM_FILTER_BITVEC)) {
+    std::vector<std::string> variants;
+    for (size_t i = 0; i < h->inner.size(); ++i) {
+      const std::string &ps = h->inner[i].s;
+      const bool is_short = short_class && ps.size() >= 16 && ps.size() <= 19;   // otherwise under exactly the main class's conditions
+      bool ok = (ps.size() <= maxL && ps.size() >= (edits_plan ? 20u : 10u)) || is_short;
+      if (h->wild_seed) ok = ok && expand_iupac(ps, 16, &variants) &&   // up to two ambiguity letters (16 variants)
+                         !(h->sem == PM_SEM_FILTER_BITVEC && pattern_n_quirk(h, h->inner[i]));   // (its value needs the text-based verify)
+      else for (unsigned char ch : ps) ok = ok && (ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T');
+      if (!ok) { h->in_rest[i] = 1; ++h->nrest; }
+      else if (is_short) { h->in_short[i] = 1; ++h->nshort; }
+    }
+    // nothing for the main class and something for the residue: one engine, the bit-parallel family
+    if (h->nrest && h->nrest + h->nshort == h->inner.size()) {
+      std::fill(h->in_rest.begin(), h->in_rest.end(), 0); h->nrest = 0;
+      std::fill(h->in_short.begin(), h->in_short.end(), 0); h->nshort = 0;
+    }
+  }
+  else if (short_class && h->kern == PM_KERNEL_SEED && !h->cfg.wildcards) {
+    // the seed family on request: no residue, but the two length classes of the edit plan
+    for (size_t i = 0; i < h->inner.size(); ++i) {
+      const std::string &ps = h->inner[i].s;
+      bool ok = ps.size() >= 16 && ps.size() <= 19;
+      for (unsigned char ch : ps) ok = ok && (ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T');
+      if (ok) { h->in_short[i] = 1; ++h->nshort; }
+    }
+  }
+  h->short_only = h->nshort != 0 && h->nshort == h->inner.size();
+  short_sub_route(h, maxL);
 }
 
 static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
@@ -757,48 +825,30 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
   for (EdgeRecords &e : h->edge) e = EdgeRecords();
   std::string why;
   bool want_seed = h->kern == PM_KERNEL_SEED || h->kern == PM_KERNEL_AUTO;
-  // A pattern set is rarely uniform: a few primers with an ambiguity letter, one that is too short
-  // or too long for the seed plan.  Where the engines' records mean the same (one inner pattern per
-  // pattern: keyword_tree, shift_and, shift_and_inexact, filter_bitvec) those few are scanned by
-  // the bit-parallel kernels into the same record buffer and the rest stays on the seed family.
-  h->in_rest.assign(h->inner.size(), 0);
-  h->nrest = 0;
-  h->in_short.assign(h->inner.size(), 0);
-  h->nshort = 0; h->short_only = false;
-  const bool edits_plan = h->cfg.indels && h->cfg.k > 0 && (h->sem == PM_SEM_FILTER_BITVEC || h->sem == PM_SEM_SHIFT_AND_INEXACT);
-  const bool short_class = edits_plan && h->cfg.k <= 2 && !h->knobs.short_bitpar;   // patterns of 16..19 characters: pm_short_edit_scan
   h->wild_seed = h->cfg.wildcards && want_seed && h->kern == PM_KERNEL_AUTO && stream_letters_plain(h) &&
                  (h->sem == PM_SEM_KEYWORD_TREE || h->sem == PM_SEM_SHIFT_AND || h->sem == PM_SEM_FILTER_BITVEC);
-  if (want_seed && (!h->cfg.wildcards || h->wild_seed) && h->kern == PM_KERNEL_AUTO &&
-      (h->sem == PM_SEM_KEYWORD_TREE || h->sem == PM_SEM_SHIFT_AND || h->sem == PM_SEM_SHIFT_AND_INEXACT || h->sem == PM_SEM_FILTER_BITVEC)) {
-    std::vector<std::string> variants;
-    for (size_t i = 0; i < h->inner.size(); ++i) {
-      const std::string &ps = h->inner[i].s;
-      const bool is_short = short_class && ps.size() >= 16 && ps.size() <= 19;   // otherwise under exactly the main class's conditions
-      bool ok = (ps.size() <= 32 && ps.size() >= (edits_plan ? 20u : 10u)) || is_short;
-      if (h->wild_seed) ok = ok && expand_iupac(ps, 16, &variants) &&   // up to two ambiguity letters (16 variants)
-                         !(h->sem == PM_SEM_FILTER_BITVEC && pattern_n_quirk(h, h->inner[i]));   // (its value needs the text-based verify)
-      else for (unsigned char ch : ps) ok = ok && (ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T');
-      if (!ok) { h->in_rest[i] = 1; ++h->nrest; }
-      else if (is_short) { h->in_short[i] = 1; ++h->nshort; }
+  h->nlong = 0;
+  bool any_long = false;                                            // (a list without a primer of 33..64 is classified once, as without the flag)
+  for (const Pattern &p : h->pats) any_long = any_long || (p.s.size() > 32 && p.s.size() <= 64);
+  if (any_long && long_route_allowed(h)) {
+    // The long primers join the main class only where the main class is the pair plan's: every primer that is neither
+    // residue nor of the 16..19 class has 20..64 characters (exact_halves, which keeps no residue: and A,C,G,T only).
+    // A list for which that does not hold -- and one without a primer of 33..64 -- is classified as without the route.
+    classify_patterns(h, want_seed, 64);
+    size_t nlong = 0;
+    bool pair_takes = true;
+    for (size_t i = 0; i < h->pats.size(); ++i) {
+      const std::string &ps = h->pats[i].s;
+      if (h->in_ssub[i]) continue;
+      if (h->sem == PM_SEM_EXACT_HALVES) { for (unsigned char ch : ps) pair_takes = pair_takes && (ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T'); pair_takes = pair_takes && ps.size() <= 64; }
+      else if (i < h->in_rest.size() && h->in_rest[i]) continue;
+      pair_takes = pair_takes && ps.size() >= 20;
+      if (ps.size() > 32) ++nlong;
     }
-    // nothing for the main class and something for the residue: one engine, the bit-parallel family
-    if (h->nrest && h->nrest + h->nshort == h->inner.size()) {
-      std::fill(h->in_rest.begin(), h->in_rest.end(), 0); h->nrest = 0;
-      std::fill(h->in_short.begin(), h->in_short.end(), 0); h->nshort = 0;
-    }
+    if (nlong && pair_takes) h->nlong = nlong;
   }
-  else if (short_class && h->kern == PM_KERNEL_SEED && !h->cfg.wildcards) {
-    // the seed family on request: no residue, but the two length classes of the edit plan
-    for (size_t i = 0; i < h->inner.size(); ++i) {
-      const std::string &ps = h->inner[i].s;
-      bool ok = ps.size() >= 16 && ps.size() <= 19;
-      for (unsigned char ch : ps) ok = ok && (ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T');
-      if (ok) { h->in_short[i] = 1; ++h->nshort; }
-    }
-  }
-  h->short_only = h->nshort != 0 && h->nshort == h->inner.size();
-  short_sub_route(h);
+  if (!h->nlong) classify_patterns(h, want_seed, 32);
+  else if (h->knobs.debug) fprintf(stderr, "[pm] long route: %zu patterns of 33..64 characters on the pair plan\n", h->nlong);
   if (want_seed && !seed_eligible(h, &why)) {
     if (h->kern == PM_KERNEL_SEED) return fail(h, PM_E_UNSUPPORTED, "seed engine: " + why);
     want_seed = false;
@@ -874,7 +924,12 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
       std::vector<Pattern> tp(sp.begin() + lo, sp.begin() + hi);
       std::vector<uint32_t> tid(sid.begin() + lo, sid.begin() + hi);
       PairTables pt;
-      const std::string msg = pair_build(tp, tid, h->alpha, sk, h->eos_code, &pt, h->knobs.pair_row);
+      const std::string msg = pair_build(tp, tid, h->alpha, sk, h->eos_code, &pt, h->knobs.pair_row, 3, h->nlong ? PAIR_MAX_LEN_WIDE : PAIR_MAX_LEN);
+      // With long primers in the main class (h->nlong) the plan cannot refuse: long_route_allowed has checked k and the
+      // stream, the classification has left the main class A,C,G,T patterns (variants under -w) of 20..64 characters, and
+      // a tile holds at most 2^21 of them.  The seed plan below could not take such a list, so a refusal is an error here,
+      // not a change of route.
+      if (!msg.empty() && h->nlong) return fail(h, PM_E_UNSUPPORTED, "pair plan (long route): " + msg);
       if (!msg.empty()) {                                            // not for this set: the seed plan below takes it
         for (PairDevice &d : h->pair) pair_free(&d);
         h->pair.clear();
@@ -1563,6 +1618,12 @@ extern "C" int pm_describe(const pm_handle *h, char *buf, size_t buflen) {
     snprintf(buf, buflen, "kernel=pm_pair_scan tiles=%d combos=%d fields=2-of-4 x 5 bases window=20 row_slots=%d chunk=%lld nchunks=%d grid=%d block=%d lds=%d schedule=%s",
              (int)h->pair.size(), h->pair[0].ncombos, h->pair[0].stride, (long long)h->geo.seg_len, h->geo.nseg, h->geo.blocks, h->geo.threads, PAIR_LDS_BYTES,
              pair_schedule_name(h->geo));
+    if (h->nlong) {
+      int wide = 0;
+      for (const PairDevice &d : h->pair) wide += d.wide ? 1 : 0;
+      const size_t at = strlen(buf);
+      if (at < buflen) snprintf(buf + at, buflen - at, " with %zu patterns of 33..64 characters (pm_pair_verify_wide, wide tiles=%d)", h->nlong, wide);
+    }
     if (h->nrest) {
       const size_t at = strlen(buf);
       if (at < buflen) snprintf(buf + at, buflen - at, " + %s for %zu patterns the seed plan does not take", bitpar_kernel_name(h->scan_k, h->scan_indels), h->nrest);
@@ -1853,12 +1914,15 @@ static int edits_end_candidates(pm_handle *h, std::vector<pm_hit> *out) {
 // (shift_and_inexact.cc:162-164), so at the very start of the stream a pattern whose first
 // d <= k characters are "missing" is reported at end = L-d with level d + mismatches.  The seed
 // kernel only sees whole windows; these few records are produced here and appended in HBM.
+// The longest pattern of the main class (edge_reach: 32, 64 with long primers on the pair plan) sizes the piece of the
+// stream read; nothing else here depends on the length.
+static int edge_reach(const pm_handle *h) { return h->nlong ? 64 : 32; }
 static int stream_start_candidates(pm_handle *h, std::vector<pm_hit> *out) {
   const int k = h->seed_k;
   EdgeRecords &e = h->edge[EDGE_STREAM_START];
   if (!e.built) {                                                   // same stream, same patterns: computed once (0.3 ms per scan at 200k patterns)
-    const int64_t need = std::min<int64_t>(h->n, 32);
-    uint8_t head[32] = {0};
+    const int64_t need = std::min<int64_t>(h->n, edge_reach(h));
+    uint8_t head[64] = {0};
     { const int rc = host_codes(h, 0, need, head); if (rc) return rc; }
     for (size_t j = 0; j < h->inner.size(); ++j) {
       if (!in_main_class(h, j)) continue;
@@ -1898,14 +1962,17 @@ static int stream_start_candidates(pm_handle *h, std::vector<pm_hit> *out) {
 // pm_seed_extend, which reads code 0 past the end itself.  exact_bases -K is the same with the mandated first
 // block in the left half's place (its records are final: the primer's id, no flag).
 // (All of them end beyond the stream: they go to the range that reaches its end, own_end >= n.)
+// `reach` = edge_reach: the characters of the stream's end that are looked at, as many as the longest pattern has (a
+// pattern of 64 hangs over by up to len2 = 32); nothing else here depends on the length.
 static int stream_end_overhang_candidates(pm_handle *h, bool bases, std::vector<pm_hit> *out) {
   const int k = h->cfg.k;
   const int64_t n = h->n;
   EdgeRecords &e = h->edge[EDGE_OVERHANG];
   if (!e.built) {                                                   // same stream, same patterns: computed once
-    const int64_t need = std::min<int64_t>(n, 32);
-    uint8_t tail[32] = {0};                                         // tail[32 - need .. 32) = the last `need` characters
-    { const int rc = host_codes(h, n - need, need, tail + 32 - need); if (rc) return rc; }
+    const int reach = edge_reach(h);
+    const int64_t need = std::min<int64_t>(n, reach);
+    uint8_t tail[64] = {0};                                         // tail[reach - need .. reach) = the last `need` characters
+    { const int rc = host_codes(h, n - need, need, tail + reach - need); if (rc) return rc; }
     auto differs = [&](unsigned char pc, int code) -> bool {
       if (h->cfg.wildcards) return acgt_of(pc).find((char)h->alpha.ch[code]) == std::string::npos;
       return code != h->alpha.nch[pc];
@@ -1925,7 +1992,7 @@ static int stream_end_overhang_candidates(pm_handle *h, bool bases, std::vector<
           int lvl = 0;
           bool dead = false;
           for (int i = 0; i < L && !dead; ++i) {
-            const int code = i < inside ? (int)tail[32 - inside + i] : 0;
+            const int code = i < inside ? (int)tail[reach - inside + i] : 0;
             if (i < inside && code == h->eos_code) dead = true;
             else if (differs((unsigned char)p.s[i], code)) {
               if (i < len1 || i < es || i >= L - ee) dead = true;   // the seed part is exact; a substitution in an exact zone is a violation
@@ -2114,7 +2181,7 @@ static int scan_wait_once(pm_handle *h, size_t *n_out) {
     return PM_OK;
   }
   std::vector<pm_hit> extra;
-  if (h->kern == PM_KERNEL_SEED && h->own_begin < 32 && h->seed_k > 0 &&
+  if (h->kern == PM_KERNEL_SEED && h->own_begin < edge_reach(h) && h->seed_k > 0 &&
       (h->sem == PM_SEM_FILTER_BITVEC || h->sem == PM_SEM_SHIFT_AND_INEXACT)) {
     const int rc = stream_start_candidates(h, &extra);
     if (rc) return rc;

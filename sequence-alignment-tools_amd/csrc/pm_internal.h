@@ -28,7 +28,7 @@ struct Alphabet {
 };
 
 // Test and measurement knobs (PM_SEED_CHUNK, PM_SEED_GROUP, PM_SEED_DEBUG, PM_SEED_TILE, PM_PAIR, PM_PAIR_ROW, PM_PAIR_MAP, PM_HALF_SCAN,
-// PM_EDIT_SCAN, PM_EDIT_TABLE_LOG, PM_SHORT_SCAN, PM_SHORT_TILE, PM_SHORT_SUB, PM_BITPAR_TP, PM_BITPAR_SEGLEN, PM_DEBUG).  The environment is read ONCE, by
+// PM_EDIT_SCAN, PM_EDIT_TABLE_LOG, PM_SHORT_SCAN, PM_SHORT_TILE, PM_SHORT_SUB, PM_LONG_SUB, PM_BITPAR_TP, PM_BITPAR_SEGLEN, PM_DEBUG).  The environment is read ONCE, by
 // pm_create (pm_api.cpp read_knobs), into the handle: nothing on the init or launch path calls getenv, and a
 // handle's behaviour does not change when its caller's environment does.  Every field's 0 / -1 / false = unset.
 struct Knobs {
@@ -49,6 +49,7 @@ struct Knobs {
   bool short_bitpar = false;         // PM_SHORT_SCAN=bitpar: patterns of 16..19 characters go to the bit-parallel residue, not to pm_short_edit_scan
   long short_tile = 0;               // PM_SHORT_TILE: patterns per tile of pm_short_edit_scan / pm_short_sub_scan
   bool short_sub_off = false;        // PM_SHORT_SUB=off: -K lists with patterns of 16..19 characters leave the pair plan as a whole (A/B runs, tests)
+  bool long_sub_off = false;         // PM_LONG_SUB=off: -K patterns of 33..64 characters stay off the pair plan whatever pm_config.long_patterns says (A/B runs, tests)
   bool debug = false;                // PM_DEBUG: stage timings on stderr
 };
 
@@ -152,6 +153,7 @@ hipError_t halves_rule_device(const pm_hit *d_in, size_t n, bool flags, int slac
 
 // ---- the caller's re-alignment and tally on the device (pm_align.hip) ----------------------------
 constexpr int AL_MAXL = 32, AL_MAXK = 3;         // device limit of the edit-distance DP; longer patterns are aligned by the host
+constexpr int AL_MAXL_SUB = 64;                  // ... but for -K (no indels: the DP is one diagonal), which the device walks up to this length
 constexpr int AL_THREADS = 64;                   // one wave per block: every lane owns a column of the block's LDS
 constexpr uint64_t TALLY_INVALID = ~0ull;        // tally key of a record the device did not align
 constexpr int TALLY_BOGUS = 4;                   // distance code of a hit that re-aligns to more than k (or to a violation)

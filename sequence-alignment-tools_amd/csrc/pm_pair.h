@@ -1,6 +1,7 @@
 // pm_pair.h -- "pair plan" scan kernel (pm_pair.hip): host tables and launch interface.
 //
-// Substitution-only candidates (-K 1, -K 2) of 20..32 character A,C,G,T patterns.  The last 20
+// Substitution-only candidates (-K 1, -K 2) of 20..32 character A,C,G,T patterns -- 20..64 in a wide tile, whose exact
+// stage reads rows of 64 characters (pm_pair_verify_wide); the scan looks at the last 20 only.  The last 20
 // bases of a pattern are cut into four fields of five bases (10 bits of the 2-bit packed window);
 // <= 2 substitutions leave two fields untouched (<= 1: the first two or the last two), so every
 // candidate agrees with its pattern on one of the C(4,2) = 6 field pairs (2 for k = 1).  A pair of
@@ -30,6 +31,7 @@ constexpr int PAIR_XCD_MIN_CHUNKS = 5 * 256;        // chunks from which pair_ge
 struct PairTables {                                 // one pattern tile
   int k = 0, maxlen = 0, ncombos = 0, eos_code = -1, stride = 0;
   bool ascii = false;
+  bool wide = false;                                // the tile holds a pattern of 33..64 characters: rows of 64 characters, zones of 64 bits
   int fa[PAIR_MAX_COMBOS] = {}, fb[PAIR_MAX_COMBOS] = {};   // key fields of every combo (a < b), the other two are (c < d)
   std::vector<uint32_t> image;                      // [combo][PAIR_BITMAP_WORDS]
   std::vector<uint64_t> slots;                      // [combo][PAIR_BITMAP_WORDS * stride]: slot (row, rank of the key inside its row), see pm_pair.hip slot_pack
@@ -41,13 +43,14 @@ struct PairTables {                                 // one pattern tile
   std::vector<uint64_t> pat40;                      // last 20 bases, 2 bits each
   std::vector<uint8_t> pat_len;
   std::vector<uint32_t> pat_id;
-  std::vector<uint8_t> pat_codes;                   // 32 stream codes per pattern
-  std::vector<uint32_t> pat_zone;                   // bit i: pattern character i lies in an exact zone
+  std::vector<uint8_t> pat_codes;                   // 32 stream codes per pattern (wide: 64), zero padded
+  std::vector<uint32_t> pat_zone;                   // bit i: pattern character i lies in an exact zone (wide: two dwords per pattern, the low one first)
 };
 
 struct PairDevice {
   int k = 0, maxlen = 0, ncombos = 0, eos_code = -1, stride = 0;
   bool ascii = false;
+  bool wide = false;                                  // see PairTables::wide: pair_launch runs pm_pair_verify_wide for this tile
   int fa[PAIR_MAX_COMBOS] = {}, fb[PAIR_MAX_COMBOS] = {};
   size_t first_off[PAIR_MAX_COMBOS] = {};
   size_t np = 0;
@@ -62,8 +65,11 @@ struct PairDevice {
 
 // "" or why the plan does not take this pattern set
 // stride_knob: slots per row of the slot table (0 = default)
+// max_len: the longest pattern the caller lets onto the plan, 32 or 64 (PAIR_MAX_LEN_WIDE); a tile with a pattern beyond 32
+// characters is a wide tile, any other is built as with max_len = 32
+constexpr int PAIR_MAX_LEN = 32, PAIR_MAX_LEN_WIDE = 64;
 std::string pair_build(const std::vector<Pattern> &pats, const std::vector<uint32_t> &ids, const Alphabet &alpha, int k,
-                       int eos_code, PairTables *out, int stride_knob = 0, int slot_patterns = 3);
+                       int eos_code, PairTables *out, int stride_knob = 0, int slot_patterns = 3, int max_len = PAIR_MAX_LEN);
 hipError_t pair_upload(const PairTables &t, PairDevice *d, hipStream_t st);
 void pair_free(PairDevice *d);
 ScanGeometry pair_geometry(const PairDevice &d, int64_t begin, int64_t end);

@@ -93,8 +93,8 @@ struct PairArgs {
   const uint2 *pat40;
   const uint8_t *pat_len;
   const uint32_t *pat_id;
-  const uint8_t *pat_codes;
-  const uint32_t *pat_zone;             // per pattern: bit i = character i lies in an exact zone (exact_start_bases / exact_end_bases)
+  const uint8_t *pat_codes;             // 32 stream codes per pattern; 64 in a wide tile (pm_pair_verify_wide)
+  const uint32_t *pat_zone;             // per pattern: bit i = character i lies in an exact zone (exact_start_bases / exact_end_bases); two dwords in a wide tile
   int viol_level;                       // a mismatch inside an exact zone: > 0 = report the candidate with this level (filter_bitvec
                                         // chains every candidate and verifies the chain), 0 = not a candidate (exact_halves, exact_bases)
   pm_hit *out;
@@ -286,6 +286,7 @@ __device__ __host__ __forceinline__ int edit_variant_table(int var) { return var
 // A suspect: a window whose slot says "within k on the other fields" for the key's first / second /
 // third pattern (what & 1, 2, 4), that the key has more than three (WHAT_REST: walk the rest of the
 // key's run of the sorted pattern list), or whose key has no slot (WHAT_ALL: walk the whole run).
+template <int CW>
 __device__ __forceinline__ void pair_resolve(const PairArgs &a, const VerifyStage &vs, int combo, uint32_t rank, uint32_t what, uint32_t wo, int64_t p, pm_hit *first, bool *have) {
   const uint32_t *fp = a.first_pat + a.first_off[combo];
   const uint32_t *ord = a.order + (size_t)combo * a.np;
@@ -300,13 +301,13 @@ __device__ __forceinline__ void pair_resolve(const PairArgs &a, const VerifyStag
     pair_emit(a, vs, extra, hh);
   };
   for (uint32_t j = 0; j < 3; ++j)
-    take(((what >> j) & 1u) && t0 + j < t1 && pair_verify<5>(a, combo, p, ord[t0 + j], &hh));   // (free slot fields repeat the first pattern)
+    take(((what >> j) & 1u) && t0 + j < t1 && pair_verify<5, CW>(a, combo, p, ord[t0 + j], &hh));   // (free slot fields repeat the first pattern)
   if (what & (WHAT_REST | WHAT_ALL)) {
     // the rest of the key's run: its patterns' other fields lie next to each other (one or two cache lines for a run of
     // twenty; ord[] -> pat40[] was two dependent random loads per pattern -- keys shared by many primers are what a
     // skewed stream with primers cut from it is made of)
     for (uint32_t t = t0 + ((what & WHAT_ALL) ? 0u : 3u); t < t1; ++t)
-      take(sym_distance(ol[t] ^ wo) <= a.k && pair_verify<5>(a, combo, p, ord[t], &hh));
+      take(sym_distance(ol[t] ^ wo) <= a.k && pair_verify<5, CW>(a, combo, p, ord[t], &hh));
   }
 }
 
@@ -316,7 +317,10 @@ __device__ __forceinline__ void pair_resolve(const PairArgs &a, const VerifyStag
 // wave and held the wave for microseconds.  The records leave block by block: one atomic on the shared counter per
 // 256 suspects -- one per wave and emit call, 10^5 to 10^6 per launch on one address at ~2 ns each, was 1.7 of
 // this kernel's 2.0 ms.
-__global__ __launch_bounds__(256) void pm_pair_verify(PairArgs a) {
+// CW = characters per row of the tile's pat_codes: 32 (pm_pair_verify), 64 (pm_pair_verify_wide: a tile with patterns of
+// 33..64 characters).  Everything in front of the exact stage -- rank, slot, the key's run -- reads the last 20 bases only.
+template <int CW>
+__device__ __forceinline__ void pair_verify_body(const PairArgs &a) {
   unsigned long long n = *a.susp_count;
   if (n > a.susp_cap) n = a.susp_cap;
   verify_staged(a, n, [&](unsigned long long i, const VerifyStage &vs, pm_hit *first) __attribute__((always_inline)) {
@@ -338,12 +342,14 @@ __global__ __launch_bounds__(256) void pm_pair_verify(PairArgs a) {
           what = (sym_distance(((uint32_t)S ^ wo) & F20) <= a.k ? 1u : 0u) | (sym_distance(((uint32_t)(S >> 20) ^ wo) & F20) <= a.k ? 2u : 0u) |
                  (sym_distance(((uint32_t)(S >> 40) ^ wo) & F20) <= a.k ? 4u : 0u) | ((sl.y >> 31) ? WHAT_REST : 0u);
         }
-        pair_resolve(a, vs, combo, rank, what, wo, (int64_t)(pw & 0xffffffffffull), first, &have);
+        pair_resolve<CW>(a, vs, combo, rank, what, wo, (int64_t)(pw & 0xffffffffffull), first, &have);
       }
     }
     return have && !(a.debug & 16);
   });
 }
+__global__ __launch_bounds__(256) void pm_pair_verify(PairArgs a) { pair_verify_body<32>(a); }
+__global__ __launch_bounds__(256) void pm_pair_verify_wide(PairArgs a) { pair_verify_body<64>(a); }
 
 // One (field pair, chunk) of the scan.  A, B: key fields (compile time: every window offset of pass A is an
 // immediate).  Per block of 1024 positions (16 per lane) a wave runs pass A -- the 16 membership tests of every
@@ -840,7 +846,7 @@ __global__ __launch_bounds__(256) void pm_pair_edit_resolve(PairArgs a) {
 // ---- host side: tables, launch -------------------------------------------------------------------
 
 std::string pair_build(const std::vector<Pattern> &pats, const std::vector<uint32_t> &ids, const Alphabet &alpha, int k,
-                       int eos_code, PairTables *out, int stride_knob, int slot_patterns) {
+                       int eos_code, PairTables *out, int stride_knob, int slot_patterns, int max_len) {
   const size_t SP = slot_patterns == 2 ? 2 : 3;                     // patterns a slot settles (the edit plan compares two: its compare is three times the substitution plan's)
   PairTables &t = *out;
   t = PairTables();
@@ -859,11 +865,17 @@ std::string pair_build(const std::vector<Pattern> &pats, const std::vector<uint3
   const size_t np = pats.size();
   if (np == 0) return "no patterns";
   if (np >= ((size_t)1 << 30)) return "too many patterns";
-  t.pat40.resize(np); t.pat_len.resize(np); t.pat_id.resize(np); t.pat_codes.assign(np * 32, 0); t.pat_zone.assign(np, 0);
+  if (max_len != PAIR_MAX_LEN && max_len != PAIR_MAX_LEN_WIDE) return "the pair plan is built for patterns of up to 32 or up to 64 characters";
+  for (size_t j = 0; j < np; ++j) {
+    const int L = (int)pats[j].s.size();
+    if (L < 20 || L > max_len) return max_len > PAIR_MAX_LEN ? "the pair plan needs patterns of 20..64 characters" : "the pair plan needs patterns of 20..32 characters";
+    t.wide = t.wide || L > PAIR_MAX_LEN;
+  }
+  const size_t CW = t.wide ? 64 : 32;                               // characters per row of pat_codes, bits of a zone
+  t.pat40.resize(np); t.pat_len.resize(np); t.pat_id.resize(np); t.pat_codes.assign(np * CW, 0); t.pat_zone.assign(np * (CW / 32), 0);
   for (size_t j = 0; j < np; ++j) {
     const std::string &s = pats[j].s;
     const int L = (int)s.size();
-    if (L < 20 || L > 32) return "the pair plan needs patterns of 20..32 characters";
     uint64_t w = 0;
     for (int i = 0; i < 20; ++i) {
       const int b2 = base2((unsigned char)s[L - 20 + i]);
@@ -872,14 +884,15 @@ std::string pair_build(const std::vector<Pattern> &pats, const std::vector<uint3
     }
     for (int i = 0; i < L; ++i) {
       if (base2((unsigned char)s[i]) < 0) return "pattern with characters other than A,C,G,T";
-      t.pat_codes[j * 32 + i] = (uint8_t)alpha.nch[(unsigned char)s[i]];
+      t.pat_codes[j * CW + i] = (uint8_t)alpha.nch[(unsigned char)s[i]];
     }
     t.pat40[j] = w; t.pat_len[j] = (uint8_t)L; t.pat_id[j] = ids[j];
     {
       const int es = std::max(0, std::min(L, pats[j].esb)), ee = std::max(0, std::min(L, pats[j].eeb));
-      uint32_t z = 0;
-      for (int i = 0; i < L; ++i) if (i < es || i >= L - ee) z |= 1u << i;
-      t.pat_zone[j] = z;
+      uint64_t z = 0;
+      for (int i = 0; i < L; ++i) if (i < es || i >= L - ee) z |= 1ull << i;
+      t.pat_zone[j * (CW / 32)] = (uint32_t)z;
+      if (t.wide) t.pat_zone[j * 2 + 1] = (uint32_t)(z >> 32);
     }
     t.maxlen = std::max(t.maxlen, L);
   }
@@ -959,7 +972,7 @@ std::string pair_build(const std::vector<Pattern> &pats, const std::vector<uint3
 
 hipError_t pair_upload(const PairTables &t, PairDevice *d, hipStream_t st) {
   pair_free(d);
-  d->k = t.k; d->maxlen = t.maxlen; d->ncombos = t.ncombos; d->eos_code = t.eos_code; d->ascii = t.ascii; d->np = t.pat40.size(); d->stride = t.stride;
+  d->k = t.k; d->maxlen = t.maxlen; d->ncombos = t.ncombos; d->eos_code = t.eos_code; d->ascii = t.ascii; d->wide = t.wide; d->np = t.pat40.size(); d->stride = t.stride;
   for (int c = 0; c < PAIR_MAX_COMBOS; ++c) { d->fa[c] = t.fa[c]; d->fb[c] = t.fb[c]; d->first_off[c] = t.first_off[c]; }
   auto up = [&](const void *src, size_t bytes, void **dst) -> hipError_t {
     hipError_t e = hipMalloc(dst, bytes ? bytes : 16);
@@ -1075,7 +1088,9 @@ hipError_t pair_launch(const PairDevice &d, const uint8_t *d_text, const uint32_
   if (ce != hipSuccess) return ce;
   // one suspect per thread for up to 8 Mi of them (the count is on the device): the verify is a chain of ~8 dependent
   // table and stream reads per suspect; six suspects per thread one after the other made every wave live 0.9 ms
-  hipLaunchKernelGGL(pm_pair_verify, dim3(32768), dim3(256), 0, st, a);
+  // (a wide tile -- one with a pattern of 33..64 characters -- through the exact stage on rows of 64 characters)
+  if (d.wide) hipLaunchKernelGGL(pm_pair_verify_wide, dim3(32768), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(pm_pair_verify, dim3(32768), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 

@@ -32,59 +32,77 @@ PM_VFN int pop32(uint32_t x) {
 // substitutions between two strings of 2-bit symbols
 PM_VFN int sym_distance(uint32_t x) { return pop32((x | (x >> 1)) & 0x55555555u); }
 
+// the per-character verdicts of a window of CW characters: one bit each
+template <int CW> struct verify_mask { typedef uint32_t type; };
+template <> struct verify_mask<64> { typedef uint64_t type; };
+PM_VFN int pop_mask(uint32_t x) { return pop32(x); }
+PM_VFN int pop_mask(uint64_t x) { return pop32((uint32_t)x) + pop32((uint32_t)(x >> 32)); }
+
 // Exact part of the verify (second kernel): (window ending at p, pattern pi) agree on this combo's key
 // and are within k substitutions on the rest of the packed window; count mismatches on the raw stream
 // codes over the whole pattern (N = mismatch, EOS = reject) and report -- once: only through the first
 // combo of the plan whose two fields are clean.
-// FW = bases per field: the plan looks at the pattern's last 4 * FW bases.  Args: the kernel's argument block (text, n, k,
-// eos_code, ncombos, fa, fb, pat_len, pat_id, pat_codes, pat_zone, viol_level).
+// FW = bases per field: the plan looks at the pattern's last 4 * FW bases.  CW = characters a pattern's row of pat_codes
+// holds, 32 or 64 (a wide tile of the pair plan, patterns of up to 64 characters: DESIGN.md 4.9): the verdicts are CW bits,
+// and a row of pat_zone is CW / 32 dwords, low dword first.  Args: the kernel's argument block (text, n, k, eos_code,
+// ncombos, fa, fb, pat_len, pat_id, pat_codes, pat_zone, viol_level).
 // Returns whether (p, pi) is a candidate this combo reports; *hh is then its record.
-template <int FW, typename Args>
+template <int FW, int CW = 32, typename Args>
 PM_VFN bool pair_verify(const Args &a, int combo, int64_t p, uint32_t pi, pm_hit *hh) {
   static_assert(FW == 4 || FW == 5, "fields of four or five bases");
+  static_assert(CW == 32 || CW == 64, "rows of 32 or 64 characters");
+  typedef typename verify_mask<CW>::type mask_t;
+  constexpr int NW = CW / 4, NV = CW / 16;                          // dwords, 16-byte loads of a row
   const int L = a.pat_len[pi];
   const int64_t start = p + 1 - L;
   if (start < 0) return false;
-  // all 32 pattern codes and the 32 stream bytes from `start` at once (every load independent of the
+  // all CW pattern codes and the CW stream bytes from `start` at once (every load independent of the
   // others: this kernel is a chain of dependent loads as it is), per-byte verdicts by SWAR
-  const uint4 *pcv = reinterpret_cast<const uint4 *>(a.pat_codes + (size_t)pi * 32);
-  const uint4 pc0 = pcv[0], pc1 = pcv[1];
-  uint32_t tw[8];
-  if (start + 32 <= a.n) {
-    uint4 t0, t1;
-    __builtin_memcpy(&t0, a.text + start, 16);
-    __builtin_memcpy(&t1, a.text + start + 16, 16);
-    tw[0] = t0.x; tw[1] = t0.y; tw[2] = t0.z; tw[3] = t0.w; tw[4] = t1.x; tw[5] = t1.y; tw[6] = t1.z; tw[7] = t1.w;
-  } else {                                            // the last bytes of the stream
+  const uint4 *pcv = reinterpret_cast<const uint4 *>(a.pat_codes + (size_t)pi * CW);
+  uint4 pc[NV];
 #pragma unroll
-    for (int d = 0; d < 8; ++d) {
+  for (int v = 0; v < NV; ++v) pc[v] = pcv[v];
+  uint32_t tw[NW];
+  if (start + CW <= a.n) {
+    uint4 t[NV];
+#pragma unroll
+    for (int v = 0; v < NV; ++v) __builtin_memcpy(&t[v], a.text + start + 16 * v, 16);
+#pragma unroll
+    for (int v = 0; v < NV; ++v) { tw[4 * v] = t[v].x; tw[4 * v + 1] = t[v].y; tw[4 * v + 2] = t[v].z; tw[4 * v + 3] = t[v].w; }
+  } else {                                            // the last bytes of the stream (a pattern shorter than its row: often)
+#pragma unroll
+    for (int d = 0; d < NW; ++d) {
       tw[d] = 0;
       for (int b = 0; b < 4; ++b) { const int64_t q = start + 4 * d + b; if (q < a.n) tw[d] |= (uint32_t)a.text[q] << (8 * b); }
     }
   }
-  const uint32_t pcw[8] = {pc0.x, pc0.y, pc0.z, pc0.w, pc1.x, pc1.y, pc1.z, pc1.w};
-  const uint32_t eb = (uint32_t)(a.eos_code & 0xff) * 0x01010101u;
-  uint32_t mism = 0, eos = 0;                         // bit i: stream byte i differs from the pattern / is EOS
+  uint32_t pcw[NW];
 #pragma unroll
-  for (int d = 0; d < 8; ++d) {
+  for (int v = 0; v < NV; ++v) { pcw[4 * v] = pc[v].x; pcw[4 * v + 1] = pc[v].y; pcw[4 * v + 2] = pc[v].z; pcw[4 * v + 3] = pc[v].w; }
+  const uint32_t eb = (uint32_t)(a.eos_code & 0xff) * 0x01010101u;
+  mask_t mism = 0, eos = 0;                           // bit i: stream byte i differs from the pattern / is EOS
+#pragma unroll
+  for (int d = 0; d < NW; ++d) {
     const uint32_t x = tw[d] ^ pcw[d], z = tw[d] ^ eb;
     const uint32_t y = (x | ((x & 0x7f7f7f7fu) + 0x7f7f7f7fu)) & 0x80808080u;
     const uint32_t e = ~(z | ((z & 0x7f7f7f7fu) + 0x7f7f7f7fu)) & 0x80808080u;
-    mism |= (((y >> 7) & 1u) | ((y >> 14) & 2u) | ((y >> 21) & 4u) | ((y >> 28) & 8u)) << (4 * d);
-    eos |= (((e >> 7) & 1u) | ((e >> 14) & 2u) | ((e >> 21) & 4u) | ((e >> 28) & 8u)) << (4 * d);
+    mism |= (mask_t)(((y >> 7) & 1u) | ((y >> 14) & 2u) | ((y >> 21) & 4u) | ((y >> 28) & 8u)) << (4 * d);
+    eos |= (mask_t)(((e >> 7) & 1u) | ((e >> 14) & 2u) | ((e >> 21) & 4u) | ((e >> 28) & 8u)) << (4 * d);
   }
-  const uint32_t lenmask = L >= 32 ? 0xffffffffu : ((1u << L) - 1u);
+  const mask_t lenmask = L >= CW ? ~(mask_t)0 : (((mask_t)1 << L) - 1u);   // (a shift by the mask's width is undefined)
   mism &= lenmask;
   if (a.eos_code >= 0 && (eos & lenmask)) return false;   // EOS inside the window: never a candidate
-  int ham = pop32(mism);                              // N (or any other code) = mismatch
+  int ham = pop_mask(mism);                           // N (or any other code) = mismatch
   if (ham > a.k) return false;
   // exact-base constraints (pattern_alignment.cc:320-323: a substitution inside an exact zone is a
   // constraint violation, the verify fails)
-  if (mism & a.pat_zone[pi]) {
+  mask_t zone = a.pat_zone[(size_t)pi * (CW / 32)];
+  if (CW == 64) zone |= (mask_t)((uint64_t)a.pat_zone[(size_t)pi * (CW / 32) + (CW / 32 - 1)] << (CW - 32));
+  if (mism & zone) {
     if (a.viol_level <= 0) return false;
     ham = a.viol_level;
   }
-  const uint32_t tail = mism >> (L - 4 * FW);         // the bases the plan looks at
+  const uint32_t tail = (uint32_t)(mism >> (L - 4 * FW));   // the bases the plan looks at
   uint32_t dirty = 0;
 #pragma unroll
   for (int j = 0; j < 4; ++j) if ((tail >> (FW * j)) & ((1u << FW) - 1u)) dirty |= 1u << j;
@@ -92,8 +110,8 @@ PM_VFN bool pair_verify(const Args &a, int combo, int64_t p, uint32_t pi, pm_hit
   for (int c = 0; c < a.ncombos && first < 0; ++c)
     if (!((dirty >> a.fa[c]) & 1u) && !((dirty >> a.fb[c]) & 1u)) first = c;
   if (first != combo) return false;
-  const int half = L / 2;
-  const bool left_clean = (mism & ((1u << half) - 1u)) == 0, right_clean = (mism >> half) == 0;
+  const int half = L / 2;                             // (<= 32 < the width of a 64-bit mask)
+  const bool left_clean = (mism & (((mask_t)1 << half) - 1u)) == 0, right_clean = (mism >> half) == 0;
   hh->end = p + 1; hh->pid = a.pat_id[pi]; hh->k = (uint8_t)ham;
   hh->aux[0] = (uint8_t)((left_clean ? 1 : 0) | (right_clean ? 2 : 0)); hh->aux[1] = hh->aux[2] = 0;
   return true;

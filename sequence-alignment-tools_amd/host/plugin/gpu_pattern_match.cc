@@ -32,6 +32,8 @@ gpu_pattern_match::gpu_pattern_match(int kernel, unsigned int k, char eos, bool 
   cfg.text_n = tn ? 1 : 0;
   cfg.eos = (unsigned char)eos;
   if (const char *dev = getenv("PM_GPU_DEVICE")) cfg.device = atoi(dev);
+  // PM_GPU_LONG=1: -K 1 / -K 2 primers of 33..64 nt may run on the pair plan (pm_config.long_patterns; default off)
+  if (const char *lp = getenv("PM_GPU_LONG")) cfg.long_patterns = atoi(lp) == 1 ? 1 : 0;
   device_ = cfg.device;
   if (pm_create(&cfg, &h_) != PM_OK) {
     std::string msg = std::string("Fatal error: ") + pm_last_error(0);

@@ -52,7 +52,7 @@ class _CountInfo(C.Structure):
 class _Config(C.Structure):
     _fields_ = [("abi_version", C.c_int32), ("semantics", C.c_int32), ("kernel", C.c_int32), ("k", C.c_int32),
                 ("indels", C.c_int32), ("wildcards", C.c_int32), ("text_n", C.c_int32), ("eos", C.c_int32),
-                ("device", C.c_int32), ("reserved", C.c_int32 * 7)]
+                ("device", C.c_int32), ("long_patterns", C.c_int32), ("reserved", C.c_int32 * 6)]
 
 
 def library_path():
@@ -201,16 +201,18 @@ class PatternMatch:
     k / indels / eos follow pick_pattern_index's arguments (select.cc:19-30): indels=True is the
     CLI's -k (edits), False is -K (substitutions only).  `semantics` forces a reference engine
     (-N), SEM_AUTO reproduces the automatic choice; `kernel` picks the GPU kernel family.
+    long_patterns=True lets -K 1 / -K 2 patterns of 33..64 characters run on the pair plan (pm_config.long_patterns).
     """
 
     def __init__(self, k=0, indels=True, eos="\n", semantics=SEM_AUTO, kernel=KERNEL_AUTO, device=0,
-                 wildcards=False, text_n=False):
+                 wildcards=False, text_n=False, long_patterns=False):
         self._L = load_library()
         cfg = _Config()
         cfg.abi_version, cfg.semantics, cfg.kernel, cfg.k = 1, semantics, kernel, k
         cfg.indels, cfg.wildcards, cfg.text_n = int(bool(indels)), int(bool(wildcards)), int(bool(text_n))
         cfg.eos = ord(eos) if isinstance(eos, str) else int(eos)
         cfg.device = device
+        cfg.long_patterns = int(bool(long_patterns))
         self._h = C.c_void_p()
         rc = self._L.pm_create(C.byref(cfg), C.byref(self._h))
         if rc:
