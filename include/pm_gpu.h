@@ -73,9 +73,14 @@ typedef enum {
                               plans, 16..19 on pm_short_edit_scan).  Under PM_KERNEL_AUTO a -K 1 / -K 2 list of 20..32
                               and 16..19 nt patterns runs on the pair plan and pm_short_sub_scan side by side; asked
                               for by name, this family keeps such a list on one plan, the Bloom plan.  Patterns of
-                              33..64 nt join the pair plan under PM_KERNEL_AUTO where pm_config.long_patterns allows
-                              it; asked for by name, this family refuses them as before */
+                              33..64 nt join the pair plan (-K 1 / -K 2) or, at k = 0, the Bloom plan under
+                              PM_KERNEL_AUTO where pm_config.long_patterns allows it; asked for by name, this family
+                              refuses them as before */
 } pm_kernel;
+
+/* bits of pm_config.long_patterns */
+#define PM_LONG_SUB   1    /* -K 1 / -K 2: patterns of 33..64 characters may run on the pair plan */
+#define PM_LONG_EXACT 2    /* k = 0: patterns of 33..64 characters may run on the seed (Bloom) plan */
 
 /* Replaces the constructor arguments of the reference engines as pick_pattern_index passes them
  * (select.cc:19-30): nmismatch, indels, wildcard, textn, eos.  dna_mut is not supported. */
@@ -89,13 +94,19 @@ typedef struct {
   int32_t text_n;          /* -W: a text N also matches (shift_and.cc:112) */
   int32_t eos;             /* raw end-of-sequence char, '\n' in the CLIs */
   int32_t device;          /* HIP device ordinal */
-  int32_t long_patterns;   /* 1 = with PM_KERNEL_AUTO, -K 1 / -K 2 (substitutions only) and filter_bitvec, bare
+  int32_t long_patterns;   /* a bit set (PM_LONG_SUB | PM_LONG_EXACT; 0 = the routing of earlier versions).
+                              PM_LONG_SUB (1) = with PM_KERNEL_AUTO, -K 1 / -K 2 (substitutions only) and filter_bitvec, bare
                               shift_and_inexact or exact_halves on an A,C,G,T-normalized or raw ASCII stream, patterns
                               of 33..64 characters (A,C,G,T; or <= 16 concrete variants under -w on a plain stream)
                               run on the pair plan beside those of 20..32: the scan reads their last 20 bases, the
-                              exact stage rows of 64 characters (pm_pair_verify_wide).  0 = they go to the bit-parallel
-                              kernels, as does every pattern of 65 characters or more either way.  (Took the place of
-                              reserved[0]: same layout, same PM_ABI_VERSION, 0 = the routing of earlier versions.) */
+                              exact stage rows of 64 characters (pm_pair_verify_wide).
+                              PM_LONG_EXACT (2) = with PM_KERNEL_AUTO, k = 0 and keyword_tree or shift_and on such a
+                              stream, patterns of 33..64 characters (same conditions) run on the Bloom plan beside
+                              those of 10..32: pm_seed_scan reads their last 20 bases (or as many as the list's
+                              shortest pattern has), the exact stage rows of 64 characters (wide tiles).
+                              A bit not set = they go to the bit-parallel kernels, as does every pattern of 65
+                              characters or more either way.  Each bit acts on its own option sets only.  (Took the
+                              place of reserved[0]: same layout, same PM_ABI_VERSION.) */
   int32_t reserved[6];
 } pm_config;
 

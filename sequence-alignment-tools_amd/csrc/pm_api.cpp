@@ -187,6 +187,7 @@ struct pm_handle {
   void *d_htemp = nullptr;
   size_t vals_cap = 0, htemp_bytes = 0;
   size_t nlong = 0;                   // patterns of 33..64 characters on the pair plan (pm_config.long_patterns); 0: no pattern beyond 32 on the seed family
+  size_t nlong_exact = 0;             // patterns of 33..64 characters on the Bloom plan at k = 0 (PM_LONG_EXACT bit of pm_config.long_patterns): wide tiles of pm_seed_scan
   std::vector<uint8_t> in_rest;       // per inner pattern: 1 = scanned by the bit-parallel residue engine beside the seed family
   size_t nrest = 0;
   // edit-distance plan, patterns of 16..19 characters: a class of their own beside the 20..32 character main class and the
@@ -416,6 +417,7 @@ static void read_knobs(Knobs *k) {
   k->short_bitpar = is("PM_SHORT_SCAN", "bitpar"); k->short_tile = (long)num("PM_SHORT_TILE");
   k->short_sub_off = is("PM_SHORT_SUB", "off");
   k->long_sub_off = is("PM_LONG_SUB", "off");
+  k->long_exact_off = is("PM_LONG_EXACT", "off");
   k->debug = getenv("PM_DEBUG") != nullptr;
 }
 
@@ -698,9 +700,21 @@ static bool stream_for_pair_plan(const pm_handle *h) {
 // takes.  Anything else, PM_LONG_SUB=off included, leaves every handle as it was built before the route existed.
 // Called with wild_seed decided.
 static bool long_route_allowed(const pm_handle *h) {
-  if (!h->cfg.long_patterns || h->knobs.long_sub_off || h->knobs.pair == 0 || h->kern != PM_KERNEL_AUTO) return false;
+  if (!(h->cfg.long_patterns & PM_LONG_SUB) || h->knobs.long_sub_off || h->knobs.pair == 0 || h->kern != PM_KERNEL_AUTO) return false;
   if (h->cfg.indels || (h->cfg.k != 1 && h->cfg.k != 2)) return false;
   if (h->sem != PM_SEM_FILTER_BITVEC && h->sem != PM_SEM_SHIFT_AND_INEXACT && h->sem != PM_SEM_EXACT_HALVES) return false;
+  if (h->cfg.wildcards && !h->wild_seed) return false;
+  return stream_for_pair_plan(h);
+}
+
+// k = 0 with primers of 33..64 characters: the caller allows them on the Bloom plan (the PM_LONG_EXACT
+// bit of pm_config.long_patterns), the engine is one whose records verify_exact makes as they are -- keyword_tree or
+// shift_and at k = 0 -- no kernel is asked for by name and the stream is one seed_build takes (the pair plan's
+// condition).  Anything else, PM_LONG_EXACT=off included, leaves every handle as it was built before the route existed.
+// Called with wild_seed decided.
+static bool long_exact_allowed(const pm_handle *h) {
+  if (!(h->cfg.long_patterns & PM_LONG_EXACT) || h->knobs.long_exact_off || h->kern != PM_KERNEL_AUTO) return false;
+  if (h->cfg.k != 0 || (h->sem != PM_SEM_KEYWORD_TREE && h->sem != PM_SEM_SHIFT_AND)) return false;
   if (h->cfg.wildcards && !h->wild_seed) return false;
   return stream_for_pair_plan(h);
 }
@@ -827,7 +841,7 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
   bool want_seed = h->kern == PM_KERNEL_SEED || h->kern == PM_KERNEL_AUTO;
   h->wild_seed = h->cfg.wildcards && want_seed && h->kern == PM_KERNEL_AUTO && stream_letters_plain(h) &&
                  (h->sem == PM_SEM_KEYWORD_TREE || h->sem == PM_SEM_SHIFT_AND || h->sem == PM_SEM_FILTER_BITVEC);
-  h->nlong = 0;
+  h->nlong = 0; h->nlong_exact = 0;
   bool any_long = false;                                            // (a list without a primer of 33..64 is classified once, as without the flag)
   for (const Pattern &p : h->pats) any_long = any_long || (p.s.size() > 32 && p.s.size() <= 64);
   if (any_long && long_route_allowed(h)) {
@@ -847,8 +861,25 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
     }
     if (nlong && pair_takes) h->nlong = nlong;
   }
-  if (!h->nlong) classify_patterns(h, want_seed, 32);
-  else if (h->knobs.debug) fprintf(stderr, "[pm] long route: %zu patterns of 33..64 characters on the pair plan\n", h->nlong);
+  else if (any_long && long_exact_allowed(h)) {
+    // k = 0: a primer of 33..64 characters is a main-class primer under the rule of 10..32 (A,C,G,T only, or <= 16 concrete
+    // variants under -w on a plain stream).  Kept only if the main class then holds such a primer; a list whose long primers
+    // are all residue anyway is classified as without the route.
+    classify_patterns(h, want_seed, 64);
+    size_t nlong = 0;
+    std::vector<std::string> variants;
+    for (size_t i = 0; i < h->inner.size(); ++i) {
+      const std::string &ps = h->inner[i].s;
+      if (ps.size() <= 32 || ps.size() > 64 || (i < h->in_rest.size() && h->in_rest[i])) continue;
+      bool ok = true;                                               // (classify_patterns clears in_rest when nothing is left for the main class)
+      if (h->wild_seed) ok = expand_iupac(ps, 16, &variants);
+      else for (unsigned char ch : ps) ok = ok && (ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T');
+      if (ok) ++nlong;
+    }
+    h->nlong_exact = nlong;
+  }
+  if (!h->nlong && !h->nlong_exact) classify_patterns(h, want_seed, 32);
+  else if (h->knobs.debug) fprintf(stderr, "[pm] long route: %zu patterns of 33..64 characters on the %s plan\n", h->nlong + h->nlong_exact, h->nlong ? "pair" : "seed");
   if (want_seed && !seed_eligible(h, &why)) {
     if (h->kern == PM_KERNEL_SEED) return fail(h, PM_E_UNSUPPORTED, "seed engine: " + why);
     want_seed = false;
@@ -953,7 +984,7 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
       if (halves_mode) { tpart.assign(partners.begin() + lo, partners.begin() + hi); tside.assign(sides.begin() + lo, sides.begin() + hi); }
       SeedTables st;
       why = seed_build(tp, tid, h->alpha, sk, h->eos_code, &st, force_lw, halves_mode ? &tpart : nullptr,
-                       halves_mode ? &tside : nullptr, h->cfg.k, edits_mode, h->knobs);
+                       halves_mode ? &tside : nullptr, h->cfg.k, edits_mode, h->knobs, h->nlong_exact ? SEED_MAX_LEN_WIDE : SEED_MAX_LEN);
       if (why.empty() && h->kern == PM_KERNEL_AUTO && st.Lw < (halves_mode ? 8 : 10)) why = "patterns too short for the seed family";
       if (!why.empty()) break;
       SeedDevice *dst = &h->sd;
@@ -1061,6 +1092,7 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
     }
   }
   if (!want_seed) {
+    h->nlong_exact = 0;                                             // (no wide tile was kept: the stream edges and pm_describe are the bit-parallel family's)
     h->halves_dev = false; h->edits_dev = false; h->half_ranked_any = false;
     std::fill(h->in_rest.begin(), h->in_rest.end(), 0); h->nrest = 0;
     std::fill(h->in_short.begin(), h->in_short.end(), 0); h->nshort = 0; h->short_only = false;
@@ -1642,6 +1674,12 @@ extern "C" int pm_describe(const pm_handle *h, char *buf, size_t buflen) {
              h->sd.edits && h->sd.edit_tabulated ? "pm_edit_scan+pm_edits_verify" : h->sd.edits ? "pm_seed_scan+pm_edits_verify" :
              h->sd.halves && h->sd.half_ranked ? "pm_half_scan+pm_half_verify" : "pm_seed_scan", 1 + (int)h->sd_more.size(), h->sd.ncombos, h->sd.r, h->sd.k + h->sd.r, h->sd.pb, h->sd.Lw, h->sd.nslots, (long long)h->geo.seg_len, h->geo.nseg,
              h->geo.blocks, h->geo.threads, SEED_LDS_BYTES);
+    if (h->nlong_exact) {
+      int wide = h->sd.wide ? 1 : 0;
+      for (const SeedDevice &d : h->sd_more) wide += d.wide ? 1 : 0;
+      const size_t at = strlen(buf);
+      if (at < buflen) snprintf(buf + at, buflen - at, " with %zu patterns of 33..64 characters (wide rows, wide tiles=%d)", h->nlong_exact, wide);
+    }
     if (h->nrest) {
       const size_t at = strlen(buf);
       if (at < buflen) snprintf(buf + at, buflen - at, " + %s for %zu patterns the seed plan does not take", bitpar_kernel_name(h->scan_k, h->scan_indels), h->nrest);
@@ -1914,9 +1952,9 @@ static int edits_end_candidates(pm_handle *h, std::vector<pm_hit> *out) {
 // (shift_and_inexact.cc:162-164), so at the very start of the stream a pattern whose first
 // d <= k characters are "missing" is reported at end = L-d with level d + mismatches.  The seed
 // kernel only sees whole windows; these few records are produced here and appended in HBM.
-// The longest pattern of the main class (edge_reach: 32, 64 with long primers on the pair plan) sizes the piece of the
-// stream read; nothing else here depends on the length.
-static int edge_reach(const pm_handle *h) { return h->nlong ? 64 : 32; }
+// The longest pattern of the main class (edge_reach: 32, 64 with long primers on the pair plan or, at k = 0, on the Bloom
+// plan) sizes the piece of the stream read; nothing else here depends on the length.
+static int edge_reach(const pm_handle *h) { return h->nlong || h->nlong_exact ? 64 : 32; }
 static int stream_start_candidates(pm_handle *h, std::vector<pm_hit> *out) {
   const int k = h->seed_k;
   EdgeRecords &e = h->edge[EDGE_STREAM_START];

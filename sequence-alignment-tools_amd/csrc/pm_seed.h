@@ -15,6 +15,7 @@ constexpr int SEED_Q2CAP = 112;                   // second queue (second-level 
 constexpr int SEED_BLOOM_WORDS = 32768;           // 128 KiB blocked Bloom filter per combo
 constexpr int SEED_BLOOM_STRIDE = SEED_BLOOM_WORDS + 4;   // + the bytes a 32-bit block that starts at the last byte reaches (16-byte granule)
 constexpr int SEED_MAX_COMBOS = 16;
+constexpr int SEED_MAX_LEN = 32, SEED_MAX_LEN_WIDE = 64;   // seed_build's max_len: the longest pattern a tile takes (64: wide tiles, k = 0)
 constexpr int SEED_LDS_BYTES = SEED_BLOOM_STRIDE * 4 + (SEED_THREADS / 64) * (SEED_QCAP + SEED_Q2CAP) * 8;   // filter + wave queues
 
 struct SeedTables {
@@ -32,7 +33,8 @@ struct SeedTables {
   std::vector<P40> pat40;
   std::vector<uint8_t> pat_len;
   std::vector<uint32_t> pat_id;
-  std::vector<uint8_t> pat_codes;                 // 32 bytes per pattern
+  std::vector<uint8_t> pat_codes;                 // 32 bytes per pattern, zero padded; 64 in a wide tile
+  bool wide = false;                              // the tile holds a pattern of 33..64 characters (seed_build with max_len = 64; k = 0 only)
   bool halves = false; int hk = 0;                // exact_halves -k mode: partner half per pattern
   int hfast = 0;                                  // see SeedArgs::hfast
   bool exact_filter = false;                      // see SeedArgs::exact_filter
@@ -68,6 +70,7 @@ struct SeedDevice {
   int mode = 0;
   int k = 0, Lw = 0, pb = 0, r = 0, ncombos = 0, maxlen = 0;
   bool ascii = false;
+  bool wide = false;                              // pat_codes in rows of 64: seed_launch picks the WIDE instances of pm_seed_scan
   size_t nslots = 0;
   int idx_bits = 0, bucket_shift = 0;
   Knobs knobs;                                    // set by the caller after seed_upload
@@ -76,7 +79,7 @@ struct SeedDevice {
 std::string seed_build(const std::vector<Pattern> &pats, const std::vector<uint32_t> &ids,
                        const Alphabet &alpha, int k, int eos_code, SeedTables *out, int force_lmin = 0,
                        const std::vector<std::string> *partners = nullptr, const std::vector<uint8_t> *sides = nullptr,
-                       int halves_k = 0, bool edits = false, const Knobs &knobs = Knobs());
+                       int halves_k = 0, bool edits = false, const Knobs &knobs = Knobs(), int max_len = SEED_MAX_LEN);
 hipError_t seed_upload(const SeedTables &t, SeedDevice *d, hipStream_t st);
 void seed_free(SeedDevice *d);
 ScanGeometry seed_geometry(const SeedDevice &d, int64_t begin, int64_t end);

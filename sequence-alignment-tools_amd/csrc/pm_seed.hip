@@ -5,7 +5,7 @@
 // EOS inside the window -- the hit set of the reference's exact engines for k = 0
 // (keyword_tree.t:427-486, shift_and.cc:208-255) and the candidate set of its substitution-only
 // k-error automaton (shift_and_inexact.cc:249-352 with indels=false), on which filter_bitvec and
-// exact_halves build.  Patterns are A/C/G/T strings of <= 32 characters.
+// exact_halves build.  Patterns are A/C/G/T strings of <= 32 characters (k = 0, on request: <= 64, in wide tiles).
 //
 // How (pigeonhole, DESIGN.md "seed family"): the last Lw characters of every pattern are cut into
 // m = k + r pieces of pb characters; <= k substitutions leave >= r pieces untouched, so a true
@@ -27,7 +27,7 @@
 // Bound: LDS/VALU issue, then L2 request rate; HBM traffic is 1 byte per base per MALL pass.
 //
 // In this file, in order: the helpers all seed kernels share (packed loads, hashes, the partner test of
-// exact_halves, the exact verify), pm_seed_scan<LW,MODE,HALVES,EDITS> (the plan above: k = 0, windows
+// exact_halves, the exact verify), pm_seed_scan<LW,MODE,HALVES,EDITS,WIDE> (the plan above: k = 0, windows
 // shorter than 20, and the round-1 forms of the two plans below), pm_edit_scan (first stage of the
 // edit-distance plan: tabulated piece hashes, key map in L2), pm_half_scan (exact_halves -k on a key
 // bitmap + rank directory), the dense second kernels pm_edits_verify / pm_half_verify / pm_bases_verify,
@@ -36,6 +36,7 @@
 #include "pm_internal.h"
 #include "pm_seed.h"
 #include "pm_slots.h"
+#include "pm_verify.h"
 
 #include <algorithm>
 #include <cstring>
@@ -71,7 +72,7 @@ struct SeedArgs {
   const uint2 *pat40;                   // packed last Lw bases of every pattern
   const uint8_t *pat_len;
   const uint32_t *pat_id;
-  const uint8_t *pat_codes;             // stream codes of every pattern char, 32 bytes per pattern
+  const uint8_t *pat_codes;             // stream codes of every pattern char, 32 bytes per pattern (64 in a wide tile: the WIDE instances)
   const uint8_t *cmap;                  // stream code -> 1 for EOS, else 0
   pm_hit *out;
   unsigned long long *counter;
@@ -266,7 +267,10 @@ __device__ __forceinline__ bool partner_possible(const SeedArgs &a, int plen, ui
 }
 
 // Third stage, exact part: (window ending at p, pattern pi) already passed the packed-distance
-// test; count mismatches on the raw stream codes (N = mismatch, EOS = reject) and report.
+// test; count mismatches on the raw stream codes (N = mismatch, EOS = reject) and report.  This is seed_verify<32>
+// (pm_verify.h, which the host check compiles) written out: calling the template here gave the same function with
+// another register assignment, and through it every narrow scan kernel 126 instead of 122 VGPRs and other code
+//  -- so the narrow kernels keep the text they were compiled from.  Change the two together.
 __device__ __noinline__ void verify_exact(const SeedArgs *ap, uint32_t mlo, uint32_t mhi, int64_t p, uint32_t pi) {
   const SeedArgs &a = *ap;
   const int L = a.pat_len[pi];
@@ -314,6 +318,17 @@ __device__ __noinline__ void verify_exact(const SeedArgs *ap, uint32_t mlo, uint
     hh.aux[0] = (uint8_t)((left_clean ? 1 : 0) | (right_clean ? 2 : 0)); hh.aux[1] = hh.aux[2] = 0;
     a.out[o] = hh;
   }
+}
+// The same for a wide tile (SeedDevice::wide: a tile with a pattern of 33..64 characters, rows of 64 codes; k = 0 only,
+// DESIGN.md 4.10).  A function of its own, called by the WIDE instances of pm_seed_scan alone: the narrow kernels and
+// their verify_exact are what they were.
+__device__ __noinline__ void verify_exact_wide(const SeedArgs *ap, uint32_t mlo, uint32_t mhi, int64_t p, uint32_t pi) {
+  const SeedArgs &a = *ap;
+  int ham;
+  uint32_t flags;
+  if (!seed_verify<64>(a, mlo, mhi, p, pi, &ham, &flags)) return;
+  const unsigned long long o = atomicAdd(a.counter, 1ull);
+  if (o < a.cap) a.out[o] = seed_record(a, p, pi, ham, flags);
 }
 
 // exact_halves -k, one seed (half pi ends at p).  Record of a half (seed_build), 32 bytes:
@@ -378,9 +393,12 @@ __device__ __noinline__ void verify_half(const SeedArgs *ap, int64_t p, uint32_t
   if (o < a.cap) a.out[o] = half_seed_record(p, pid);
 }
 
-template <bool HALVES>
+template <bool HALVES, bool WIDE = false>
 __device__ __forceinline__ void verify_hit(const SeedArgs *ap, uint32_t mlo, uint32_t mhi, int64_t p, uint32_t pi) {
-  if (HALVES) verify_half(ap, p, pi); else verify_exact(ap, mlo, mhi, p, pi);
+  static_assert(!(HALVES && WIDE), "halves are never rows of 64 characters");
+  if (HALVES) verify_half(ap, p, pi);
+  else if (WIDE) verify_exact_wide(ap, mlo, mhi, p, pi);
+  else verify_exact(ap, mlo, mhi, p, pi);
 }
 
 // ---- edits (-k with filter_bitvec / shift_and_inexact semantics) --------------------------------
@@ -583,9 +601,9 @@ __device__ __forceinline__ bool packed_close(const uint2 &pp, uint64_t W, int k)
   return (int)__popcll((x | (x >> 1)) & 0x5555555555555555ull) <= k;
 }
 
-template <bool HALVES>
+template <bool HALVES, bool WIDE = false>
 __device__ __forceinline__ void verify_pattern(const SeedArgs &a, uint32_t mlo, uint32_t mhi, uint64_t W, int64_t p, uint32_t pi) {
-  if (HALVES || packed_close(a.pat40[pi], W, a.k)) verify_hit<HALVES>(a.self, mlo, mhi, p, pi);
+  if (HALVES || packed_close(a.pat40[pi], W, a.k)) verify_hit<HALVES, WIDE>(a.self, mlo, mhi, p, pi);
 }
 
 // slots of a loaded bucket whose fingerprint matches, as a bit mask; bit 8 = the bucket is full
@@ -605,7 +623,7 @@ __device__ __forceinline__ uint32_t match_mask(const uint4 &q0, const uint4 &q1,
 // Second stage.  A 32-byte bucket (two 16-byte loads issued together) holds 8 fingerprinted
 // slots; the probe sequence ends at the first bucket with a free slot, which is almost always the
 // first one.  check_bucket tests the slots of a bucket that is already in registers.
-template <bool HALVES, bool EDITS = false>
+template <bool HALVES, bool EDITS = false, bool WIDE = false>
 __device__ __forceinline__ bool check_bucket(const SeedArgs &a, const uint4 &q0, const uint4 &q1, uint32_t fp, uint32_t imask,
                                              uint32_t mlo, uint32_t mhi, uint64_t W, int64_t p) {
   const uint32_t sl[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
@@ -614,14 +632,14 @@ __device__ __forceinline__ bool check_bucket(const SeedArgs &a, const uint4 &q0,
     if (sl[i] == EMPTY) return true;
     if ((sl[i] & ~imask) == fp) {
       if (EDITS) verify_edits(a.self, p, sl[i] & imask);
-      else verify_pattern<HALVES>(a, mlo, mhi, W, p, sl[i] & imask);
+      else verify_pattern<HALVES, WIDE>(a, mlo, mhi, W, p, sl[i] & imask);
     }
   }
   return false;
 }
 
 // continue a probe sequence from bucket b (rare: only after a full bucket)
-template <bool HALVES, bool EDITS = false>
+template <bool HALVES, bool EDITS = false, bool WIDE = false>
 __device__ __noinline__ void probe_from(const SeedArgs *ap, const uint4 *buckets, uint32_t b, uint32_t fp, uint32_t imask,
                                         uint32_t mlo, uint32_t mhi, uint64_t W, int64_t p) {
   const SeedArgs &a = *ap;
@@ -629,16 +647,18 @@ __device__ __noinline__ void probe_from(const SeedArgs *ap, const uint4 *buckets
   for (;;) {
     b &= bmask;
     const uint4 q0 = buckets[2 * (size_t)b], q1 = buckets[2 * (size_t)b + 1];
-    if (check_bucket<HALVES, EDITS>(a, q0, q1, fp, imask, mlo, mhi, W, p)) break;
+    if (check_bucket<HALVES, EDITS, WIDE>(a, q0, q1, fp, imask, mlo, mhi, W, p)) break;
     ++b;
   }
 }
 
 
 // LW > 0: window length known at compile time (all shifts immediate); LW == 0: taken from a.Lw.
-// MODE: see window_hash.
-template <int LW, int MODE, bool HALVES, bool EDITS = false>
+// MODE: see window_hash.  WIDE: the tile's rows of pat_codes hold 64 characters (a pattern of 33..64 characters at
+// k = 0): the exact stage is verify_exact_wide, everything in front of it is the narrow instance's.
+template <int LW, int MODE, bool HALVES, bool EDITS = false, bool WIDE = false>
 __global__ __launch_bounds__(SEED_THREADS) void pm_seed_scan(SeedArgs a) {
+  static_assert(!WIDE || (!HALVES && !EDITS), "wide tiles: the exact engines only");
   extern __shared__ uint32_t lds[];
   uint32_t *bloom = lds;                                          // SEED_BLOOM_STRIDE dwords, at LDS address 0 (bloom_block)
   uint2 *queue_all = reinterpret_cast<uint2 *>(lds + SEED_BLOOM_STRIDE);
@@ -781,7 +801,7 @@ __global__ __launch_bounds__(SEED_THREADS) void pm_seed_scan(SeedArgs a) {
       if ((mm & 511u) && !(a.debug & 4)) {
         const uint64_t W = ((uint64_t)whi << 32) | wlo;
         if (mm & 255u) {
-          if (!HALVES && !EDITS && packed_close(pp, W, a.k)) verify_hit<HALVES>(a.self, mlo, mhi, p, pidx);
+          if (!HALVES && !EDITS && packed_close(pp, W, a.k)) verify_hit<HALVES, WIDE>(a.self, mlo, mhi, p, pidx);
           uint32_t rest = (mm & 255u) & ((mm & 255u) - 1u);         // matches beyond the first (rare)
           while (rest) {
             const int sidx = __ffs(rest) - 1;
@@ -790,10 +810,10 @@ __global__ __launch_bounds__(SEED_THREADS) void pm_seed_scan(SeedArgs a) {
 #pragma unroll
             for (int t = 0; t < 8; ++t) slot = sidx == t ? sl[t] : slot;
             if (EDITS) verify_edits(a.self, p, slot & imask);
-            else verify_pattern<HALVES>(a, mlo, mhi, W, p, slot & imask);
+            else verify_pattern<HALVES, WIDE>(a, mlo, mhi, W, p, slot & imask);
           }
         }
-        if (mm & 256u) probe_from<HALVES, EDITS>(a.self, buckets, (h2 >> a.bucket_shift) + 1, h2 << a.idx_bits, imask, mlo, mhi, W, p);
+        if (mm & 256u) probe_from<HALVES, EDITS, WIDE>(a.self, buckets, (h2 >> a.bucket_shift) + 1, h2 << a.idx_bits, imask, mlo, mhi, W, p);
       }
     }
     q2n = 0;
@@ -1764,7 +1784,7 @@ hipError_t edits_verify_launch(const uint8_t *d_records, int k, int maxlen, bool
 
 std::string seed_build(const std::vector<Pattern> &pats, const std::vector<uint32_t> &ids,
                        const Alphabet &alpha, int k, int eos_code, SeedTables *out, int force_lmin,
-                       const std::vector<std::string> *partners, const std::vector<uint8_t> *sides, int halves_k, bool edits, const Knobs &knobs) {
+                       const std::vector<std::string> *partners, const std::vector<uint8_t> *sides, int halves_k, bool edits, const Knobs &knobs, int max_len) {
   SeedTables &t = *out;
   t = SeedTables();
   t.k = k;
@@ -1781,12 +1801,19 @@ std::string seed_build(const std::vector<Pattern> &pats, const std::vector<uint3
   int lmin = 1 << 30, lmax = 0;
   for (const Pattern &p : pats) {
     if (p.s.empty()) return "empty pattern";
-    if (p.s.size() > 32) return "pattern longer than 32 characters";
+    if (p.s.size() > 32 && max_len <= 32) return "pattern longer than 32 characters";
+    if (p.s.size() > 64) return "pattern longer than 64 characters";
     for (unsigned char ch : p.s) if (base2(ch) < 0) return "pattern with characters other than A,C,G,T";
     lmin = std::min(lmin, (int)p.s.size()); lmax = std::max(lmax, (int)p.s.size());
   }
   if (pats.empty()) { lmin = lmax = 1; }
   t.maxlen = lmax;
+  // A tile whose longest pattern exceeds 32 is a wide tile: rows of 64 codes for verify_exact_wide, everything else -- made
+  // of the last Lw bases -- in the form it has.  Only the exact engines' k = 0 plan reads such rows: the halves' and the
+  // automaton's 32-byte records, and k > 0 (whose long patterns belong to the pair plan), are refused, not assumed.
+  t.wide = lmax > 32;
+  if (t.wide && (partners || edits || k != 0)) return "patterns of 33..64 characters: the seed plan takes them at k = 0 only";
+  const size_t row = t.wide ? 64 : 32;              // bytes of pat_codes per pattern
   if (force_lmin > 0) lmin = std::min(lmin, force_lmin);
   t.Lw = std::min(lmin, 20);
   // choose m = k + r pieces of pb bases: fewest filter lookups + verifies
@@ -1834,7 +1861,7 @@ std::string seed_build(const std::vector<Pattern> &pats, const std::vector<uint3
     t.perm_sel[ci] = sel;
   }
   const size_t np = pats.size();
-  t.pat40.resize(np); t.pat_len.resize(np); t.pat_id.resize(np); t.pat_codes.assign(np * 32, 0);
+  t.pat40.resize(np); t.pat_len.resize(np); t.pat_id.resize(np); t.pat_codes.assign(np * row, 0);
   t.halves = partners != nullptr; t.hk = halves_k;
   t.part32.assign(np, 0); t.part_len.assign(np, 0); t.part_side.assign(np, 0);
   if (partners)
@@ -1895,11 +1922,11 @@ std::string seed_build(const std::vector<Pattern> &pats, const std::vector<uint3
     t.pat40[j] = {(uint32_t)w, (uint32_t)(w >> 32)};
     t.pat_len[j] = (uint8_t)L;
     t.pat_id[j] = ids[j];
-    for (int i = 0; i < L; ++i) t.pat_codes[j * 32 + i] = (uint8_t)alpha.nch[(unsigned char)s[i]];
-    if (edits) edit_record_fill(s, ids[j], &t.pat_codes[j * 32]);   // the row becomes the automaton record edits_verify reads
+    for (int i = 0; i < L; ++i) t.pat_codes[j * row + i] = (uint8_t)alpha.nch[(unsigned char)s[i]];
+    if (edits) edit_record_fill(s, ids[j], &t.pat_codes[j * row]);   // the row becomes the automaton record edits_verify reads
     if (partners) {                                // halves: the row doubles as the 32-byte record verify_half reads
       if (L > 16) return "exact_halves half longer than 16 characters";
-      uint8_t *rec = &t.pat_codes[j * 32];
+      uint8_t *rec = &t.pat_codes[j * row];
       const uint32_t w32 = t.part32[j], idv = ids[j];
       memmove(rec + 16 - L, rec, (size_t)L);         // codes right-aligned in bytes [16-L, 16)
       memset(rec, 0, (size_t)(16 - L));
@@ -2035,7 +2062,8 @@ std::string seed_build(const std::vector<Pattern> &pats, const std::vector<uint3
 
 hipError_t seed_upload(const SeedTables &t, SeedDevice *d, hipStream_t st) {
   seed_free(d);
-  d->k = t.k; d->Lw = t.Lw; d->pb = t.pb; d->r = t.r; d->ascii = t.ascii; d->maxlen = t.maxlen;
+  d->k = t.k; d->Lw = t.Lw; d->pb = t.pb; d->r = t.r; d->ascii = t.ascii; d->maxlen = t.maxlen; d->wide = t.wide;
+  if (t.wide && !((t.Lw == 20 && t.mode == 2) || t.Lw < 20)) return hipErrorInvalidConfiguration;   // (the WIDE instances: seed_launch)
   d->ncombos = (int)t.combos.size(); d->nslots = t.nslots; d->idx_bits = t.idx_bits; d->bucket_shift = t.bucket_shift;
   for (int c = 0; c < d->ncombos; ++c) {
     uint64_t cm = 0;
@@ -2090,14 +2118,18 @@ hipError_t seed_upload(const SeedTables &t, SeedDevice *d, hipStream_t st) {
                            reinterpret_cast<const void *>(pm_seed_scan<0, 0, true>),
                            reinterpret_cast<const void *>(pm_seed_scan<20, 1, false, true>), reinterpret_cast<const void *>(pm_edit_scan),
                            reinterpret_cast<const void *>(pm_half_scan)};
-  for (const void *kf : kernels) {
+  // the WIDE instances, for a wide tile only: a handle without one makes the calls it always made, and no other
+  const void *wide_kernels[] = {reinterpret_cast<const void *>(pm_seed_scan<20, 2, false, false, true>), reinterpret_cast<const void *>(pm_seed_scan<0, 0, false, false, true>)};
+  auto prepare = [&](const void *kf) -> hipError_t {
     // bloom_block addresses the filter from LDS address 0: a kernel that acquired static LDS (which
     // the dynamic block would follow) must fail here, at init, not compute with a shifted filter
     hipFuncAttributes fa;
     if ((e = hipFuncGetAttributes(&fa, kf)) != hipSuccess) return e;
     if (fa.sharedSizeBytes != 0) return hipErrorInvalidConfiguration;
-    if ((e = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, SEED_LDS_BYTES)) != hipSuccess) return e;
-  }
+    return hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, SEED_LDS_BYTES);
+  };
+  for (const void *kf : kernels) if ((e = prepare(kf)) != hipSuccess) return e;
+  if (t.wide) for (const void *kf : wide_kernels) if ((e = prepare(kf)) != hipSuccess) return e;
   return hipStreamSynchronize(st);
 }
 
@@ -2161,6 +2193,8 @@ hipError_t seed_launch(const SeedDevice &d, const uint8_t *d_text, const uint32_
   // `sa`, the second kernels `a` (by value, in v) -- and only that: `self` points at the device copy of `sa`, whose list,
   // counter and capacity are the scan's, so a second kernel must not read through it.
   const bool two = d.edits || (d.halves && d.half_ranked);
+  // a wide tile (rows of 64 codes) is read by the WIDE instances alone: k = 0, window of 20 with four byte pieces or the generic form
+  if (d.wide && (two || d.halves || d.k != 0 || !((d.Lw == 20 && d.mode == 2) || d.Lw < 20))) return hipErrorInvalidConfiguration;
   if (two && (!es || !es->d_seeds || !es->d_seed_count)) return hipErrorInvalidValue;
   SeedArgs sa = a;
   EditVerifyArgs v{};
@@ -2196,6 +2230,8 @@ hipError_t seed_launch(const SeedDevice &d, const uint8_t *d_text, const uint32_
     hipLaunchKernelGGL(pm_half_verify, dim3(256 * 16), dim3(256), 0, st, v);
   }
   else if (d.halves) hipLaunchKernelGGL((pm_seed_scan<0, 0, true>), grid, block, SEED_LDS_BYTES, st, a);
+  else if (d.wide && d.Lw == 20) hipLaunchKernelGGL((pm_seed_scan<20, 2, false, false, true>), grid, block, SEED_LDS_BYTES, st, a);
+  else if (d.wide) hipLaunchKernelGGL((pm_seed_scan<0, 0, false, false, true>), grid, block, SEED_LDS_BYTES, st, a);
   else if (d.Lw == 20 && d.mode == 1) hipLaunchKernelGGL((pm_seed_scan<20, 1, false>), grid, block, SEED_LDS_BYTES, st, a);
   else if (d.Lw == 20 && d.mode == 2) hipLaunchKernelGGL((pm_seed_scan<20, 2, false>), grid, block, SEED_LDS_BYTES, st, a);
   else if (d.Lw == 20) hipLaunchKernelGGL((pm_seed_scan<20, 0, false>), grid, block, SEED_LDS_BYTES, st, a);

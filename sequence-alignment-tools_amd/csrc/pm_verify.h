@@ -1,8 +1,10 @@
 // pm_verify.h -- the exact stage of the substitution plans, shared by pm_pair.hip (patterns of 20..32 characters: tail of
 // 20 bases, four fields of five) and pm_short.hip (patterns of 16..19 characters: tail of 16 bases, four fields of four),
+// the exact stage of the Bloom plan (seed_verify: pm_seed.hip, rows of 32 or 64 characters),
 // the window arithmetic of pm_short_sub_scan, and the way records leave a verify kernel (pair_emit, verify_staged: the
 // loop both pm_pair_verify and pm_short_sub_verify are).  All but those two compiles with a plain C++ compiler as well:
-// tests/test_short_sub_host.py checks it against a plain restatement.
+// tests/test_short_sub_host.py, tests/test_long_sub_host.py and tests/test_long_exact_host.py check it against plain
+// restatements.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -115,6 +117,68 @@ PM_VFN bool pair_verify(const Args &a, int combo, int64_t p, uint32_t pi, pm_hit
   hh->end = p + 1; hh->pid = a.pat_id[pi]; hh->k = (uint8_t)ham;
   hh->aux[0] = (uint8_t)((left_clean ? 1 : 0) | (right_clean ? 2 : 0)); hh->aux[1] = hh->aux[2] = 0;
   return true;
+}
+
+// Exact stage of the Bloom plan (pm_seed.hip: verify_exact, verify_exact_wide): (window ending at p, pattern pi) passed
+// the packed-distance test on the pattern's last Lw bases; count mismatches on the raw stream codes over the whole
+// pattern (N = mismatch, EOS = reject) and report -- once: only through the combo made of the first r clean pieces
+// (mlo, mhi: the caller's combo as window bits, two per base).
+// CW = characters a pattern's row of pat_codes holds: 32, or 64 in a wide tile (patterns of up to 64 characters at
+// k = 0); the verdicts are CW bits.  Four stream bytes against four pattern codes per step, per-byte
+// verdicts by SWAR.  Rolled on purpose: the function must stay small in registers, or the callers' allocation suffers
+// (DESIGN.md 4.1).  The stream is read inside [start, min(start + 4 * ceil(L / 4), n)) and nowhere else.
+// Args: text, n, k, r, Lw, pb, eos_code, pat_len, pat_id, pat_codes.
+// Returns whether (p, pi) is a candidate this combo reports; *ham is then its distance and *flags its clean-half flags
+// (seed_record makes the record of them: the kernels do that behind the list's counter, as they always did).
+template <int CW = 32, typename Args>
+PM_VFN bool seed_verify(const Args &a, uint32_t mlo, uint32_t mhi, int64_t p, uint32_t pi, int *ham_out, uint32_t *flags) {
+  static_assert(CW == 32 || CW == 64, "rows of 32 or 64 characters");
+  typedef typename verify_mask<CW>::type mask_t;
+  const int L = a.pat_len[pi];
+  const int64_t start = p + 1 - L;
+  if (start < 0) return false;
+  const uint32_t *pc = reinterpret_cast<const uint32_t *>(a.pat_codes + (size_t)pi * CW);
+  const uint32_t eb = (uint32_t)(a.eos_code & 0xff) * 0x01010101u;
+  mask_t mism = 0, eos = 0;                           // bit i: stream byte i differs from the pattern / is EOS
+#pragma unroll 1
+  for (int d = 0; 4 * d < L; ++d) {
+    const int64_t off = start + 4 * d;
+    uint32_t tw = 0;
+    if (off + 4 <= a.n) __builtin_memcpy(&tw, a.text + off, 4);
+    else
+      for (int b = 0; off + b < a.n; ++b) tw |= (uint32_t)a.text[off + b] << (8 * b);   // last bytes of the stream
+    const uint32_t x = tw ^ pc[d], z = tw ^ eb;
+    const uint32_t y = (x | ((x & 0x7f7f7f7fu) + 0x7f7f7f7fu)) & 0x80808080u;
+    const uint32_t e = ~(z | ((z & 0x7f7f7f7fu) + 0x7f7f7f7fu)) & 0x80808080u;
+    mism |= (mask_t)(((y >> 7) & 1u) | ((y >> 14) & 2u) | ((y >> 21) & 4u) | ((y >> 28) & 8u)) << (4 * d);
+    eos |= (mask_t)(((e >> 7) & 1u) | ((e >> 14) & 2u) | ((e >> 21) & 4u) | ((e >> 28) & 8u)) << (4 * d);
+  }
+  const mask_t lenmask = L >= CW ? ~(mask_t)0 : (((mask_t)1 << L) - 1u);   // (a shift by the mask's width is undefined)
+  mism &= lenmask;
+  if (a.eos_code >= 0 && (eos & lenmask)) return false;   // EOS inside the window: never a candidate
+  const int ham = pop_mask(mism);                     // N (or any other code) = mismatch
+  if (ham > a.k) return false;
+  const int half = L / 2, m = a.k + a.r;              // (half <= 32 < the width of a 64-bit mask; 16 at CW = 32)
+  const bool left_clean = (mism & (((mask_t)1 << half) - 1u)) == 0, right_clean = (mism >> half) == 0;
+  uint32_t dirty = 0;                                 // pieces (of the last Lw bases) with a mismatch
+  const uint32_t sm = (uint32_t)(mism >> (L - a.Lw)), pmask = (1u << a.pb) - 1u;
+  for (int j = 0; j < m; ++j)
+    if ((sm >> (j * a.pb)) & pmask) dirty |= 1u << j;
+  // report once: only through the combo made of the first r clean pieces
+  uint64_t first = 0;
+  const uint64_t field = (1ull << (2 * a.pb)) - 1ull;
+  for (int j = 0, t = 0; j < m && t < a.r; ++j)
+    if (!(dirty >> j & 1)) { first |= field << (2 * a.pb * j); ++t; }
+  if (first != (((uint64_t)mhi << 32) | mlo)) return false;
+  *ham_out = ham; *flags = (left_clean ? 1u : 0u) | (right_clean ? 2u : 0u);
+  return true;
+}
+template <typename Args>
+PM_VFN pm_hit seed_record(const Args &a, int64_t p, uint32_t pi, int ham, uint32_t flags) {
+  pm_hit hh;
+  hh.end = p + 1; hh.pid = a.pat_id[pi]; hh.k = (uint8_t)ham;
+  hh.aux[0] = (uint8_t)flags; hh.aux[1] = hh.aux[2] = 0;
+  return hh;
 }
 
 // ---- window arithmetic of pm_short_sub_scan (pm_short.hip) ----------------------------------------
