@@ -117,7 +117,7 @@ struct pm_handle {
   size_t susp_cap = 0;
   unsigned long long *h_seed_count = nullptr;   // pinned, 1 + 256 entries: a copy into pageable memory would make the "async" scan call wait for the kernels
   EdgeRecords edge[EDGE_RULES];       // the records the host adds at the stream's edges, per rule
-  uint8_t *d_dp_codes = nullptr;      // device DP (pm_cluster_dp): 32 stream codes per pattern, exact zones
+  uint8_t *d_dp_codes = nullptr;      // device DP (pm_cluster_dp): 32 stream codes per pattern (64 with nlong_edits), exact zones
   int32_t *d_dp_esb = nullptr, *d_dp_eeb = nullptr;
   pm_hit *d_ext = nullptr;            // its output (swapped with d_cands after every scan)
   uint8_t *d_half_codes = nullptr, *d_half_len = nullptr;
@@ -187,6 +187,7 @@ struct pm_handle {
   void *d_htemp = nullptr;
   size_t vals_cap = 0, htemp_bytes = 0;
   size_t nlong = 0;                   // patterns of 33..64 characters on the pair plan (pm_config.long_patterns); 0: no pattern beyond 32 on the seed family
+  size_t nlong_edits = 0;             // patterns of 33..64 characters on the edit plan under -k 1 / -k 2 (PM_LONG_EDITS bit of pm_config.long_patterns): wide tiles of pm_edits_verify_wide, rows of 64 for pm_cluster_dp<64>
   size_t nlong_exact = 0;             // patterns of 33..64 characters on the Bloom plan at k = 0 (PM_LONG_EXACT bit of pm_config.long_patterns): wide tiles of pm_seed_scan
   std::vector<uint8_t> in_rest;       // per inner pattern: 1 = scanned by the bit-parallel residue engine beside the seed family
   size_t nrest = 0;
@@ -418,6 +419,7 @@ static void read_knobs(Knobs *k) {
   k->short_sub_off = is("PM_SHORT_SUB", "off");
   k->long_sub_off = is("PM_LONG_SUB", "off");
   k->long_exact_off = is("PM_LONG_EXACT", "off");
+  k->long_edits_off = is("PM_LONG_EDITS", "off");
   k->debug = getenv("PM_DEBUG") != nullptr;
 }
 
@@ -645,7 +647,7 @@ static bool seed_eligible(pm_handle *h, std::string *why) {
       if (i < h->in_rest.size() && h->in_rest[i]) continue;         // goes to the bit-parallel residue
       if (i < h->in_short.size() && h->in_short[i]) continue;       // 16..19 characters: pm_short_edit_scan
       const Pattern &p = h->pats[i];
-      if (p.s.size() > 32 || p.s.size() < 20) { *why = "the edit-distance seed plan needs 16..32 character patterns"; return false; }
+      if (p.s.size() > (h->nlong_edits ? 64u : 32u) || p.s.size() < 20) { *why = "the edit-distance seed plan needs 16..32 character patterns"; return false; }
     }
     for (uint32_t id : h->inner_ids) if (id >= (1u << 22)) { *why = "the edit-distance seed plan packs pattern ids into 22 bits"; return false; }
     if (sem == PM_SEM_SHIFT_AND_INEXACT) {
@@ -715,6 +717,19 @@ static bool long_route_allowed(const pm_handle *h) {
 static bool long_exact_allowed(const pm_handle *h) {
   if (!(h->cfg.long_patterns & PM_LONG_EXACT) || h->knobs.long_exact_off || h->kern != PM_KERNEL_AUTO) return false;
   if (h->cfg.k != 0 || (h->sem != PM_SEM_KEYWORD_TREE && h->sem != PM_SEM_SHIFT_AND)) return false;
+  if (h->cfg.wildcards && !h->wild_seed) return false;
+  return stream_for_pair_plan(h);
+}
+
+// -k 1 / -k 2 with primers of 33..64 characters: the caller allows them on the edit plan (the PM_LONG_EDITS
+// bit of pm_config.long_patterns), the engine is one whose candidates are the automaton's -- filter_bitvec or bare
+// shift_and_inexact with indels -- no kernel is asked for by name and the stream is one seed_build takes (the pair plan's
+// condition).  Anything else, PM_LONG_EDITS=off included, leaves every handle as it was built before the route existed.
+// Called with wild_seed decided.
+static bool long_edits_allowed(const pm_handle *h) {
+  if (!(h->cfg.long_patterns & PM_LONG_EDITS) || h->knobs.long_edits_off || h->kern != PM_KERNEL_AUTO) return false;
+  if (!h->cfg.indels || (h->cfg.k != 1 && h->cfg.k != 2)) return false;
+  if (h->sem != PM_SEM_FILTER_BITVEC && h->sem != PM_SEM_SHIFT_AND_INEXACT) return false;
   if (h->cfg.wildcards && !h->wild_seed) return false;
   return stream_for_pair_plan(h);
 }
@@ -841,7 +856,7 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
   bool want_seed = h->kern == PM_KERNEL_SEED || h->kern == PM_KERNEL_AUTO;
   h->wild_seed = h->cfg.wildcards && want_seed && h->kern == PM_KERNEL_AUTO && stream_letters_plain(h) &&
                  (h->sem == PM_SEM_KEYWORD_TREE || h->sem == PM_SEM_SHIFT_AND || h->sem == PM_SEM_FILTER_BITVEC);
-  h->nlong = 0; h->nlong_exact = 0;
+  h->nlong = 0; h->nlong_exact = 0; h->nlong_edits = 0;
   bool any_long = false;                                            // (a list without a primer of 33..64 is classified once, as without the flag)
   for (const Pattern &p : h->pats) any_long = any_long || (p.s.size() > 32 && p.s.size() <= 64);
   if (any_long && long_route_allowed(h)) {
@@ -878,8 +893,25 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
     }
     h->nlong_exact = nlong;
   }
-  if (!h->nlong && !h->nlong_exact) classify_patterns(h, want_seed, 32);
-  else if (h->knobs.debug) fprintf(stderr, "[pm] long route: %zu patterns of 33..64 characters on the %s plan\n", h->nlong + h->nlong_exact, h->nlong ? "pair" : "seed");
+  else if (any_long && long_edits_allowed(h)) {
+    // -k 1 / -k 2: a primer of 33..64 characters is a main-class primer under the rule of 20..32 (A,C,G,T only, or <= 16
+    // concrete variants under -w on a plain stream).  Kept only if the main class then holds such a primer; a list whose
+    // long primers are all residue anyway is classified as without the route.
+    classify_patterns(h, want_seed, 64);
+    size_t nlong = 0;
+    std::vector<std::string> variants;
+    for (size_t i = 0; i < h->inner.size(); ++i) {
+      const std::string &ps = h->inner[i].s;
+      if (ps.size() <= 32 || ps.size() > 64 || (i < h->in_rest.size() && h->in_rest[i])) continue;
+      bool ok = true;                                               // (classify_patterns clears in_rest when nothing is left for the main class)
+      if (h->wild_seed) ok = expand_iupac(ps, 16, &variants) && !(h->sem == PM_SEM_FILTER_BITVEC && pattern_n_quirk(h, h->inner[i]));
+      else for (unsigned char ch : ps) ok = ok && (ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T');
+      if (ok) ++nlong;
+    }
+    h->nlong_edits = nlong;
+  }
+  if (!h->nlong && !h->nlong_exact && !h->nlong_edits) classify_patterns(h, want_seed, 32);
+  else if (h->knobs.debug) fprintf(stderr, "[pm] long route: %zu patterns of 33..64 characters on the %s plan\n", h->nlong + h->nlong_exact + h->nlong_edits, h->nlong ? "pair" : h->nlong_edits ? "edit" : "seed");
   if (want_seed && !seed_eligible(h, &why)) {
     if (h->kern == PM_KERNEL_SEED) return fail(h, PM_E_UNSUPPORTED, "seed engine: " + why);
     want_seed = false;
@@ -984,7 +1016,7 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
       if (halves_mode) { tpart.assign(partners.begin() + lo, partners.begin() + hi); tside.assign(sides.begin() + lo, sides.begin() + hi); }
       SeedTables st;
       why = seed_build(tp, tid, h->alpha, sk, h->eos_code, &st, force_lw, halves_mode ? &tpart : nullptr,
-                       halves_mode ? &tside : nullptr, h->cfg.k, edits_mode, h->knobs, h->nlong_exact ? SEED_MAX_LEN_WIDE : SEED_MAX_LEN);
+                       halves_mode ? &tside : nullptr, h->cfg.k, edits_mode, h->knobs, h->nlong_exact || h->nlong_edits ? SEED_MAX_LEN_WIDE : SEED_MAX_LEN);
       if (why.empty() && h->kern == PM_KERNEL_AUTO && st.Lw < (halves_mode ? 8 : 10)) why = "patterns too short for the seed family";
       if (!why.empty()) break;
       SeedDevice *dst = &h->sd;
@@ -1066,7 +1098,7 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
       // slot, over the same pattern list as the automaton records of h->sd (seed records carry indices into it)
       if (edits_mode && h->cfg.k == 2 && !h->bases_edits && h->sd_more.empty() && !h->knobs.edit_bloom && !h->knobs.edit_hash && !sp.empty()) {
         PairTables pt;
-        const std::string msg = pair_build(sp, sid, h->alpha, 2, h->eos_code, &pt, h->knobs.pair_row, 2);
+        const std::string msg = pair_build(sp, sid, h->alpha, 2, h->eos_code, &pt, h->knobs.pair_row, 2, h->nlong_edits ? PAIR_MAX_LEN_WIDE : PAIR_MAX_LEN);   // (the tables read a pattern's last 20 bases only)
         if (msg.empty()) {
           HIP_TRY(h, pair_upload(pt, &h->epair, h->stream));
           h->epair.knobs = h->knobs;
@@ -1092,7 +1124,7 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
     }
   }
   if (!want_seed) {
-    h->nlong_exact = 0;                                             // (no wide tile was kept: the stream edges and pm_describe are the bit-parallel family's)
+    h->nlong_exact = 0; h->nlong_edits = 0;                         // (no wide tile was kept: the stream edges and pm_describe are the bit-parallel family's)
     h->halves_dev = false; h->edits_dev = false; h->half_ranked_any = false;
     std::fill(h->in_rest.begin(), h->in_rest.end(), 0); h->nrest = 0;
     std::fill(h->in_short.begin(), h->in_short.end(), 0); h->nshort = 0; h->short_only = false;
@@ -1664,6 +1696,10 @@ extern "C" int pm_describe(const pm_handle *h, char *buf, size_t buflen) {
   else if (h->kern == PM_KERNEL_SEED && h->edits_dev && h->epair_on) {
     snprintf(buf, buflen, "kernel=pm_pair_edit_scan+pm_pair_edit_resolve+pm_edits_verify tiles=1 tests=14 fields=2-of-4 x 5 bases, displaced by |d| <= 2 window=20 row_slots=%d slot_patterns=2 chunk=%lld nchunks=%d grid=%d block=%d lds=%d schedule=%s",
              h->epair.stride, (long long)h->geo.seg_len, h->geo.nseg, h->geo.blocks, h->geo.threads, PAIR_LDS_BYTES, pair_schedule_name(h->geo));
+    if (h->nlong_edits) {
+      const size_t at = strlen(buf);
+      if (at < buflen) snprintf(buf + at, buflen - at, " with %zu patterns of 33..64 characters (pm_edits_verify_wide, wide tiles=%d)", h->nlong_edits, h->sd.wide ? 1 : 0);
+    }
     if (h->nrest) {
       const size_t at = strlen(buf);
       if (at < buflen) snprintf(buf + at, buflen - at, " + %s for %zu patterns the seed plan does not take", bitpar_kernel_name(h->scan_k, h->scan_indels), h->nrest);
@@ -1679,6 +1715,12 @@ extern "C" int pm_describe(const pm_handle *h, char *buf, size_t buflen) {
       for (const SeedDevice &d : h->sd_more) wide += d.wide ? 1 : 0;
       const size_t at = strlen(buf);
       if (at < buflen) snprintf(buf + at, buflen - at, " with %zu patterns of 33..64 characters (wide rows, wide tiles=%d)", h->nlong_exact, wide);
+    }
+    if (h->nlong_edits) {
+      int wide = h->sd.wide ? 1 : 0;
+      for (const SeedDevice &d : h->sd_more) wide += d.wide ? 1 : 0;
+      const size_t at = strlen(buf);
+      if (at < buflen) snprintf(buf + at, buflen - at, " with %zu patterns of 33..64 characters (pm_edits_verify_wide, wide tiles=%d)", h->nlong_edits, wide);
     }
     if (h->nrest) {
       const size_t at = strlen(buf);
@@ -1928,14 +1970,15 @@ static int edits_start_candidates(pm_handle *h, std::vector<pm_hit> *out) {
 // L + k + 8 characters -- its last bit depends on the last L + k only -- (from the stream-start state when that
 // is the whole stream); duplicates of the kernel's records leave with the dedup.  Computed once per stream.
 // Found by scripts/fuzz_families.py (seed 1308).
+static int edge_reach(const pm_handle *h) { return h->nlong || h->nlong_exact || h->nlong_edits ? 64 : 32; }
 static int edits_end_candidates(pm_handle *h, std::vector<pm_hit> *out) {
   const int k = h->cfg.k;
   const int64_t n = h->n;
   if (h->own_end <= n - 4 || n <= 0) return PM_OK;                  // (the range that holds such an end gets it: the last range may be shorter than four positions)
   EdgeRecords &e = h->edge[EDGE_EDITS_END];
   if (!e.built) {
-    const int64_t T = std::min<int64_t>(n, 32 + k + 8);
-    uint8_t tail[64] = {0};
+    const int64_t T = std::min<int64_t>(n, edge_reach(h) + k + 8);  // (the main class's longest pattern + k + 8: at most 74)
+    uint8_t tail[80] = {0};
     { const int rc = host_codes(h, n - T, T, tail); if (rc) return rc; }
     for (size_t j = 0; j < h->inner.size(); ++j) {
       if (!in_main_class(h, j)) continue;
@@ -1952,9 +1995,8 @@ static int edits_end_candidates(pm_handle *h, std::vector<pm_hit> *out) {
 // (shift_and_inexact.cc:162-164), so at the very start of the stream a pattern whose first
 // d <= k characters are "missing" is reported at end = L-d with level d + mismatches.  The seed
 // kernel only sees whole windows; these few records are produced here and appended in HBM.
-// The longest pattern of the main class (edge_reach: 32, 64 with long primers on the pair plan or, at k = 0, on the Bloom
-// plan) sizes the piece of the stream read; nothing else here depends on the length.
-static int edge_reach(const pm_handle *h) { return h->nlong || h->nlong_exact ? 64 : 32; }
+// The longest pattern of the main class (edge_reach: 32, 64 with long primers on the pair plan, at k = 0 on the Bloom
+// plan or under -k on the edit plan) sizes the piece of the stream read; nothing else here depends on the length.
 static int stream_start_candidates(pm_handle *h, std::vector<pm_hit> *out) {
   const int k = h->seed_k;
   EdgeRecords &e = h->edge[EDGE_STREAM_START];
@@ -2088,14 +2130,16 @@ static int bases_edge_candidates(pm_handle *h, std::vector<pm_hit> *out) {
 }
 
 // per pattern (index = position in the pattern list): 32 stream codes, length, exact zones -- what the
-// device-side DPs (pm_cluster_dp) and pm_bases_seeds read
+// device-side DPs (pm_cluster_dp) and pm_bases_seeds read.  With long primers on the edit plan (nlong_edits) the rows hold
+// 64 codes: dp_row is the stride, and pm_cluster_dp<64> the one reader (cluster_dp_device's `wide`).
+static size_t dp_row(const pm_handle *h) { return h->nlong_edits ? 64 : 32; }
 static int ensure_dp_tables(pm_handle *h) {
-  const size_t np = h->pats.size();
+  const size_t np = h->pats.size(), row = dp_row(h);
   if (!h->d_dp_codes) {
-    std::vector<uint8_t> codes(np * 32, 0);
+    std::vector<uint8_t> codes(np * row, 0);
     std::vector<int32_t> es(np), ee(np);
     for (size_t i = 0; i < np; ++i) {
-      for (size_t q = 0; q < h->pats[i].s.size() && q < 32; ++q) codes[i * 32 + q] = (uint8_t)h->alpha.nch[(unsigned char)h->pats[i].s[q]];
+      for (size_t q = 0; q < h->pats[i].s.size() && q < row; ++q) codes[i * row + q] = (uint8_t)h->alpha.nch[(unsigned char)h->pats[i].s[q]];
       es[i] = h->pats[i].esb; ee[i] = h->pats[i].eeb;
     }
     PM_TRY(dev_upload(h, &h->d_dp_codes, codes, 32, "d_dp_codes"));
@@ -3018,7 +3062,7 @@ static int finalize_device_impl(pm_handle *h, const void *d_cands, size_t n, int
   if (cluster_dp)
     HIP_TRY(h, cluster_dp_device(src, n, h->d_carry, ncarry, h->cfg.k, true, scanned_to, last, h->d_text, h->n, h->eos_code, h->d_dp_codes, h->d_fpat_len,
                                  h->d_dp_esb, h->d_dp_eeb, h->d_fpat_id, own, h->d_keys, h->d_keys_alt, h->d_ctemp, h->ctemp_bytes,
-                                 h->d_fout, h->d_fleft, h->d_fcounts, h->stream));
+                                 h->d_fout, h->d_fleft, h->d_fcounts, h->stream, dp_row(h) == 64));
   else
   HIP_TRY(h, cluster_device(src, n, h->d_carry, ncarry, h->cfg.k, scanned_to, last, h->zoned ? 3 : -1, h->d_fpat_len, h->d_fpat_id, own, h->d_keys, h->d_keys_alt,
                             h->d_ctemp, h->ctemp_bytes, h->d_fout, h->d_fleft, h->d_fcounts, h->stream));

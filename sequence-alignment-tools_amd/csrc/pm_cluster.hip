@@ -14,6 +14,7 @@
 // unchanged for the host stage.
 #include <hipcub/hipcub.hpp>
 
+#include "pm_edits.h"
 #include "pm_internal.h"
 
 namespace pm {
@@ -167,109 +168,17 @@ __global__ __launch_bounds__(256) void pm_dedup_unpack(const uint64_t *keys, siz
 }
 
 // ---- filter_bitvec with edits: clustering and the banded DP per cluster on the device ------------
-// editdist_alignment::align (reference pattern_alignment.cc:117-705) as pm_align.cpp restates it,
-// on stream codes (the patterns of the seed family are A,C,G,T, so code equality is character
-// equality), band cells in thread-private memory as (value, flags) bytes.  Returns true and
-// (*end, *value) when the alignment's value is <= k.
-constexpr int DP_MAXL = 32, DP_MAXDELTA = 10, DP_MAXW = DP_MAXDELTA + 2 * 3 + 2;
-enum : uint8_t { D_EQ = 2, D_SUB = 8, D_INS = 16, D_DEL = 32, D_VIOL = 64, D_END = 128 };
-
-// The stream window (<= DP_MAXL + 3 + DP_MAXDELTA + 1 characters) and the pattern are copied into LDS first (byte i of
-// thread t at i * DP_THREADS + t): read cell by cell from global memory, a dependent byte load per cell, they were
-// most of the kernel's time.
-constexpr int DP_THREADS = 256, DP_WIN = 48;
-__device__ bool device_editdist(const uint8_t *text, int64_t n, int64_t end, int64_t end2, const uint8_t *pat, int L,
-                                int lconst, int rconst, int k, bool indels, int eos, int64_t *out_end, int *out_value,
-                                uint8_t *swin, uint8_t *spat) {
-  uint8_t dp[(DP_MAXL + 1) * DP_MAXW], fl[(DP_MAXL + 1) * DP_MAXW];
-  const int viol = 5 * k + 1, b = indels ? k : 0;
-  int64_t ws = 0;
-  if (end > (int64_t)L + k) ws = end - L - k;                      // :137-139
-  const int buflen = (int)(end2 - ws), delta = (int)(end2 - end);
-  const int W = delta + 2 * b + 2;
-  auto at = [&](int p, int t) { return p * W + (t - (p - b)); };
-  for (int i = 0; i <= buflen && i < DP_WIN; ++i) { const int64_t q = ws + i; swin[i * DP_THREADS] = q >= 0 && q < n ? text[q] : (uint8_t)0; }
-  for (int i = 0; i < L; ++i) spat[i * DP_THREADS] = pat[i];
-  pat = nullptr;
-  auto tch = [&](int t) -> int { return (int)swin[(buflen - t) * DP_THREADS]; };   // win[buflen - t]
-  int lbexact = 0, rbexact = L + 1;                                // :230-233
-  if (lconst > 0) rbexact = L + 1 - lconst;
-  if (rconst > 0) lbexact = rconst;
-  dp[at(0, 0)] = 0; fl[at(0, 0)] = D_END;
-  for (int p = 1, ub = b < L ? b : L; p <= ub; ++p) {              // column 0 (:253-268)
-    const int i = at(p, 0);
-    if (!indels || p < lbexact || p >= rbexact) { dp[i] = (uint8_t)viol; fl[i] = D_VIOL; }
-    else { dp[i] = (uint8_t)(dp[at(p - 1, 0)] + 1); fl[i] = D_DEL; }
-  }
-  for (int t = 1, ub = buflen < delta + b ? buflen : delta + b; t <= ub; ++t) {   // row 0 (:276-294)
-    const int i = at(0, t);
-    if (t <= delta) { dp[i] = 0; fl[i] = D_END; }
-    else if (!indels || lbexact > 0) { dp[i] = (uint8_t)viol; fl[i] = D_VIOL; }
-    else { dp[i] = (uint8_t)(dp[at(0, t - 1)] + 1); fl[i] = D_INS; }
-  }
-  for (int p = 1; p <= L; ++p) {                                   // :296-437
-    const int lb = p - b > 1 ? p - b : 1, ub = buflen < p + delta + b ? buflen : p + delta + b;
-    const int pc = spat[(L - p) * DP_THREADS];
-    const bool zone_sub = (p <= lbexact || p >= rbexact), zone_ins = (p < lbexact || p >= rbexact);
-    int rowmin = viol;
-    for (int t = lb; t <= ub; ++t) {
-      const int tc = tch(t);
-      int v, v1; uint8_t ac;
-      if (tc == pc) { v = dp[at(p - 1, t - 1)]; ac = D_EQ; }
-      else if (tc == eos || zone_sub) { v = viol; ac = D_VIOL; }
-      else { v = dp[at(p - 1, t - 1)] + 1; ac = D_SUB; }
-      if (tc == eos || !indels || t <= lb || zone_ins) {
-        if (viol < v) { v = viol; ac = D_VIOL; }
-      } else {
-        v1 = dp[at(p, t - 1)] + 1;
-        if (v1 < v) { v = v1; ac = D_INS; } else if (v1 == v) ac |= D_INS;
-      }
-      if (!indels || t >= ub || zone_sub) {
-        if (viol < v) { v = viol; ac = D_VIOL; }
-      } else {
-        v1 = dp[at(p - 1, t)] + 1;
-        if (v1 < v) { v = v1; ac = D_DEL; } else if (v1 == v) ac |= D_DEL;
-      }
-      const int i = at(p, t);
-      dp[i] = (uint8_t)v; fl[i] = ac;
-      rowmin = rowmin < v ? rowmin : v;
-    }
-    if (rowmin > k) return false;                                  // :425-436
-  }
-  int best = L - b < buflen ? L - b : buflen;                      // :443-475
-  if (best < 0) best = 0;
-  int bestval = dp[at(L, best)];
-  for (int c = best + 1, ub = buflen < L + delta + b ? buflen : L + delta + b; c <= ub; ++c) {
-    const int v = dp[at(L, c)];
-    if (v < bestval || (v <= bestval && (fl[at(L, c)] & (D_EQ | D_SUB)))) { bestval = v; best = c; }
-  }
-  int p = L, t = best;
-  if (t < p - b || t > p + b + delta) return false;                // :482-490
-  int last = 0;                                                    // 0 none, 1 eq, 2 sub, 3 ins, 4 del
-  for (int guard = 0; guard < 4 * (DP_MAXL + DP_MAXW); ++guard) {  // traceback (:514-590): only the end column matters here
-    const uint8_t ac = fl[at(p, t)];
-    if (ac & D_END) break;
-    const bool match = ac & (D_EQ | D_SUB), sub = ac & D_SUB, ins = ac & D_INS, del = ac & D_DEL;
-    if (match && !((last == 3 && ins) || (last == 4 && del))) {
-      --p; --t;
-      if ((ac & D_EQ) && !(last == 2 && sub)) last = 1;
-      else if (sub) last = 2;
-    } else if (del) { --p; last = 4; }
-    else if (ins) { --t; last = 3; }
-    else if (ac & D_VIOL) { p = 0; t = 0; break; }
-    else return false;
-  }
-  *out_end = end2 - t;                                             // :603-610
-  *out_value = bestval;
-  return bestval <= k;
-}
-
+// The DP is pm_edits.h's device_editdist<MAXL> (checked on the host).  MAXL = 32: every handle but one with patterns of
+// 33..64 characters on the edit plan, whose rows of pattern codes are 64 bytes (MAXL is the row stride) and whose clusters
+// go through the 64 instance.  A cluster of a longer pattern, or one that spans more than DP_MAXDELTA
+// ends, goes to the host stage.
+template <int MAXL>
 __global__ void pm_cluster_dp(const uint64_t *keys, size_t n, int k, int indels, int64_t scanned_to, int last,
                               const uint8_t *text, int64_t ntext, int eos,
                               const uint8_t *pat_codes, const uint8_t *pat_len, const int32_t *esb, const int32_t *eeb,
                               const uint32_t *pat_id, OwnedRange own, pm_hit *out, unsigned long long *out_count,
                               pm_hit *left, unsigned long long *left_count) {
-  __shared__ uint8_t swin[DP_WIN * DP_THREADS], spat[DP_MAXL * DP_THREADS];   // device_editdist's copies of window and pattern
+  __shared__ uint8_t swin[dp_win(MAXL) * DP_THREADS], spat[MAXL * DP_THREADS];   // device_editdist's copies of window and pattern
   const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
   if (i >= n) return;
   const uint64_t key = keys[i];
@@ -292,7 +201,7 @@ __global__ void pm_cluster_dp(const uint64_t *keys, size_t n, int k, int indels,
   if (!chain_owned(own, end, prev, win, out_count + 2)) return;
   const int L = pat_len[pid - 1];
   const bool incomplete = !last && scanned_to < prev + win;        // :118-121
-  if (incomplete || prev - end > DP_MAXDELTA || L > DP_MAXL || k > 3) {   // host stage: may still grow / long repeat cluster
+  if (incomplete || prev - end > DP_MAXDELTA || L > MAXL || k > 3) {   // host stage: may still grow / long repeat cluster
     for (size_t t = i; t < j; ++t) {
       if (t > i && (keys[t] >> 2) == (keys[t - 1] >> 2)) continue;  // duplicate
       const unsigned long long o = atomicAdd(left_count, 1ull);
@@ -304,7 +213,7 @@ __global__ void pm_cluster_dp(const uint64_t *keys, size_t n, int k, int indels,
     return;
   }
   int64_t rend = 0; int rval = 0;
-  if (device_editdist(text, ntext, end, prev, pat_codes + (size_t)(pid - 1) * 32, L, esb[pid - 1], eeb[pid - 1], k, indels != 0, eos, &rend, &rval, swin + threadIdx.x, spat + threadIdx.x) &&
+  if (device_editdist<MAXL>(text, ntext, end, prev, pat_codes + (size_t)(pid - 1) * MAXL, L, esb[pid - 1], eeb[pid - 1], k, indels != 0, eos, &rend, &rval, swin + threadIdx.x, spat + threadIdx.x) &&
       hit_owned(own, rend)) {
     const unsigned long long o = wave_reserve_slot(out_count);
     pm_hit h;
@@ -323,7 +232,7 @@ hipError_t cluster_dp_device(const pm_hit *d_in, size_t n1, const pm_hit *d_in2,
                              const uint8_t *d_text, int64_t ntext, int eos_code,
                              const uint8_t *d_pat_codes, const uint8_t *d_pat_len, const int32_t *d_esb, const int32_t *d_eeb,
                              const uint32_t *d_pat_id, const OwnedRange &own, uint64_t *d_keys, uint64_t *d_keys_alt, void *d_temp, size_t temp_bytes,
-                             pm_hit *d_out, pm_hit *d_left, unsigned long long *d_counts, hipStream_t st) {
+                             pm_hit *d_out, pm_hit *d_left, unsigned long long *d_counts, hipStream_t st, bool wide) {
   hipError_t e = hipMemsetAsync(d_counts, 0, 3 * sizeof(unsigned long long), st);
   const size_t n = n1 + n2;
   if (e != hipSuccess || n == 0) return e;
@@ -333,7 +242,11 @@ hipError_t cluster_dp_device(const pm_hit *d_in, size_t n1, const pm_hit *d_in2,
   if (n2) hipLaunchKernelGGL(pm_dedup_pack, dim3((unsigned)((n2 + threads - 1) / threads)), dim3(threads), 0, st, d_in2, n2, d_keys + n1);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   if ((e = hipcub::DeviceRadixSort::SortKeys(d_temp, temp_bytes, d_keys, d_keys_alt, (int)n, 0, 64, st)) != hipSuccess) return e;
-  hipLaunchKernelGGL(pm_cluster_dp, dim3(blocks), dim3(threads), 0, st, d_keys_alt, n, k, indels ? 1 : 0, scanned_to, last ? 1 : 0,
+  // wide: d_pat_codes in rows of 64 (a handle with patterns of 33..64 characters on the edit plan)
+  if (wide) hipLaunchKernelGGL(pm_cluster_dp<64>, dim3(blocks), dim3(threads), 0, st, d_keys_alt, n, k, indels ? 1 : 0, scanned_to, last ? 1 : 0,
+                     d_text, ntext, eos_code, d_pat_codes, d_pat_len, d_esb, d_eeb, d_pat_id, own, d_out, d_counts, d_left, d_counts + 1);
+  else
+  hipLaunchKernelGGL(pm_cluster_dp<32>, dim3(blocks), dim3(threads), 0, st, d_keys_alt, n, k, indels ? 1 : 0, scanned_to, last ? 1 : 0,
                      d_text, ntext, eos_code, d_pat_codes, d_pat_len, d_esb, d_eeb, d_pat_id, own, d_out, d_counts, d_left, d_counts + 1);
   return hipGetLastError();
 }

@@ -28,7 +28,7 @@ struct Alphabet {
 };
 
 // Test and measurement knobs (PM_SEED_CHUNK, PM_SEED_GROUP, PM_SEED_DEBUG, PM_SEED_TILE, PM_PAIR, PM_PAIR_ROW, PM_PAIR_MAP, PM_HALF_SCAN,
-// PM_EDIT_SCAN, PM_EDIT_TABLE_LOG, PM_SHORT_SCAN, PM_SHORT_TILE, PM_SHORT_SUB, PM_LONG_SUB, PM_LONG_EXACT, PM_BITPAR_TP, PM_BITPAR_SEGLEN, PM_DEBUG).  The environment is read ONCE, by
+// PM_EDIT_SCAN, PM_EDIT_TABLE_LOG, PM_SHORT_SCAN, PM_SHORT_TILE, PM_SHORT_SUB, PM_LONG_SUB, PM_LONG_EXACT, PM_LONG_EDITS, PM_BITPAR_TP, PM_BITPAR_SEGLEN, PM_DEBUG).  The environment is read ONCE, by
 // pm_create (pm_api.cpp read_knobs), into the handle: nothing on the init or launch path calls getenv, and a
 // handle's behaviour does not change when its caller's environment does.  Every field's 0 / -1 / false = unset.
 struct Knobs {
@@ -51,6 +51,7 @@ struct Knobs {
   bool short_sub_off = false;        // PM_SHORT_SUB=off: -K lists with patterns of 16..19 characters leave the pair plan as a whole (A/B runs, tests)
   bool long_sub_off = false;         // PM_LONG_SUB=off: -K patterns of 33..64 characters stay off the pair plan whatever pm_config.long_patterns says (A/B runs, tests)
   bool long_exact_off = false;       // PM_LONG_EXACT=off: k = 0 patterns of 33..64 characters stay off the seed plan whatever pm_config.long_patterns says (A/B runs, tests)
+  bool long_edits_off = false;       // PM_LONG_EDITS=off: -k patterns of 33..64 characters stay off the edit plan whatever pm_config.long_patterns says (A/B runs, tests)
   bool debug = false;                // PM_DEBUG: stage timings on stderr
 };
 
@@ -144,7 +145,7 @@ hipError_t cluster_dp_device(const pm_hit *d_in, size_t n1, const pm_hit *d_in2,
                              const uint8_t *d_text, int64_t ntext, int eos_code,
                              const uint8_t *d_pat_codes, const uint8_t *d_pat_len, const int32_t *d_esb, const int32_t *d_eeb,
                              const uint32_t *d_pat_id, const OwnedRange &own, uint64_t *d_keys, uint64_t *d_keys_alt, void *d_temp, size_t temp_bytes,
-                             pm_hit *d_out, pm_hit *d_left, unsigned long long *d_counts, hipStream_t st);
+                             pm_hit *d_out, pm_hit *d_left, unsigned long long *d_counts, hipStream_t st, bool wide = false);
 
 // exact_halves' sequential per-pattern rule on the device (pm_cluster.hip)
 size_t halves_temp_bytes(size_t n);

@@ -15,7 +15,7 @@ constexpr int SEED_Q2CAP = 112;                   // second queue (second-level 
 constexpr int SEED_BLOOM_WORDS = 32768;           // 128 KiB blocked Bloom filter per combo
 constexpr int SEED_BLOOM_STRIDE = SEED_BLOOM_WORDS + 4;   // + the bytes a 32-bit block that starts at the last byte reaches (16-byte granule)
 constexpr int SEED_MAX_COMBOS = 16;
-constexpr int SEED_MAX_LEN = 32, SEED_MAX_LEN_WIDE = 64;   // seed_build's max_len: the longest pattern a tile takes (64: wide tiles, k = 0)
+constexpr int SEED_MAX_LEN = 32, SEED_MAX_LEN_WIDE = 64;   // seed_build's max_len: the longest pattern a tile takes (64: wide tiles, k = 0 or the edit plan)
 constexpr int SEED_LDS_BYTES = SEED_BLOOM_STRIDE * 4 + (SEED_THREADS / 64) * (SEED_QCAP + SEED_Q2CAP) * 8;   // filter + wave queues
 
 struct SeedTables {
@@ -34,7 +34,7 @@ struct SeedTables {
   std::vector<uint8_t> pat_len;
   std::vector<uint32_t> pat_id;
   std::vector<uint8_t> pat_codes;                 // 32 bytes per pattern, zero padded; 64 in a wide tile
-  bool wide = false;                              // the tile holds a pattern of 33..64 characters (seed_build with max_len = 64; k = 0 only)
+  bool wide = false;                              // the tile holds a pattern of 33..64 characters (seed_build with max_len = 64; k = 0, or the edit plan: 64-byte automaton records)
   bool halves = false; int hk = 0;                // exact_halves -k mode: partner half per pattern
   int hfast = 0;                                  // see SeedArgs::hfast
   bool exact_filter = false;                      // see SeedArgs::exact_filter
@@ -70,7 +70,7 @@ struct SeedDevice {
   int mode = 0;
   int k = 0, Lw = 0, pb = 0, r = 0, ncombos = 0, maxlen = 0;
   bool ascii = false;
-  bool wide = false;                              // pat_codes in rows of 64: seed_launch picks the WIDE instances of pm_seed_scan
+  bool wide = false;                              // pat_codes in rows of 64: seed_launch picks the WIDE instances of pm_seed_scan, or pm_edits_verify_wide
   size_t nslots = 0;
   int idx_bits = 0, bucket_shift = 0;
   Knobs knobs;                                    // set by the caller after seed_upload
@@ -105,6 +105,7 @@ hipError_t seed_launch(const SeedDevice &d, const uint8_t *d_text, const uint32_
 
 // the automaton stage of the edit-distance plan on its own (first stages outside pm_seed.hip: pm_short.hip)
 void edit_record_fill(const std::string &s, uint32_t id, uint8_t *rec);
+void edit_record_fill_wide(const std::string &s, uint32_t id, uint8_t *rec);   // the 64-byte record of a wide tile
 hipError_t edits_verify_launch(const uint8_t *d_records, int k, int maxlen, bool ascii, int eos_code, const uint8_t *d_text, int64_t n,
                                int64_t begin, int64_t end, const uint64_t *d_seeds, const unsigned long long *d_seed_count, uint64_t seed_cap,
                                pm_hit *d_out, unsigned long long *d_counter, uint64_t cap, hipStream_t st);

@@ -33,6 +33,7 @@
 // bitmap + rank directory), the dense second kernels pm_edits_verify / pm_half_verify / pm_bases_verify,
 // pm_pack_stream, and the host side (edit_cover, seed_build, seed_upload, seed_launch).
 #include "pm_bits.h"
+#include "pm_edits.h"
 #include "pm_internal.h"
 #include "pm_seed.h"
 #include "pm_slots.h"
@@ -402,76 +403,8 @@ __device__ __forceinline__ void verify_hit(const SeedArgs *ap, uint32_t mlo, uin
 }
 
 // ---- edits (-k with filter_bitvec / shift_and_inexact semantics) --------------------------------
-// The candidates of these engines are the end positions at which the Wu-Manber k-error automaton
-// (shift_and_inexact.cc:249-352) has the pattern's last bit set.  A seed (3 clean pieces under one
-// of the displacement patterns) says "pattern pi ends within +-k of p+1"; the automaton is then
-// run for that one pattern over the L+k+4 stream characters in front of p+3, from the empty state
-// (its last bit depends on the last L+k characters only), and the ends p-1..p+3 are read off.
-// Record (seed_build): masks of A,C,G,T over the pattern positions (bit i = character i) | L | id.
-// Returns one nibble per end p-1+d, d = 0..4: level+1, or 0.
-__device__ __forceinline__ uint32_t edits_verify(const SeedArgs &a, int64_t p, uint32_t pi, uint32_t *pid) {
-  const uint4 *rec = reinterpret_cast<const uint4 *>(a.pat_codes + (size_t)pi * 32);
-  const uint4 M = rec[0], r = rec[1];
-  const int L = (int)(r.x & 0xffu), k = a.edits;
-  *pid = r.y;
-  // characters [base + skip, p+3) are consumed: maxlen+k+4 of them, so that every end p-1..p+3 has
-  // its L+k characters; an earlier start only adds true history
-  const int nch = (a.maxlen + k + 4 + 15) >> 4;                   // wave-uniform number of 16-byte pieces
-  const int skip = 16 * nch - (a.maxlen + k + 4);                 // wave-uniform: leading characters of the first piece not needed
-  const int64_t base = p + 3 - 16 * (int64_t)nch;
-  uint32_t R0 = 0, R1 = 0, R2 = 0;
-  if (base + skip <= 0) { R1 = 1u; R2 = 3u; }                     // true start of the stream: l prefix bits in row l (:162-164)
-  const uint32_t last = 1u << (L - 1);
-  uint32_t res = 0;
-#pragma unroll 1
-  for (int c = 0; c < nch; ++c) {
-    const int64_t off = base + 16 * c;
-    uint4 v;
-    const bool inside = off >= 0 && off + 16 <= a.n;
-    if (inside) __builtin_memcpy(&v, a.text + off, 16);
-    else {
-      uint32_t w[4] = {0, 0, 0, 0};
-#pragma unroll
-      for (int b = 0; b < 16; ++b) {
-        const int64_t q = off + b;
-        const uint32_t x = (q >= 0 && q < a.n) ? (uint32_t)a.text[q] << (8 * (b & 3)) : 0u;
-        if (b < 4) w[0] |= x; else if (b < 8) w[1] |= x; else if (b < 12) w[2] |= x; else w[3] |= x;
-      }
-      v = make_uint4(w[0], w[1], w[2], w[3]);
-    }
-    const uint32_t vw[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int b = 0; b < 16; ++b) {
-      if (c == 0 && b < skip) continue;                            // wave-uniform
-      const uint32_t ch = (vw[b >> 2] >> (8 * (b & 3))) & 0xffu;
-      uint32_t U;
-      if (a.ascii) U = ch == 'A' ? M.x : ch == 'C' ? M.y : ch == 'G' ? M.z : ch == 'T' ? M.w : 0u;
-      else {
-        const uint32_t u01 = (ch & 1u) ? M.y : M.x, u23 = (ch & 1u) ? M.w : M.z;
-        U = ch > 3u ? 0u : ((ch & 2u) ? u23 : u01);
-      }
-      // one character (pm_bitpar.hip step<K, true>): substitution, insertion and deletion terms
-      const uint32_t x0 = (R0 << 1) | 1u, m1 = x0 | R0;
-      uint32_t n0 = x0 & U;
-      const uint32_t x1 = (R1 << 1) | 1u;
-      uint32_t n1 = (x1 & U) | m1 | (n0 << 1) | 1u | n0;
-      uint32_t n2 = 0;
-      if (k >= 2) {                                                // wave-uniform
-        const uint32_t m2 = x1 | R1, x2 = (R2 << 1) | 1u;
-        n2 = (x2 & U) | m2 | (n1 << 1) | 1u | n1;
-      }
-      bool live = true;
-      if (!inside) { const int64_t t = off + b; live = t >= 0 && t < a.n; }   // only at the stream's ends
-      if ((int)ch == a.eos_code) { n0 = 0; n1 = 0; n2 = 0; }      // EOS clears every row
-      if (live) { R0 = n0; R1 = n1; R2 = n2; }
-      if (c == nch - 1 && b >= 11) {                               // ends p-1 .. p+3 = after the characters p-2 .. p+2
-        const uint32_t lvl = (R0 & last) ? 1u : (R1 & last) ? 2u : (R2 & last) ? 3u : 0u;
-        if (live) res |= lvl << (4 * (b - 11));
-      }
-    }
-  }
-  return res;
-}
+// The automaton run per seed record is pm_edits.h's edits_verify<ROW> (checked on the host): 32-bit rows over the 32-byte
+// records of a tile of patterns of 20..32 characters, 64-bit rows over the 64-byte records of a wide tile.
 
 // q-gram lemma with positions, q = 4: k edits touch at most 4k of the 17 four-base words of the
 // pattern's last 20 bases; every untouched word sits in the stream within k positions of where the
@@ -1590,7 +1523,37 @@ __global__ __launch_bounds__(256) void pm_edits_verify(EditVerifyArgs v) {
   SlotBlocks<SEED_OUT_BLOCK, pm_hit> out = {a.out, a.counter, a.cap};
   seed_list_each(v, [&](bool live, int64_t p, uint32_t code) __attribute__((always_inline)) {
     uint32_t res = 0, pid = 0;
-    if (live) res = edits_verify(a, p, seed_pattern(a, code), &pid);
+    if (live) res = edits_verify<uint32_t>(a, a.maxlen, p, seed_pattern(a, code), &pid);
+    if (__ballot(res != 0) == 0) return;
+#pragma unroll 1
+    for (int d = 0; d < 5; ++d) {
+      const uint32_t lvl1 = (res >> (4 * d)) & 15u;
+      const int64_t e = p - 1 + d;
+      out.put(lane, lvl1 != 0 && e > a.begin && e <= a.end, edit_record(e, pid, lvl1));
+    }
+  });
+  out.mark_unused(lane);
+}
+
+// The same over a wide tile (a pattern of 33..64 characters: 64-byte records, 64-bit rows).  A wave whose
+// seeds are all of patterns of up to 32 characters -- most waves of a tile that holds a few long patterns among many
+// short ones -- consumes 32 + k + 4 characters per seed as the narrow kernel does, not the tile's maxlen + k + 4: a later
+// start is sound as long as every end has its L + k characters, and the stream-start rows go by where the wave's
+// consumption really begins (edits_verify takes both from the maxlen it is given).
+__global__ __launch_bounds__(256) void pm_edits_verify_wide(EditVerifyArgs v) {
+  const SeedArgs &a = v.a;
+  const int lane = threadIdx.x & 63;
+  SlotBlocks<SEED_OUT_BLOCK, pm_hit> out = {a.out, a.counter, a.cap};
+  seed_list_each(v, [&](bool live, int64_t p, uint32_t code) __attribute__((always_inline)) {
+    uint32_t res = 0, pid = 0, pi = 0, L = 0;
+    if (live) { pi = seed_pattern(a, code); L = a.pat_codes[(size_t)pi * 64 + 32]; }
+#ifdef PM_WIDE_TILE_START                                          // A/B measurement build (Makefile VARIANT): every wave starts at the tile's maxlen + k + 4
+    const int maxlen = a.maxlen;
+    (void)L;
+#else
+    const int maxlen = __ballot(L > 32u) ? a.maxlen : 32;          // wave-uniform
+#endif
+    if (live) res = edits_verify<uint64_t>(a, maxlen, p, pi, &pid);
     if (__ballot(res != 0) == 0) return;
 #pragma unroll 1
     for (int d = 0; d < 5; ++d) {
@@ -1764,6 +1727,16 @@ void edit_record_fill(const std::string &s, uint32_t id, uint8_t *rec) {
   const uint32_t len = (uint32_t)s.size();
   memcpy(rec, M, 16); memcpy(rec + 16, &len, 4); memcpy(rec + 20, &id, 4); memset(rec + 24, 0, 8);
 }
+// The 64-byte record of a wide tile (edits_verify<uint64_t>): the four masks as 64-bit rows | length | id | padding.
+void edit_record_fill_wide(const std::string &s, uint32_t id, uint8_t *rec) {
+  uint64_t M[4] = {0, 0, 0, 0};
+  for (size_t i = 0; i < s.size() && i < 64; ++i) {
+    const char *at = strchr("ACGT", s[i]);
+    if (at && s[i]) M[at - "ACGT"] |= 1ull << i;
+  }
+  const uint32_t len = (uint32_t)s.size();
+  memcpy(rec, M, 32); memcpy(rec + 32, &len, 4); memcpy(rec + 36, &id, 4); memset(rec + 40, 0, 24);
+}
 
 // pm_edits_verify alone, for a first stage that lives in another file (pm_short.hip): one automaton run per seed record
 // (pattern index << 40 | position, ~0 = unused slot) of d_seeds[0 .. min(*d_seed_count, seed_cap)) over the records
@@ -1809,10 +1782,11 @@ std::string seed_build(const std::vector<Pattern> &pats, const std::vector<uint3
   if (pats.empty()) { lmin = lmax = 1; }
   t.maxlen = lmax;
   // A tile whose longest pattern exceeds 32 is a wide tile: rows of 64 codes for verify_exact_wide, everything else -- made
-  // of the last Lw bases -- in the form it has.  Only the exact engines' k = 0 plan reads such rows: the halves' and the
-  // automaton's 32-byte records, and k > 0 (whose long patterns belong to the pair plan), are refused, not assumed.
+  // of the last Lw bases -- in the form it has.  The exact engines' k = 0 plan reads such rows, and the edit plan, whose
+  // rows are then the 64-byte automaton records of pm_edits_verify_wide: the halves' 32-byte records and
+  // substitutions with k > 0 (whose long patterns belong to the pair plan) are refused, not assumed.
   t.wide = lmax > 32;
-  if (t.wide && (partners || edits || k != 0)) return "patterns of 33..64 characters: the seed plan takes them at k = 0 only";
+  if (t.wide && (partners || (!edits && k != 0))) return "patterns of 33..64 characters: the seed plan takes them at k = 0 and on the edit plan only";
   const size_t row = t.wide ? 64 : 32;              // bytes of pat_codes per pattern
   if (force_lmin > 0) lmin = std::min(lmin, force_lmin);
   t.Lw = std::min(lmin, 20);
@@ -1923,7 +1897,8 @@ std::string seed_build(const std::vector<Pattern> &pats, const std::vector<uint3
     t.pat_len[j] = (uint8_t)L;
     t.pat_id[j] = ids[j];
     for (int i = 0; i < L; ++i) t.pat_codes[j * row + i] = (uint8_t)alpha.nch[(unsigned char)s[i]];
-    if (edits) edit_record_fill(s, ids[j], &t.pat_codes[j * row]);   // the row becomes the automaton record edits_verify reads
+    if (edits && t.wide) edit_record_fill_wide(s, ids[j], &t.pat_codes[j * row]);
+    else if (edits) edit_record_fill(s, ids[j], &t.pat_codes[j * row]);   // the row becomes the automaton record edits_verify reads
     if (partners) {                                // halves: the row doubles as the 32-byte record verify_half reads
       if (L > 16) return "exact_halves half longer than 16 characters";
       uint8_t *rec = &t.pat_codes[j * row];
@@ -2063,7 +2038,7 @@ std::string seed_build(const std::vector<Pattern> &pats, const std::vector<uint3
 hipError_t seed_upload(const SeedTables &t, SeedDevice *d, hipStream_t st) {
   seed_free(d);
   d->k = t.k; d->Lw = t.Lw; d->pb = t.pb; d->r = t.r; d->ascii = t.ascii; d->maxlen = t.maxlen; d->wide = t.wide;
-  if (t.wide && !((t.Lw == 20 && t.mode == 2) || t.Lw < 20)) return hipErrorInvalidConfiguration;   // (the WIDE instances: seed_launch)
+  if (t.wide && !t.edits && !((t.Lw == 20 && t.mode == 2) || t.Lw < 20)) return hipErrorInvalidConfiguration;   // (the WIDE instances: seed_launch)
   d->ncombos = (int)t.combos.size(); d->nslots = t.nslots; d->idx_bits = t.idx_bits; d->bucket_shift = t.bucket_shift;
   for (int c = 0; c < d->ncombos; ++c) {
     uint64_t cm = 0;
@@ -2129,7 +2104,7 @@ hipError_t seed_upload(const SeedTables &t, SeedDevice *d, hipStream_t st) {
     return hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, SEED_LDS_BYTES);
   };
   for (const void *kf : kernels) if ((e = prepare(kf)) != hipSuccess) return e;
-  if (t.wide) for (const void *kf : wide_kernels) if ((e = prepare(kf)) != hipSuccess) return e;
+  if (t.wide && !t.edits) for (const void *kf : wide_kernels) if ((e = prepare(kf)) != hipSuccess) return e;
   return hipStreamSynchronize(st);
 }
 
@@ -2194,7 +2169,9 @@ hipError_t seed_launch(const SeedDevice &d, const uint8_t *d_text, const uint32_
   // counter and capacity are the scan's, so a second kernel must not read through it.
   const bool two = d.edits || (d.halves && d.half_ranked);
   // a wide tile (rows of 64 codes) is read by the WIDE instances alone: k = 0, window of 20 with four byte pieces or the generic form
-  if (d.wide && (two || d.halves || d.k != 0 || !((d.Lw == 20 && d.mode == 2) || d.Lw < 20))) return hipErrorInvalidConfiguration;
+  // -- or, on the edit plan (64-byte automaton records), by pm_edits_verify_wide
+  if (d.wide && !d.edits && (two || d.halves || d.k != 0 || !((d.Lw == 20 && d.mode == 2) || d.Lw < 20))) return hipErrorInvalidConfiguration;
+  if (d.wide && d.edits && es && es->bases) return hipErrorInvalidConfiguration;   // (pm_bases_verify reads 32-byte records)
   if (two && (!es || !es->d_seeds || !es->d_seed_count)) return hipErrorInvalidValue;
   SeedArgs sa = a;
   EditVerifyArgs v{};
@@ -2219,7 +2196,8 @@ hipError_t seed_launch(const SeedDevice &d, const uint8_t *d_text, const uint32_
       BasesArgs b;
       b.codes = es->b_codes; b.len = es->b_len; b.esb = es->b_esb; b.eeb = es->b_eeb; b.own_lo = es->own_lo; b.own_hi = es->own_hi;
       hipLaunchKernelGGL(pm_bases_verify, dim3(256 * 16), dim3(256), 0, st, v, b);
-    } else
+    } else if (d.wide) hipLaunchKernelGGL(pm_edits_verify_wide, dim3(256 * 16), dim3(256), 0, st, v);
+    else
     hipLaunchKernelGGL(pm_edits_verify, dim3(256 * 16), dim3(256), 0, st, v);
   }
   else if (two) {
