@@ -82,6 +82,7 @@ typedef enum {
 #define PM_LONG_SUB   1    /* -K 1 / -K 2: patterns of 33..64 characters may run on the pair plan */
 #define PM_LONG_EXACT 2    /* k = 0: patterns of 33..64 characters may run on the seed (Bloom) plan */
 #define PM_LONG_EDITS 4    /* -k 1 / -k 2: patterns of 33..64 characters may run on the edit plan */
+#define PM_LONG_HALVES 8   /* -k 1 / -k 2 under exact_halves: patterns of 33..64 characters may run on the halves plan */
 
 /* Replaces the constructor arguments of the reference engines as pick_pattern_index passes them
  * (select.cc:19-30): nmismatch, indels, wildcard, textn, eos.  dna_mut is not supported. */
@@ -95,7 +96,7 @@ typedef struct {
   int32_t text_n;          /* -W: a text N also matches (shift_and.cc:112) */
   int32_t eos;             /* raw end-of-sequence char, '\n' in the CLIs */
   int32_t device;          /* HIP device ordinal */
-  int32_t long_patterns;   /* a bit set (PM_LONG_SUB | PM_LONG_EXACT | PM_LONG_EDITS; 0 = the routing of earlier versions).
+  int32_t long_patterns;   /* a bit set (PM_LONG_SUB | PM_LONG_EXACT | PM_LONG_EDITS | PM_LONG_HALVES; 0 = the routing of earlier versions).
                               PM_LONG_SUB (1) = with PM_KERNEL_AUTO, -K 1 / -K 2 (substitutions only) and filter_bitvec, bare
                               shift_and_inexact or exact_halves on an A,C,G,T-normalized or raw ASCII stream, patterns
                               of 33..64 characters (A,C,G,T; or <= 16 concrete variants under -w on a plain stream)
@@ -109,6 +110,12 @@ typedef struct {
                               shift_and_inexact on such a stream, patterns of 33..64 characters (same conditions) run
                               on the edit plan beside those of 20..32: its first stages read their last 20 bases, the
                               automaton runs on 64-bit rows (pm_edits_verify_wide), the cluster DP on 64 rows.
+                              PM_LONG_HALVES (8) = with PM_KERNEL_AUTO, -k 1 / -k 2 (edits) and exact_halves (selected
+                              or asked for) on such a stream, no wildcards, a list whose patterns are all A,C,G,T and
+                              have 16..64 characters (exact_halves keeps no residue) stays on the halves plan when
+                              one of them has 33..64: a half of 16..32 characters is tested by pm_half_scan on the
+                              bases the lane carries, by pm_half_verify_wide on 64-byte records, and extended by
+                              pm_seed_extend on rows of 32 codes.
                               A bit not set = they go to the bit-parallel kernels, as does every pattern of 65
                               characters or more either way.  Each bit acts on its own option sets only.  (Took the
                               place of reserved[0]: same layout, same PM_ABI_VERSION.) */

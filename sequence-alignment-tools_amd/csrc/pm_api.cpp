@@ -188,6 +188,7 @@ struct pm_handle {
   size_t vals_cap = 0, htemp_bytes = 0;
   size_t nlong = 0;                   // patterns of 33..64 characters on the pair plan (pm_config.long_patterns); 0: no pattern beyond 32 on the seed family
   size_t nlong_edits = 0;             // patterns of 33..64 characters on the edit plan under -k 1 / -k 2 (PM_LONG_EDITS bit of pm_config.long_patterns): wide tiles of pm_edits_verify_wide, rows of 64 for pm_cluster_dp<64>
+  size_t nlong_halves = 0;            // patterns of 33..64 characters on the halves plan under exact_halves -k 1 / -k 2 (PM_LONG_HALVES bit of pm_config.long_patterns): wide tiles of pm_half_scan<true> + pm_half_verify_wide, rows of 32 for pm_seed_extend<32>
   size_t nlong_exact = 0;             // patterns of 33..64 characters on the Bloom plan at k = 0 (PM_LONG_EXACT bit of pm_config.long_patterns): wide tiles of pm_seed_scan
   std::vector<uint8_t> in_rest;       // per inner pattern: 1 = scanned by the bit-parallel residue engine beside the seed family
   size_t nrest = 0;
@@ -420,6 +421,7 @@ static void read_knobs(Knobs *k) {
   k->long_sub_off = is("PM_LONG_SUB", "off");
   k->long_exact_off = is("PM_LONG_EXACT", "off");
   k->long_edits_off = is("PM_LONG_EDITS", "off");
+  k->long_halves_off = is("PM_LONG_HALVES", "off");
   k->debug = getenv("PM_DEBUG") != nullptr;
 }
 
@@ -637,7 +639,7 @@ static bool seed_eligible(pm_handle *h, std::string *why) {
   if (h->cfg.k > 0 && h->cfg.indels && sem == PM_SEM_EXACT_HALVES) {
     // exact_halves with edits: exact seeds of the halves + partner prefilter on the GPU, DP on the host
     if (h->cfg.k > 2) { *why = "exact_halves -k > 2 runs on the bit-parallel family"; return false; }
-    for (const Pattern &p : h->pats) if (p.s.size() > 32 || p.s.size() < 16) { *why = "exact_halves -k on the seed family needs 16..32 character patterns"; return false; }
+    for (const Pattern &p : h->pats) if (p.s.size() > (h->nlong_halves ? 64u : 32u) || p.s.size() < 16) { *why = "exact_halves -k on the seed family needs 16..32 character patterns"; return false; }
     return true;
   }
   if (h->cfg.k > 0 && h->cfg.indels && (sem == PM_SEM_FILTER_BITVEC || sem == PM_SEM_SHIFT_AND_INEXACT)) {
@@ -731,6 +733,19 @@ static bool long_edits_allowed(const pm_handle *h) {
   if (!h->cfg.indels || (h->cfg.k != 1 && h->cfg.k != 2)) return false;
   if (h->sem != PM_SEM_FILTER_BITVEC && h->sem != PM_SEM_SHIFT_AND_INEXACT) return false;
   if (h->cfg.wildcards && !h->wild_seed) return false;
+  return stream_for_pair_plan(h);
+}
+
+static size_t half_row(const pm_handle *h) { return h->nlong_halves ? 32 : 16; }   // codes per half in d_half_codes (pm_seed_extend<16> / <32>)
+// exact_halves -k 1 / -k 2 with primers of 33..64 characters: the caller allows them on the halves plan (the
+// PM_LONG_HALVES bit of pm_config.long_patterns), the engine is exact_halves -- selected or asked for -- with indels, no
+// wildcards, no kernel is asked for by name and the stream is one seed_build takes (the pair plan's condition).  The list
+// itself is looked at by init_common: exact_halves keeps no residue, so every pattern has to be one the plan takes.
+// Anything else, PM_LONG_HALVES=off included, leaves every handle as it was built before the route existed.
+static bool long_halves_allowed(const pm_handle *h) {
+  if (!(h->cfg.long_patterns & PM_LONG_HALVES) || h->knobs.long_halves_off || h->kern != PM_KERNEL_AUTO) return false;
+  if (!h->cfg.indels || (h->cfg.k != 1 && h->cfg.k != 2)) return false;
+  if (h->sem != PM_SEM_EXACT_HALVES || h->cfg.wildcards) return false;
   return stream_for_pair_plan(h);
 }
 
@@ -856,7 +871,7 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
   bool want_seed = h->kern == PM_KERNEL_SEED || h->kern == PM_KERNEL_AUTO;
   h->wild_seed = h->cfg.wildcards && want_seed && h->kern == PM_KERNEL_AUTO && stream_letters_plain(h) &&
                  (h->sem == PM_SEM_KEYWORD_TREE || h->sem == PM_SEM_SHIFT_AND || h->sem == PM_SEM_FILTER_BITVEC);
-  h->nlong = 0; h->nlong_exact = 0; h->nlong_edits = 0;
+  h->nlong = 0; h->nlong_exact = 0; h->nlong_edits = 0; h->nlong_halves = 0;
   bool any_long = false;                                            // (a list without a primer of 33..64 is classified once, as without the flag)
   for (const Pattern &p : h->pats) any_long = any_long || (p.s.size() > 32 && p.s.size() <= 64);
   if (any_long && long_route_allowed(h)) {
@@ -910,8 +925,21 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
     }
     h->nlong_edits = nlong;
   }
-  if (!h->nlong && !h->nlong_exact && !h->nlong_edits) classify_patterns(h, want_seed, 32);
-  else if (h->knobs.debug) fprintf(stderr, "[pm] long route: %zu patterns of 33..64 characters on the %s plan\n", h->nlong + h->nlong_exact + h->nlong_edits, h->nlong ? "pair" : h->nlong_edits ? "edit" : "seed");
+  else if (any_long && long_halves_allowed(h)) {
+    // exact_halves -k 1 / -k 2: one engine, no residue -- the list stays on the halves plan only as a whole: every primer
+    // A,C,G,T and of 16..64 characters.  A 65-mer, a 15-mer or a primer with an N leaves it on the bit-parallel family.
+    classify_patterns(h, want_seed, 64);
+    size_t nlong = 0;
+    bool takes = true;
+    for (const Pattern &p : h->pats) {
+      takes = takes && p.s.size() >= 16 && p.s.size() <= 64;
+      for (unsigned char ch : p.s) takes = takes && (ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T');
+      if (p.s.size() > 32) ++nlong;
+    }
+    if (takes) h->nlong_halves = nlong;
+  }
+  if (!h->nlong && !h->nlong_exact && !h->nlong_edits && !h->nlong_halves) classify_patterns(h, want_seed, 32);
+  else if (h->knobs.debug) fprintf(stderr, "[pm] long route: %zu patterns of 33..64 characters on the %s plan\n", h->nlong + h->nlong_exact + h->nlong_edits + h->nlong_halves, h->nlong ? "pair" : h->nlong_edits ? "edit" : h->nlong_halves ? "halves" : "seed");
   if (want_seed && !seed_eligible(h, &why)) {
     if (h->kern == PM_KERNEL_SEED) return fail(h, PM_E_UNSUPPORTED, "seed engine: " + why);
     want_seed = false;
@@ -970,7 +998,8 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
       size_t fits = 0;                                 // seed_build's rule: the ranked plan when >= 90 % of the halves fit its partner test
       for (size_t i = 0; i < sp.size(); ++i) {
         const int L = (int)sp[i].s.size(), plen = (int)partners[i].size();
-        if (sides[i] ? L + plen + h->cfg.k <= 32 : plen + h->cfg.k <= 16) ++fits;
+        if (L + plen > 32) ++fits;                       // (a half of a pattern of 33..64 characters: its slot tests the half itself)
+        else if (sides[i] ? L + plen + h->cfg.k <= 32 : plen + h->cfg.k <= 16) ++fits;
       }
       if (fits * 10 >= sp.size() * 9) tile_keys = (size_t)1 << 20;
     }
@@ -1016,7 +1045,7 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
       if (halves_mode) { tpart.assign(partners.begin() + lo, partners.begin() + hi); tside.assign(sides.begin() + lo, sides.begin() + hi); }
       SeedTables st;
       why = seed_build(tp, tid, h->alpha, sk, h->eos_code, &st, force_lw, halves_mode ? &tpart : nullptr,
-                       halves_mode ? &tside : nullptr, h->cfg.k, edits_mode, h->knobs, h->nlong_exact || h->nlong_edits ? SEED_MAX_LEN_WIDE : SEED_MAX_LEN);
+                       halves_mode ? &tside : nullptr, h->cfg.k, edits_mode, h->knobs, h->nlong_exact || h->nlong_edits || h->nlong_halves ? SEED_MAX_LEN_WIDE : SEED_MAX_LEN);
       if (why.empty() && h->kern == PM_KERNEL_AUTO && st.Lw < (halves_mode ? 8 : 10)) why = "patterns too short for the seed family";
       if (!why.empty()) break;
       SeedDevice *dst = &h->sd;
@@ -1107,10 +1136,11 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
       }
       if (halves_mode) {
         const size_t nh = h->inner.size();
-        std::vector<uint8_t> codes(nh * 16, 0), lens(nh, 0);
+        const size_t hrow = half_row(h);
+        std::vector<uint8_t> codes(nh * hrow, 0), lens(nh, 0);
         for (size_t i = 0; i < nh; ++i) {
           lens[i] = (uint8_t)h->inner[i].s.size();
-          for (size_t q = 0; q < h->inner[i].s.size() && q < 16; ++q) codes[i * 16 + q] = (uint8_t)h->alpha.nch[(unsigned char)h->inner[i].s[q]];
+          for (size_t q = 0; q < h->inner[i].s.size() && q < hrow; ++q) codes[i * hrow + q] = (uint8_t)h->alpha.nch[(unsigned char)h->inner[i].s[q]];
         }
         std::vector<int32_t> es(h->pats.size()), ee(h->pats.size());
         for (size_t i = 0; i < h->pats.size(); ++i) { es[i] = h->pats[i].esb; ee[i] = h->pats[i].eeb; }
@@ -1124,7 +1154,7 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
     }
   }
   if (!want_seed) {
-    h->nlong_exact = 0; h->nlong_edits = 0;                         // (no wide tile was kept: the stream edges and pm_describe are the bit-parallel family's)
+    h->nlong_exact = 0; h->nlong_edits = 0; h->nlong_halves = 0;    // (no wide tile was kept: the stream edges and pm_describe are the bit-parallel family's)
     h->halves_dev = false; h->edits_dev = false; h->half_ranked_any = false;
     std::fill(h->in_rest.begin(), h->in_rest.end(), 0); h->nrest = 0;
     std::fill(h->in_short.begin(), h->in_short.end(), 0); h->nshort = 0; h->short_only = false;
@@ -1722,6 +1752,12 @@ extern "C" int pm_describe(const pm_handle *h, char *buf, size_t buflen) {
       const size_t at = strlen(buf);
       if (at < buflen) snprintf(buf + at, buflen - at, " with %zu patterns of 33..64 characters (pm_edits_verify_wide, wide tiles=%d)", h->nlong_edits, wide);
     }
+    if (h->nlong_halves) {
+      int wide = h->sd.wide ? 1 : 0;
+      for (const SeedDevice &d : h->sd_more) wide += d.wide ? 1 : 0;
+      const size_t at = strlen(buf);
+      if (at < buflen) snprintf(buf + at, buflen - at, " with %zu patterns of 33..64 characters (pm_half_verify_wide, wide tiles=%d)", h->nlong_halves, wide);
+    }
     if (h->nrest) {
       const size_t at = strlen(buf);
       if (at < buflen) snprintf(buf + at, buflen - at, " + %s for %zu patterns the seed plan does not take", bitpar_kernel_name(h->scan_k, h->scan_indels), h->nrest);
@@ -1970,7 +2006,7 @@ static int edits_start_candidates(pm_handle *h, std::vector<pm_hit> *out) {
 // L + k + 8 characters -- its last bit depends on the last L + k only -- (from the stream-start state when that
 // is the whole stream); duplicates of the kernel's records leave with the dedup.  Computed once per stream.
 // Found by scripts/fuzz_families.py (seed 1308).
-static int edge_reach(const pm_handle *h) { return h->nlong || h->nlong_exact || h->nlong_edits ? 64 : 32; }
+static int edge_reach(const pm_handle *h) { return h->nlong || h->nlong_exact || h->nlong_edits || h->nlong_halves ? 64 : 32; }
 static int edits_end_candidates(pm_handle *h, std::vector<pm_hit> *out) {
   const int k = h->cfg.k;
   const int64_t n = h->n;
@@ -2215,7 +2251,7 @@ static int scan_wait_once(pm_handle *h, size_t *n_out) {
     // handed on are the successful extensions
     if (!h->d_ext) HIP_TRY(h, hipMalloc((void **)&h->d_ext, h->cap * sizeof(pm_hit)));
     HIP_TRY(h, extend_seeds(h->d_text, h->n, h->d_cands, cnt, h->d_half_codes, h->d_half_len, h->d_hesb, h->d_heeb,
-                            h->cfg.k, h->eos_code, h->d_ext, h->d_counter, h->cap, h->stream));
+                            h->cfg.k, h->eos_code, h->d_ext, h->d_counter, h->cap, h->stream, (int)half_row(h)));
     HIP_TRY(h, hipMemcpyAsync(h->h_counter, h->d_counter, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, stream_wait(h));
     std::swap(h->d_cands, h->d_ext);

@@ -5,7 +5,8 @@
 // global_align (primer_alignment.cc:10-299): a DP of the partner half against len+k stream
 // characters, band |t-p| <= k, unit costs, constraint violations priced at 5k+1, the end column
 // chosen by the reference's tie rule (:253-280).  One lane runs one seed: the partner half is
-// <= 16 characters and the band 2k+1 <= 5 cells wide, so two rolling rows live in registers and
+// <= 16 characters (<= 32 for a handle with patterns of 33..64 characters: pm_seed_extend<32>) and the
+// band 2k+1 <= 5 cells wide, so two rolling rows live in registers and
 // the whole DP is a few hundred integer ops; no traceback is needed in the yes/no form.
 // Input: seed records {end = seed position, pid = inner id (2j+1 left half, 2j+2 right half)}.
 // Output: for every seed whose extension succeeds one record
@@ -25,7 +26,7 @@ struct ExtendArgs {
   int64_t n;
   const pm_hit *seeds;
   unsigned long long nseeds;
-  const uint8_t *half_codes;   // [2N][16] stream codes of the half patterns
+  const uint8_t *half_codes;   // [2N][ROW] stream codes of the half patterns (ROW = 16; 32 with halves of patterns of 33..64 characters)
   const uint8_t *half_len;     // [2N]
   const int32_t *esb, *eeb;    // [N] exact_start_bases / exact_end_bases of the whole patterns
   int k, eos_code;
@@ -112,7 +113,11 @@ __device__ __forceinline__ bool global_align_dev(TC tc, int textlen, PC pc, int 
   return true;
 }
 
+// ROW: the row stride of half_codes.  The DP loops over the partner's length and keeps a band of 2k+2 cells: it takes a
+// partner of up to 32 characters as it is.
+template <int ROW>
 __global__ void pm_seed_extend(ExtendArgs a) {
+  static_assert(ROW == 16 || ROW == 32, "rows of 16 or 32 codes");
   const unsigned long long i = blockIdx.x * (unsigned long long)blockDim.x + threadIdx.x;
   if (i >= a.nseeds) return;
   const pm_hit s = a.seeds[i];
@@ -128,7 +133,7 @@ __global__ void pm_seed_extend(ExtendArgs a) {
   if (left) {
     // primer_alignment_lmatch (:568-617): partner = right half, text = [end1, end1+len2+k) forwards;
     // lmatch_-len(p1) is unsigned arithmetic landing in an int (:608): negative = no constraint
-    const uint8_t *pat = a.half_codes + (size_t)(2 * j + 1) * 16;
+    const uint8_t *pat = a.half_codes + (size_t)(2 * j + 1) * ROW;
     const int64_t base = s.end;
     const uint32_t lm = (uint32_t)esb - (uint32_t)len1;
     int lbexact = 0, rbexact = len2 + 1;
@@ -139,7 +144,7 @@ __global__ void pm_seed_extend(ExtendArgs a) {
     ok = global_align_dev(tc, len2 + k, pc, len2, lbexact, rbexact, k, a.eos_code, &matchlen, &value);
   } else {
     // primer_alignment_rmatch (:651-704): partner = left half, text = [textstart, end2-len2) backwards
-    const uint8_t *pat = a.half_codes + (size_t)(2 * j) * 16;
+    const uint8_t *pat = a.half_codes + (size_t)(2 * j) * ROW;
     const int plen = len1 + len2 + k;
     const int64_t textstart = s.end > (int64_t)plen ? s.end - plen : 0;
     const int buflen = (int)(s.end - len2 - textstart);
@@ -167,14 +172,16 @@ __global__ void pm_seed_extend(ExtendArgs a) {
 
 hipError_t extend_seeds(const uint8_t *d_text, int64_t n, const pm_hit *d_seeds, size_t nseeds,
                         const uint8_t *d_half_codes, const uint8_t *d_half_len, const int32_t *d_esb, const int32_t *d_eeb,
-                        int k, int eos_code, pm_hit *d_out, unsigned long long *d_counter, size_t cap, hipStream_t st) {
+                        int k, int eos_code, pm_hit *d_out, unsigned long long *d_counter, size_t cap, hipStream_t st, int half_row) {
   hipError_t e = hipMemsetAsync(d_counter, 0, sizeof(unsigned long long), st);
   if (e != hipSuccess || nseeds == 0) return e;
   ExtendArgs a;
   a.text = d_text; a.n = n; a.seeds = d_seeds; a.nseeds = nseeds; a.half_codes = d_half_codes; a.half_len = d_half_len;
   a.esb = d_esb; a.eeb = d_eeb; a.k = k; a.eos_code = eos_code; a.out = d_out; a.counter = d_counter; a.cap = cap;
   const int threads = 256;
-  hipLaunchKernelGGL(pm_seed_extend, dim3((unsigned)((nseeds + threads - 1) / threads)), dim3(threads), 0, st, a);
+  const dim3 grid((unsigned)((nseeds + threads - 1) / threads));
+  if (half_row == 32) hipLaunchKernelGGL(pm_seed_extend<32>, grid, dim3(threads), 0, st, a);
+  else hipLaunchKernelGGL(pm_seed_extend<16>, grid, dim3(threads), 0, st, a);
   return hipGetLastError();
 }
 

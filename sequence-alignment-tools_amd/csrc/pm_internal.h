@@ -28,7 +28,7 @@ struct Alphabet {
 };
 
 // Test and measurement knobs (PM_SEED_CHUNK, PM_SEED_GROUP, PM_SEED_DEBUG, PM_SEED_TILE, PM_PAIR, PM_PAIR_ROW, PM_PAIR_MAP, PM_HALF_SCAN,
-// PM_EDIT_SCAN, PM_EDIT_TABLE_LOG, PM_SHORT_SCAN, PM_SHORT_TILE, PM_SHORT_SUB, PM_LONG_SUB, PM_LONG_EXACT, PM_LONG_EDITS, PM_BITPAR_TP, PM_BITPAR_SEGLEN, PM_DEBUG).  The environment is read ONCE, by
+// PM_EDIT_SCAN, PM_EDIT_TABLE_LOG, PM_SHORT_SCAN, PM_SHORT_TILE, PM_SHORT_SUB, PM_LONG_SUB, PM_LONG_EXACT, PM_LONG_EDITS, PM_LONG_HALVES, PM_BITPAR_TP, PM_BITPAR_SEGLEN, PM_DEBUG).  The environment is read ONCE, by
 // pm_create (pm_api.cpp read_knobs), into the handle: nothing on the init or launch path calls getenv, and a
 // handle's behaviour does not change when its caller's environment does.  Every field's 0 / -1 / false = unset.
 struct Knobs {
@@ -52,6 +52,7 @@ struct Knobs {
   bool long_sub_off = false;         // PM_LONG_SUB=off: -K patterns of 33..64 characters stay off the pair plan whatever pm_config.long_patterns says (A/B runs, tests)
   bool long_exact_off = false;       // PM_LONG_EXACT=off: k = 0 patterns of 33..64 characters stay off the seed plan whatever pm_config.long_patterns says (A/B runs, tests)
   bool long_edits_off = false;       // PM_LONG_EDITS=off: -k patterns of 33..64 characters stay off the edit plan whatever pm_config.long_patterns says (A/B runs, tests)
+  bool long_halves_off = false;      // PM_LONG_HALVES=off: exact_halves -k lists with patterns of 33..64 characters stay off the halves plan whatever pm_config.long_patterns says (A/B runs, tests)
   bool debug = false;                // PM_DEBUG: stage timings on stderr
 };
 
@@ -282,6 +283,7 @@ hipError_t short_sub_launch(const ShortSubDevice &d, const uint8_t *d_text, cons
 // ---- seed extension DP on the GPU (pm_extend.hip) ---------------------------------------------
 hipError_t extend_seeds(const uint8_t *d_text, int64_t n, const pm_hit *d_seeds, size_t nseeds,
                         const uint8_t *d_half_codes, const uint8_t *d_half_len, const int32_t *d_esb, const int32_t *d_eeb,
-                        int k, int eos_code, pm_hit *d_out, unsigned long long *d_counter, size_t cap, hipStream_t st);
+                        int k, int eos_code, pm_hit *d_out, unsigned long long *d_counter, size_t cap, hipStream_t st,
+                        int half_row = 16);   // codes per row of d_half_codes: 16, or 32 (halves of patterns of 33..64 characters)
 
 }  // namespace pm

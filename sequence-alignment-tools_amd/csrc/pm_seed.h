@@ -15,7 +15,7 @@ constexpr int SEED_Q2CAP = 112;                   // second queue (second-level 
 constexpr int SEED_BLOOM_WORDS = 32768;           // 128 KiB blocked Bloom filter per combo
 constexpr int SEED_BLOOM_STRIDE = SEED_BLOOM_WORDS + 4;   // + the bytes a 32-bit block that starts at the last byte reaches (16-byte granule)
 constexpr int SEED_MAX_COMBOS = 16;
-constexpr int SEED_MAX_LEN = 32, SEED_MAX_LEN_WIDE = 64;   // seed_build's max_len: the longest pattern a tile takes (64: wide tiles, k = 0 or the edit plan)
+constexpr int SEED_MAX_LEN = 32, SEED_MAX_LEN_WIDE = 64;   // seed_build's max_len: the longest pattern a tile takes (64: wide tiles, k = 0, the edit plan or the halves plan)
 constexpr int SEED_LDS_BYTES = SEED_BLOOM_STRIDE * 4 + (SEED_THREADS / 64) * (SEED_QCAP + SEED_Q2CAP) * 8;   // filter + wave queues
 
 struct SeedTables {
@@ -34,7 +34,7 @@ struct SeedTables {
   std::vector<uint8_t> pat_len;
   std::vector<uint32_t> pat_id;
   std::vector<uint8_t> pat_codes;                 // 32 bytes per pattern, zero padded; 64 in a wide tile
-  bool wide = false;                              // the tile holds a pattern of 33..64 characters (seed_build with max_len = 64; k = 0, or the edit plan: 64-byte automaton records)
+  bool wide = false;                              // the tile holds a pattern of 33..64 characters (seed_build with max_len = 64; k = 0, or the edit plan: 64-byte automaton records) or, on the halves plan, a half of one (64-byte half records, pm_halves.h)
   bool halves = false; int hk = 0;                // exact_halves -k mode: partner half per pattern
   int hfast = 0;                                  // see SeedArgs::hfast
   bool exact_filter = false;                      // see SeedArgs::exact_filter
@@ -70,7 +70,7 @@ struct SeedDevice {
   int mode = 0;
   int k = 0, Lw = 0, pb = 0, r = 0, ncombos = 0, maxlen = 0;
   bool ascii = false;
-  bool wide = false;                              // pat_codes in rows of 64: seed_launch picks the WIDE instances of pm_seed_scan, or pm_edits_verify_wide
+  bool wide = false;                              // pat_codes in rows of 64: seed_launch picks the WIDE instances of pm_seed_scan, pm_edits_verify_wide, or pm_half_scan<true> + pm_half_verify_wide
   size_t nslots = 0;
   int idx_bits = 0, bucket_shift = 0;
   Knobs knobs;                                    // set by the caller after seed_upload

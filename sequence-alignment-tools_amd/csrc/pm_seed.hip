@@ -5,7 +5,8 @@
 // EOS inside the window -- the hit set of the reference's exact engines for k = 0
 // (keyword_tree.t:427-486, shift_and.cc:208-255) and the candidate set of its substitution-only
 // k-error automaton (shift_and_inexact.cc:249-352 with indels=false), on which filter_bitvec and
-// exact_halves build.  Patterns are A/C/G/T strings of <= 32 characters (k = 0, on request: <= 64, in wide tiles).
+// exact_halves build.  Patterns are A/C/G/T strings of <= 32 characters (k = 0, the edit plan and the halves plan, on
+// request: <= 64, in wide tiles).
 //
 // How (pigeonhole, DESIGN.md "seed family"): the last Lw characters of every pattern are cut into
 // m = k + r pieces of pb characters; <= k substitutions leave >= r pieces untouched, so a true
@@ -29,11 +30,12 @@
 // In this file, in order: the helpers all seed kernels share (packed loads, hashes, the partner test of
 // exact_halves, the exact verify), pm_seed_scan<LW,MODE,HALVES,EDITS,WIDE> (the plan above: k = 0, windows
 // shorter than 20, and the round-1 forms of the two plans below), pm_edit_scan (first stage of the
-// edit-distance plan: tabulated piece hashes, key map in L2), pm_half_scan (exact_halves -k on a key
-// bitmap + rank directory), the dense second kernels pm_edits_verify / pm_half_verify / pm_bases_verify,
+// edit-distance plan: tabulated piece hashes, key map in L2), pm_half_scan<WIDE> (exact_halves -k on a key
+// bitmap + rank directory), the dense second kernels pm_edits_verify / pm_half_verify(_wide) / pm_bases_verify,
 // pm_pack_stream, and the host side (edit_cover, seed_build, seed_upload, seed_launch).
 #include "pm_bits.h"
 #include "pm_edits.h"
+#include "pm_halves.h"
 #include "pm_internal.h"
 #include "pm_seed.h"
 #include "pm_slots.h"
@@ -394,10 +396,37 @@ __device__ __noinline__ void verify_half(const SeedArgs *ap, int64_t p, uint32_t
   if (o < a.cap) a.out[o] = half_seed_record(p, pid);
 }
 
+// The same in a wide tile (a tile with a half of a pattern of 33..64 characters): 64-byte records
+// (pm_halves.h), the whole half -- up to 32 characters -- on the raw stream.  A partner of up to 16 characters gets the
+// partner test of the narrow tiles; a longer one does not fit its 32-bit word and 24-base window, and the test is only a
+// necessary condition: pm_seed_extend decides.
+__device__ __forceinline__ bool half_seed_ok_wide(const SeedArgs &a, int64_t p, uint32_t pi, uint32_t *pid) {
+  const uint8_t *rec = a.pat_codes + (size_t)pi * HALF_ROW_WIDE;
+  const HalfRecWide r = half_record_info(rec);
+  if (!half_match_wide(a.text, a.n, rec, r.L, p)) return false;
+  *pid = r.id;
+  if (r.plen > 16) return true;
+  const int64_t r0 = partner_window(p, r.L + r.plen, r.side, a.hk);
+  if (r0 < 0 || r0 + 24 > a.n) return true;            // near the stream ends: let the DP decide
+  uint64_t w0, w1, w2;
+  __builtin_memcpy(&w0, a.text + r0, 8);
+  __builtin_memcpy(&w1, a.text + r0 + 8, 8);
+  __builtin_memcpy(&w2, a.text + r0 + 16, 8);
+  return partner_possible(a, r.plen, (uint32_t)r.part, w0, w1, w2);
+}
+
+__device__ __noinline__ void verify_half_wide(const SeedArgs *ap, int64_t p, uint32_t pi) {
+  const SeedArgs &a = *ap;
+  uint32_t pid = 0;
+  if (!half_seed_ok_wide(a, p, pi, &pid)) return;
+  const unsigned long long o = atomicAdd(a.counter, 1ull);
+  if (o < a.cap) a.out[o] = half_seed_record(p, pid);
+}
+
 template <bool HALVES, bool WIDE = false>
 __device__ __forceinline__ void verify_hit(const SeedArgs *ap, uint32_t mlo, uint32_t mhi, int64_t p, uint32_t pi) {
-  static_assert(!(HALVES && WIDE), "halves are never rows of 64 characters");
-  if (HALVES) verify_half(ap, p, pi);
+  if (HALVES && WIDE) verify_half_wide(ap, p, pi);
+  else if (HALVES) verify_half(ap, p, pi);
   else if (WIDE) verify_exact_wide(ap, mlo, mhi, p, pi);
   else verify_exact(ap, mlo, mhi, p, pi);
 }
@@ -591,7 +620,7 @@ __device__ __noinline__ void probe_from(const SeedArgs *ap, const uint4 *buckets
 // k = 0): the exact stage is verify_exact_wide, everything in front of it is the narrow instance's.
 template <int LW, int MODE, bool HALVES, bool EDITS = false, bool WIDE = false>
 __global__ __launch_bounds__(SEED_THREADS) void pm_seed_scan(SeedArgs a) {
-  static_assert(!WIDE || (!HALVES && !EDITS), "wide tiles: the exact engines only");
+  static_assert(!WIDE || !EDITS, "wide tiles: the exact engines and the halves");
   extern __shared__ uint32_t lds[];
   uint32_t *bloom = lds;                                          // SEED_BLOOM_STRIDE dwords, at LDS address 0 (bloom_block)
   uint2 *queue_all = reinterpret_cast<uint2 *>(lds + SEED_BLOOM_STRIDE);
@@ -688,7 +717,7 @@ __global__ __launch_bounds__(SEED_THREADS) void pm_seed_scan(SeedArgs a) {
         h2 = window_hash<MODE>(e.x, e.y & 0xffu, mlo, mhi, sel) * HASH_SLOT;
         const size_t b = h2 >> a.bucket_shift;
         b0 = buckets[2 * b]; b1 = buckets[2 * b + 1];
-        if (HALVES) load_tail16(a, p, th0, th1);                   // independent of the bucket: same round trip
+        if (HALVES && !WIDE) load_tail16(a, p, th0, th1);          // independent of the bucket: same round trip
         mm = match_mask(b0, b1, h2 << a.idx_bits, imask);
       }
       const uint32_t sl[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
@@ -708,6 +737,9 @@ __global__ __launch_bounds__(SEED_THREADS) void pm_seed_scan(SeedArgs a) {
       if constexpr (HALVES) {                                      // block-reserved output
         uint32_t pid = 0;
         bool pass = false;
+        if constexpr (WIDE) {                                      // 64-byte records: every load dependent
+          if ((mm & 255u) && !(a.debug & 4)) pass = half_seed_ok_wide(a, p, pidx, &pid);
+        } else
         if ((mm & 255u) && !(a.debug & 4)) {
           if (a.hfast) {
             // record and partner window in one round trip (side = parity of the half's index)
@@ -1327,7 +1359,10 @@ __global__ __launch_bounds__(SEED_THREADS) void pm_edit_scan(SeedArgs a) {
 //     walks the key's halves with the exact test on the raw stream (half_seed_ok: N and EOS reject, the
 //     half's bases in front of the key) and writes the seed records pm_seed_extend takes.
 // Halves whose partner window does not fit the 48 carried bases (patterns of 31, 32 characters) pass
-// the first kernel unfiltered.
+// the first kernel unfiltered.  A half of a pattern of 33..64 characters (a wide tile) has 16..32
+// characters and lies inside the carried bases itself: its slot holds the half's bases in front of the key, and
+// pm_half_scan<true> compares those in place of the partner test (pm_halves.h); pm_half_verify_wide then tests the
+// whole half on the raw stream against its 64-byte record.
 constexpr int HR_BITMAP_WORDS = 32768, HR_SUPER = 512, HR_REL_WORDS = 2048;
 constexpr int HR_IMAGE_WORDS = HR_BITMAP_WORDS + HR_SUPER + HR_REL_WORDS;
 constexpr int HR_QCAP = 80;                                         // key hits per wave queue (16-byte entries)
@@ -1350,6 +1385,22 @@ __device__ __forceinline__ bool half_partner_fast(const SeedArgs &a, uint32_t pa
   return partner_possible_packed(k, plen, part, T);
 }
 
+// A slot of the second kind (a wide tile only, pm_half_scan<true>): the value 7 in the `half length - 10` field -- halves
+// of up to 16 characters never have it -- marks a half of a pattern of 33..64 characters.  slot.x then holds the half's
+// bases in front of its key and the 5-bit field how many of them count (pm_halves.h); the lane compares them on the
+// carried bases in place of the partner test.
+__device__ __host__ __forceinline__ uint32_t half_slot_info_wide(int cnt, int side, uint32_t nmore, uint32_t more_at) {
+  return (uint32_t)cnt | ((uint32_t)side << 5) | (7u << 6) | ((nmore > 7 ? 7u : nmore) << 9) | (more_at << 12);
+}
+template <bool WIDE>
+__device__ __forceinline__ bool half_slot_pass(const SeedArgs &a, uint32_t x, uint32_t info, uint32_t d0, uint32_t d1, uint32_t d2, int64_t p) {
+  if (WIDE && ((info >> 6) & 7u) == 7u) return half_slot_test(x, (int)(info & 31u), d0, d1);
+  return half_partner_fast(a, x, info, d0, d1, d2, p);
+}
+
+// WIDE: the tile holds slots of the second kind; launched for wide tiles only.  pm_half_scan<false> is the kernel
+// pm_half_scan was before the template, instruction for instruction.
+template <bool WIDE>
 __global__ __launch_bounds__(SEED_THREADS) void pm_half_scan(SeedArgs a) {
   extern __shared__ uint32_t lds[];
   const int cj = blockIdx.x;
@@ -1408,7 +1459,7 @@ __global__ __launch_bounds__(SEED_THREADS) void pm_half_scan(SeedArgs a) {
       bool pass = false;
       uint32_t more = 0, at = 0;
       if (on && !(a.debug & 4)) {
-        pass = half_partner_fast(a, sv.x, sv.y, d0, d1, d2, p);
+        pass = half_slot_pass<WIDE>(a, sv.x, sv.y, d0, d1, d2, p);
         more = (sv.y >> 9) & 7u; at = sv.y >> 12;
         if (more == 7u) { pass = true; more = 0; }                   // many halves share the key: the verify kernel walks them
         if (pass) more = 0;
@@ -1417,7 +1468,7 @@ __global__ __launch_bounds__(SEED_THREADS) void pm_half_scan(SeedArgs a) {
         if (more) {
           const uint2 mv = a.hr_more[at];
           ++at; --more;
-          if (half_partner_fast(a, mv.x, mv.y, d0, d1, d2, p)) { pass = true; more = 0; }
+          if (half_slot_pass<WIDE>(a, mv.x, mv.y, d0, d1, d2, p)) { pass = true; more = 0; }
         }
       }
       out.put(lane, pass, edit_seed_record(p, rank));
@@ -1579,6 +1630,24 @@ __global__ __launch_bounds__(256) void pm_half_verify(EditVerifyArgs v) {
       uint32_t pid = 0;
       bool pass = false;
       if (t < t1) { pass = half_seed_ok(a, p, a.hr_order[t], &pid); ++t; }
+      out.put(lane, pass, half_seed_record(p, pid));
+    }
+  });
+  out.mark_unused(lane);
+}
+
+// The same over a wide tile: 64-byte records, the whole half of up to 32 characters on the raw stream (half_seed_ok_wide).
+__global__ __launch_bounds__(256) void pm_half_verify_wide(EditVerifyArgs v) {
+  const SeedArgs &a = v.a;
+  const int lane = threadIdx.x & 63;
+  SlotBlocks<SEED_OUT_BLOCK, pm_hit> out = {a.out, a.counter, a.cap};
+  seed_list_each(v, [&](bool live, int64_t p, uint32_t rank) __attribute__((always_inline)) {
+    uint32_t t = 0, t1 = 0;
+    if (live) { t = a.hr_first[rank]; t1 = a.hr_first[rank + 1]; }
+    while (__ballot(t < t1)) {
+      uint32_t pid = 0;
+      bool pass = false;
+      if (t < t1) { pass = half_seed_ok_wide(a, p, a.hr_order[t], &pid); ++t; }
       out.put(lane, pass, half_seed_record(p, pid));
     }
   });
@@ -1783,13 +1852,22 @@ std::string seed_build(const std::vector<Pattern> &pats, const std::vector<uint3
   t.maxlen = lmax;
   // A tile whose longest pattern exceeds 32 is a wide tile: rows of 64 codes for verify_exact_wide, everything else -- made
   // of the last Lw bases -- in the form it has.  The exact engines' k = 0 plan reads such rows, and the edit plan, whose
-  // rows are then the 64-byte automaton records of pm_edits_verify_wide: the halves' 32-byte records and
+  // rows are then the 64-byte automaton records of pm_edits_verify_wide:
   // substitutions with k > 0 (whose long patterns belong to the pair plan) are refused, not assumed.
   t.wide = lmax > 32;
-  if (t.wide && (partners || (!edits && k != 0))) return "patterns of 33..64 characters: the seed plan takes them at k = 0 and on the edit plan only";
+  // exact_halves -k (partners): the patterns are halves, and a tile that holds a half of a pattern of 33..64 characters is
+  // the wide one: 64-byte half records (pm_halves.h), halves of up to 32 characters.  A tile without one
+  // is built byte for byte as with max_len = 32.
+  if (partners) {
+    if (t.wide) return "exact_halves half longer than 32 characters";
+    for (size_t j = 0; j < pats.size(); ++j) t.wide = t.wide || pats[j].s.size() + (*partners)[j].size() > 32;
+    if (t.wide && max_len <= 32) return "exact_halves pattern longer than 32 characters";
+  }
+  else if (t.wide && !edits && k != 0) return "patterns of 33..64 characters: the seed plan takes them at k = 0, on the edit plan and on the halves plan only";
   const size_t row = t.wide ? 64 : 32;              // bytes of pat_codes per pattern
   if (force_lmin > 0) lmin = std::min(lmin, force_lmin);
   t.Lw = std::min(lmin, 20);
+  if (partners) t.Lw = std::min(t.Lw, 16);          // (halves of 17..32 characters exist in wide tiles only: the HALVES instances key on at most 16 bases)
   // choose m = k + r pieces of pb bases: fewest filter lookups + verifies
   t.mode = 0;
   if (t.Lw == 20 && k <= 2) {
@@ -1838,13 +1916,15 @@ std::string seed_build(const std::vector<Pattern> &pats, const std::vector<uint3
   t.pat40.resize(np); t.pat_len.resize(np); t.pat_id.resize(np); t.pat_codes.assign(np * row, 0);
   t.halves = partners != nullptr; t.hk = halves_k;
   t.part32.assign(np, 0); t.part_len.assign(np, 0); t.part_side.assign(np, 0);
+  std::vector<uint64_t> part64(t.wide && partners ? np : 0, 0);   // wide tile: the partner of up to 32 bases
   if (partners)
     for (size_t j = 0; j < np; ++j) {
       const std::string &ps = (*partners)[j];
-      if (ps.size() > 16) return "exact_halves partner longer than 16 characters";
-      uint32_t w2 = 0;
-      for (size_t i = 0; i < ps.size(); ++i) { const int b2 = base2((unsigned char)ps[i]); if (b2 < 0) return "pattern with characters other than A,C,G,T"; w2 |= (uint32_t)b2 << (2 * i); }
-      t.part32[j] = w2; t.part_len[j] = (uint8_t)ps.size(); t.part_side[j] = (*sides)[j];
+      if (ps.size() > (t.wide ? 32u : 16u)) return t.wide ? "exact_halves partner longer than 32 characters" : "exact_halves partner longer than 16 characters";
+      uint64_t w2 = 0;
+      for (size_t i = 0; i < ps.size(); ++i) { const int b2 = base2((unsigned char)ps[i]); if (b2 < 0) return "pattern with characters other than A,C,G,T"; w2 |= (uint64_t)b2 << (2 * i); }
+      t.part32[j] = (uint32_t)w2; t.part_len[j] = (uint8_t)ps.size(); t.part_side[j] = (*sides)[j];
+      if (t.wide) part64[j] = w2;
     }
   // halves whose key is one piece of <= 10 bases at the low end of the window: 4^10 keys = the bits of the LDS filter
   t.exact_filter = partners != nullptr && t.mode == 0 && C == 1 && t.r == 1 && t.combos[0][0] == 0 && 2 * t.pb <= 20;
@@ -1899,6 +1979,11 @@ std::string seed_build(const std::vector<Pattern> &pats, const std::vector<uint3
     for (int i = 0; i < L; ++i) t.pat_codes[j * row + i] = (uint8_t)alpha.nch[(unsigned char)s[i]];
     if (edits && t.wide) edit_record_fill_wide(s, ids[j], &t.pat_codes[j * row]);
     else if (edits) edit_record_fill(s, ids[j], &t.pat_codes[j * row]);   // the row becomes the automaton record edits_verify reads
+    if (partners && t.wide) {                      // halves in a wide tile: the 64-byte record of pm_halves.h
+      uint8_t codes[HALF_MAX_WIDE];
+      memcpy(codes, &t.pat_codes[j * row], (size_t)L);
+      half_record_fill_wide(codes, L, part64[j], t.part_len[j], t.part_side[j], ids[j], &t.pat_codes[j * row]);
+    } else
     if (partners) {                                // halves: the row doubles as the 32-byte record verify_half reads
       if (L > 16) return "exact_halves half longer than 16 characters";
       uint8_t *rec = &t.pat_codes[j * row];
@@ -1918,7 +2003,8 @@ std::string seed_build(const std::vector<Pattern> &pats, const std::vector<uint3
   if (partners)
     for (size_t j = 0; j < np; ++j) {
       const int L = (int)pats[j].s.size(), plen = t.part_len[j];
-      if (t.part_side[j] ? L + plen + halves_k <= 32 : plen + halves_k <= 16) ++half_fits;
+      if (L + plen > 32) ++half_fits;               // a half of a pattern of 33..64 characters: a slot that tests the half itself
+      else if (t.part_side[j] ? L + plen + halves_k <= 32 : plen + halves_k <= 16) ++half_fits;
     }
   if (partners && np > 0 && lmin >= 10 && half_fits * 10 >= np * 9 && !knobs.half_bloom) {
     std::vector<uint64_t> srt(np);
@@ -1943,7 +2029,14 @@ std::string seed_build(const std::vector<Pattern> &pats, const std::vector<uint3
       for (size_t q = j; q < j2; ++q) {
         const uint32_t pi = (uint32_t)srt[q];
         t.hr_order[q] = pi;
-        const uint64_t rec = (uint64_t)t.part32[pi] | ((uint64_t)half_slot_info(t.part_len[pi], t.part_side[pi], (int)pats[pi].s.size(), q == j ? (uint32_t)(j2 - j - 1) : 0u, q == j ? more_at : 0u) << 32);
+        const uint32_t nmore = q == j ? (uint32_t)(j2 - j - 1) : 0u, at = q == j ? more_at : 0u;
+        uint64_t rec;
+        if (pats[pi].s.size() + t.part_len[pi] > 32) {   // wide tile, a half of a long pattern: the slot of the second kind
+          int cnt = 0;
+          const uint32_t x = half_slot_wide(pats[pi].s.data(), (int)pats[pi].s.size(), base2, &cnt);
+          rec = (uint64_t)x | ((uint64_t)half_slot_info_wide(cnt, t.part_side[pi], nmore, at) << 32);
+        } else
+        rec = (uint64_t)t.part32[pi] | ((uint64_t)half_slot_info(t.part_len[pi], t.part_side[pi], (int)pats[pi].s.size(), nmore, at) << 32);
         if (q == j) t.hr_slots.push_back(rec); else t.hr_more.push_back(rec);
       }
       j = j2;
@@ -2092,7 +2185,7 @@ hipError_t seed_upload(const SeedTables &t, SeedDevice *d, hipStream_t st) {
                            reinterpret_cast<const void *>(pm_seed_scan<20, 0, false>), reinterpret_cast<const void *>(pm_seed_scan<0, 0, false>),
                            reinterpret_cast<const void *>(pm_seed_scan<0, 0, true>),
                            reinterpret_cast<const void *>(pm_seed_scan<20, 1, false, true>), reinterpret_cast<const void *>(pm_edit_scan),
-                           reinterpret_cast<const void *>(pm_half_scan)};
+                           reinterpret_cast<const void *>(pm_half_scan<false>)};
   // the WIDE instances, for a wide tile only: a handle without one makes the calls it always made, and no other
   const void *wide_kernels[] = {reinterpret_cast<const void *>(pm_seed_scan<20, 2, false, false, true>), reinterpret_cast<const void *>(pm_seed_scan<0, 0, false, false, true>)};
   auto prepare = [&](const void *kf) -> hipError_t {
@@ -2104,7 +2197,9 @@ hipError_t seed_upload(const SeedTables &t, SeedDevice *d, hipStream_t st) {
     return hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, SEED_LDS_BYTES);
   };
   for (const void *kf : kernels) if ((e = prepare(kf)) != hipSuccess) return e;
-  if (t.wide && !t.edits) for (const void *kf : wide_kernels) if ((e = prepare(kf)) != hipSuccess) return e;
+  const void *wide_half_kernels[] = {reinterpret_cast<const void *>(pm_seed_scan<0, 0, true, false, true>), reinterpret_cast<const void *>(pm_half_scan<true>)};
+  if (t.wide && !t.edits && !t.halves) for (const void *kf : wide_kernels) if ((e = prepare(kf)) != hipSuccess) return e;
+  if (t.wide && t.halves) for (const void *kf : wide_half_kernels) if ((e = prepare(kf)) != hipSuccess) return e;
   return hipStreamSynchronize(st);
 }
 
@@ -2169,8 +2264,9 @@ hipError_t seed_launch(const SeedDevice &d, const uint8_t *d_text, const uint32_
   // counter and capacity are the scan's, so a second kernel must not read through it.
   const bool two = d.edits || (d.halves && d.half_ranked);
   // a wide tile (rows of 64 codes) is read by the WIDE instances alone: k = 0, window of 20 with four byte pieces or the generic form
-  // -- or, on the edit plan (64-byte automaton records), by pm_edits_verify_wide
-  if (d.wide && !d.edits && (two || d.halves || d.k != 0 || !((d.Lw == 20 && d.mode == 2) || d.Lw < 20))) return hipErrorInvalidConfiguration;
+  // -- or, on the edit plan (64-byte automaton records), by pm_edits_verify_wide; the 64-byte half records of the halves plan
+  // by pm_half_scan<true> + pm_half_verify_wide or the HALVES && WIDE instance
+  if (d.wide && !d.edits && !d.halves && (two || d.k != 0 || !((d.Lw == 20 && d.mode == 2) || d.Lw < 20))) return hipErrorInvalidConfiguration;
   if (d.wide && d.edits && es && es->bases) return hipErrorInvalidConfiguration;   // (pm_bases_verify reads 32-byte records)
   if (two && (!es || !es->d_seeds || !es->d_seed_count)) return hipErrorInvalidValue;
   SeedArgs sa = a;
@@ -2203,10 +2299,15 @@ hipError_t seed_launch(const SeedDevice &d, const uint8_t *d_text, const uint32_
   else if (two) {
     // pm_half_scan's records (rank of the key, position) are the key hits whose partner test passes; pm_half_verify resolves
     // them on the raw stream into seed records
-    hipLaunchKernelGGL(pm_half_scan, dim3(g.nseg), block, SEED_LDS_BYTES, st, sa);
+    if (d.wide) hipLaunchKernelGGL(pm_half_scan<true>, dim3(g.nseg), block, SEED_LDS_BYTES, st, sa);
+    else
+    hipLaunchKernelGGL(pm_half_scan<false>, dim3(g.nseg), block, SEED_LDS_BYTES, st, sa);
     if ((ce = hipGetLastError()) != hipSuccess) return ce;
+    if (d.wide) hipLaunchKernelGGL(pm_half_verify_wide, dim3(256 * 16), dim3(256), 0, st, v);
+    else
     hipLaunchKernelGGL(pm_half_verify, dim3(256 * 16), dim3(256), 0, st, v);
   }
+  else if (d.halves && d.wide) hipLaunchKernelGGL((pm_seed_scan<0, 0, true, false, true>), grid, block, SEED_LDS_BYTES, st, a);
   else if (d.halves) hipLaunchKernelGGL((pm_seed_scan<0, 0, true>), grid, block, SEED_LDS_BYTES, st, a);
   else if (d.wide && d.Lw == 20) hipLaunchKernelGGL((pm_seed_scan<20, 2, false, false, true>), grid, block, SEED_LDS_BYTES, st, a);
   else if (d.wide) hipLaunchKernelGGL((pm_seed_scan<0, 0, false, false, true>), grid, block, SEED_LDS_BYTES, st, a);

@@ -203,18 +203,20 @@ class PatternMatch:
     (-N), SEM_AUTO reproduces the automatic choice; `kernel` picks the GPU kernel family.
     long_patterns=True lets -K 1 / -K 2 patterns of 33..64 characters run on the pair plan (bit 0 of pm_config.long_patterns),
     long_exact=True lets k = 0 patterns of 33..64 characters run on the seed plan (bit 1), long_edits=True lets -k 1 / -k 2
-    patterns of 33..64 characters run on the edit plan (bit 2); each acts on its own option sets.
+    patterns of 33..64 characters run on the edit plan (bit 2), long_halves=True lets exact_halves -k 1 / -k 2 lists with
+    patterns of 33..64 characters stay on the halves plan (bit 3); each acts on its own option sets.
     """
 
     def __init__(self, k=0, indels=True, eos="\n", semantics=SEM_AUTO, kernel=KERNEL_AUTO, device=0,
-                 wildcards=False, text_n=False, long_patterns=False, long_exact=False, long_edits=False):
+                 wildcards=False, text_n=False, long_patterns=False, long_exact=False, long_edits=False,
+                 long_halves=False):
         self._L = load_library()
         cfg = _Config()
         cfg.abi_version, cfg.semantics, cfg.kernel, cfg.k = 1, semantics, kernel, k
         cfg.indels, cfg.wildcards, cfg.text_n = int(bool(indels)), int(bool(wildcards)), int(bool(text_n))
         cfg.eos = ord(eos) if isinstance(eos, str) else int(eos)
         cfg.device = device
-        cfg.long_patterns = int(bool(long_patterns)) | (2 if long_exact else 0) | (4 if long_edits else 0)
+        cfg.long_patterns = int(bool(long_patterns)) | (2 if long_exact else 0) | (4 if long_edits else 0) | (8 if long_halves else 0)
         self._h = C.c_void_p()
         rc = self._L.pm_create(C.byref(cfg), C.byref(self._h))
         if rc:
