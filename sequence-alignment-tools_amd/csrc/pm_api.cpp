@@ -1016,7 +1016,8 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
       std::vector<Pattern> tp(sp.begin() + lo, sp.begin() + hi);
       std::vector<uint32_t> tid(sid.begin() + lo, sid.begin() + hi);
       PairTables pt;
-      const std::string msg = pair_build(tp, tid, h->alpha, sk, h->eos_code, &pt, h->knobs.pair_row, 3, h->nlong ? PAIR_MAX_LEN_WIDE : PAIR_MAX_LEN);
+      const std::string msg = pair_build(tp, tid, h->alpha, sk, h->eos_code, &pt, h->knobs.pair_row, 3, h->nlong ? PAIR_MAX_LEN_WIDE : PAIR_MAX_LEN,
+                                         (h->knobs.seed_debug & 64) != 0);
       // With long primers in the main class (h->nlong) the plan cannot refuse: long_route_allowed has checked k and the
       // stream, the classification has left the main class A,C,G,T patterns (variants under -w) of 20..64 characters, and
       // a tile holds at most 2^21 of them.  The seed plan below could not take such a list, so a refusal is an error here,
@@ -1127,7 +1128,8 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
       // slot, over the same pattern list as the automaton records of h->sd (seed records carry indices into it)
       if (edits_mode && h->cfg.k == 2 && !h->bases_edits && h->sd_more.empty() && !h->knobs.edit_bloom && !h->knobs.edit_hash && !sp.empty()) {
         PairTables pt;
-        const std::string msg = pair_build(sp, sid, h->alpha, 2, h->eos_code, &pt, h->knobs.pair_row, 2, h->nlong_edits ? PAIR_MAX_LEN_WIDE : PAIR_MAX_LEN);   // (the tables read a pattern's last 20 bases only)
+        const std::string msg = pair_build(sp, sid, h->alpha, 2, h->eos_code, &pt, h->knobs.pair_row, 2, h->nlong_edits ? PAIR_MAX_LEN_WIDE : PAIR_MAX_LEN,
+                                           (h->knobs.seed_debug & 64) != 0);   // (the tables read a pattern's last 20 bases only)
         if (msg.empty()) {
           HIP_TRY(h, pair_upload(pt, &h->epair, h->stream));
           h->epair.knobs = h->knobs;

@@ -67,9 +67,12 @@ struct PairDevice {
 // stride_knob: slots per row of the slot table (0 = default)
 // max_len: the longest pattern the caller lets onto the plan, 32 or 64 (PAIR_MAX_LEN_WIDE); a tile with a pattern beyond 32
 // characters is a wide tile, any other is built as with max_len = 32
+// empty_markers: every row's overflow marker flagged and without patterns, as before the markers held their keys' patterns
+// (PM_SEED_DEBUG bit 6; A/B runs and tests -- results are the same, the scan kernel passes more suspects to the verify)
 constexpr int PAIR_MAX_LEN = 32, PAIR_MAX_LEN_WIDE = 64;
 std::string pair_build(const std::vector<Pattern> &pats, const std::vector<uint32_t> &ids, const Alphabet &alpha, int k,
-                       int eos_code, PairTables *out, int stride_knob = 0, int slot_patterns = 3, int max_len = PAIR_MAX_LEN);
+                       int eos_code, PairTables *out, int stride_knob = 0, int slot_patterns = 3, int max_len = PAIR_MAX_LEN,
+                       bool empty_markers = false);
 hipError_t pair_upload(const PairTables &t, PairDevice *d, hipStream_t st);
 void pair_free(PairDevice *d);
 ScanGeometry pair_geometry(const PairDevice &d, int64_t begin, int64_t end);

@@ -26,8 +26,9 @@
 //                global_load_dwordx2.  The slot holds the OTHER 20 window bits of up to three patterns
 //                with this key; three XOR + popcount against the window's own other fields decide the
 //                window, five rounds later.  What survives is a true candidate on the packed bases
-//                (1e-3 of the positions), a key with more than three patterns, or a key beyond its
-//                row's slots (0.3 % of the keys at 200k patterns: row occupancy is Poisson);
+//                (1e-3 of the positions) or a key with more than three patterns.  The keys beyond their
+//                row's slots (0.3 % of the keys at 200k patterns: row occupancy is Poisson) share the
+//                row's last slot, which holds their patterns in the same form (see slot_pack);
 //   * those few are queued per wave in LDS and leave in batches for a suspect list; a second kernel,
 //     pm_pair_verify, works out rank and slot again and reads the raw stream bytes for the exact
 //     distance (N = mismatch, EOS = reject) with every lane busy;
@@ -63,11 +64,13 @@ constexpr uint32_t F20 = 0xfffffu;
 constexpr uint32_t WHAT_REST = 8u, WHAT_ALL = 16u;                   // suspect: walk the key's patterns from the fourth / from the first
 // Slot of a key, 8 bytes: the other 20 window bits of up to three patterns that have the key
 // (o1 | o2 << 20 | o3 << 40; with fewer than three patterns the free fields repeat o1) and bit 63 =
-// "not settled by these three": more patterns share the key, or -- last slot of every row -- the key
-// lies beyond its row's slots.  It is the high dword's sign bit: the consume stage ORs that dword into its
+// "not settled by these three": more patterns share the key.  The last slot of every row is its overflow
+// marker, the slot of every key beyond the row's slots: it holds the patterns of all those keys in the same
+// form, and the flag when they are more than its fields take (pair_build; pm_pair_verify never reads a
+// marker's fields: it walks the key's own run).  The flag is the high dword's sign bit: the consume stage ORs that dword into its
 // three "within k" verdicts, whose sign is what it tests (bits 60..62 stay zero).  (Until round 3's fuzz the flag
 // went into the third count as -8: with -K 1 a window whose other ten bases all differ from the slot's third
-// pattern -- every window without an A, on a row's overflow marker -- came out at 10 - 8 - 2 = 0, not suspicious.)
+// pattern -- every window without an A, on a row's overflow marker, then empty -- came out at 10 - 8 - 2 = 0, not suspicious.)
 __device__ __host__ __forceinline__ uint64_t slot_pack(uint32_t o1, uint32_t o2, uint32_t o3, bool walk) {
   return (uint64_t)o1 | ((uint64_t)o2 << 20) | ((uint64_t)o3 << 40) | ((uint64_t)(walk ? 8 : 0) << 60);
 }
@@ -81,7 +84,7 @@ struct PairArgs {
   int nchunks, ncombos, group;
   int work_map;                         // blockIdx -> (combo, chunk), pm_workmap.h: PAIR_MAP_SUPERCHUNK, PAIR_MAP_XCD, PAIR_MAP_XCD_SUPERCHUNK
   int k, eos_code, debug;
-  int stride;                           // slots per row of the slot table (the last one is the row's overflow marker)
+  int stride;                           // slots per row of the slot table (the last one is the row's overflow marker: the patterns of the keys beyond the others)
   int fa[PAIR_MAX_COMBOS], fb[PAIR_MAX_COMBOS];
   const uint32_t *image;                // [combo][PAIR_BITMAP_WORDS]: key bitmap
   const uint2 *slots;                   // [combo][PAIR_BITMAP_WORDS * stride]
@@ -846,7 +849,7 @@ __global__ __launch_bounds__(256) void pm_pair_edit_resolve(PairArgs a) {
 // ---- host side: tables, launch -------------------------------------------------------------------
 
 std::string pair_build(const std::vector<Pattern> &pats, const std::vector<uint32_t> &ids, const Alphabet &alpha, int k,
-                       int eos_code, PairTables *out, int stride_knob, int slot_patterns, int max_len) {
+                       int eos_code, PairTables *out, int stride_knob, int slot_patterns, int max_len, bool empty_markers) {
   const size_t SP = slot_patterns == 2 ? 2 : 3;                     // patterns a slot settles (the edit plan compares two: its compare is three times the substitution plan's)
   PairTables &t = *out;
   t = PairTables();
@@ -901,9 +904,12 @@ std::string pair_build(const std::vector<Pattern> &pats, const std::vector<uint3
   else { t.ncombos = 0; for (int x = 0; x < 4; ++x) for (int y = x + 1; y < 4; ++y) { t.fa[t.ncombos] = x; t.fb[t.ncombos] = y; ++t.ncombos; } }
   const int C = t.ncombos;
   // Slots per row of the slot table: rows (32 keys each) hold a Poisson number of the keys that occur, 5.5 on
-  // average at 200k patterns; the last slot of a row is its overflow marker.  12 slots = 96 bytes per row keep
-  // a field pair's table at 3 MiB -- inside an XCD's 4 MiB of L2 -- with 0.3 % of the keys beyond their row
-  // (3 Gbp x 200k patterns: 12 slots 14.8 ms, 14: 15.2, 16: 16.9 -- L2 misses; 10: 21.8 -- overflow suspects);
+  // average at 200k patterns; the last slot of a row is its overflow marker: the keys ranked beyond the other slots
+  // share it, and it holds their patterns (flagged "walk" only when they are more than a slot's fields: rows of
+  // stride + 2 keys or more; empty_markers = the form before that, flagged and without patterns, where every window
+  // on such a key was a suspect).  12 slots = 96 bytes per row keep a field pair's table at 3 MiB -- inside an XCD's
+  // 4 MiB of L2 -- with 0.3 % of the keys beyond their row (3 Gbp x 200k patterns, measured with empty markers:
+  // 12 slots 14.8 ms, 14: 15.2, 16: 16.9 -- L2 misses; 10: 21.8 -- overflow suspects);
   // fuller tiles (the 250k-pattern tiles of a 10^6-primer set: 6.9 keys per row) take 14.
   t.stride = stride_knob >= 2 && stride_knob <= 33 ? stride_knob : (np <= 230000 ? 12 : (np <= 300000 ? 14 : 16));
   const size_t ST = (size_t)t.stride, KMAX = ST - 1;
@@ -932,13 +938,24 @@ std::string pair_build(const std::vector<Pattern> &pats, const std::vector<uint3
     uint32_t *rb = &t.row_base[(size_t)ci * (PAIR_BITMAP_WORDS + 1)];
     std::vector<uint32_t> &f = fp[ci];
     f.reserve(np + 1);
-    for (size_t r = 0; r < (size_t)PAIR_BITMAP_WORDS; ++r) slot[r * ST + KMAX] = slot_pack(0, 0, 0, true);   // overflow markers
+    for (size_t r = 0; r < (size_t)PAIR_BITMAP_WORDS; ++r) slot[r * ST + KMAX] = slot_pack(0, 0, 0, true);   // markers of rows without overflow: never addressed
     uint32_t cur_row = 0, in_row = 0;
+    // the row's overflow patterns -- those of its keys from the KMAX-th on, in order[] order: the first SP of them, and how many there are
+    uint32_t ov[3] = {0, 0, 0};
+    size_t nov = 0;
+    auto close_row = [&]() {
+      if (nov && !empty_markers) {
+        for (size_t q = std::min(nov, SP); q < 3; ++q) ov[q] = ov[0];   // free fields repeat the first pattern
+        slot[(size_t)cur_row * ST + KMAX] = slot_pack(ov[0], ov[1], ov[2], nov > SP);
+      }
+      nov = 0;
+    };
     for (size_t j = 0; j < np;) {
       const uint32_t bitpos = (uint32_t)(srt[j] >> 32);
       size_t j2 = j;
       while (j2 < np && (uint32_t)(srt[j2] >> 32) == bitpos) ++j2;
       const uint32_t row = bitpos >> 5;
+      if (cur_row < row) close_row();
       while (cur_row < row) { rb[++cur_row] = (uint32_t)f.size(); in_row = 0; }
       img[row] |= 1u << (bitpos & 31u);
       f.push_back((uint32_t)j);
@@ -947,13 +964,15 @@ std::string pair_build(const std::vector<Pattern> &pats, const std::vector<uint3
         const uint32_t pi = (uint32_t)srt[q];
         ord[q] = pi;
         ol[q] = field_of(t.pat40[pi], fc) | (field_of(t.pat40[pi], fd) << 10);
-        if (q - j < SP) o[q - j] = field_of(t.pat40[pi], fc) | (field_of(t.pat40[pi], fd) << 10);
+        if (q - j < SP) o[q - j] = ol[q];
+        if (in_row >= KMAX) { if (nov < SP) ov[nov] = ol[q]; ++nov; }
       }
       for (size_t q = std::min(j2 - j, SP); q < 3; ++q) o[q] = o[0];   // free fields repeat the first pattern
       if (in_row < KMAX) slot[(size_t)row * ST + in_row] = slot_pack(o[0], o[1], o[2], j2 - j > SP);
       ++in_row;
       j = j2;
     }
+    close_row();
     while (cur_row < (uint32_t)PAIR_BITMAP_WORDS) rb[++cur_row] = (uint32_t)f.size();
     f.push_back((uint32_t)np);
   };
