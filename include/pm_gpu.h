@@ -322,6 +322,56 @@ int pm_count_scan(pm_handle *h, int64_t begin, int64_t end, uint64_t max_count);
 typedef struct { uint64_t tallied, skipped, aligned_device, aligned_host, bogus, record_bytes_to_host; pm_hit first_bogus; } pm_count_info;
 int pm_counts(pm_handle *h, uint64_t *counts, uint8_t *capped, size_t npat, pm_count_info *info);
 
+/* ---- pcr_match's pairing stage on the device (pcr_match.cc:948-1259).  The final hits of the primers stay in
+ * HBM in a list the handle holds; one round joins every held hit with its partner primer's hits inside the amplicon window,
+ * re-aligns the hits that take part, filters the pairs and counts the N's of the surviving amplicons.  Only survivors cross
+ * PCIe.  Opt-in: nothing else of the library changes.
+ *
+ * pm_pcr_setup: after pm_init / pm_init_device / pm_init_packed without windows (PM_E_UNSUPPORTED for windowed and
+ * host-only handles).  The handle must hold an even number 2n of patterns, n even, added with ids 1..2n in order -- the
+ * numbering of pcr_match.cc:806-906: 2j-1 forward, 2j reverse, n+1..2n their reverse complements.  size_lb / size_ub: n/2
+ * UniSTS size bounds, one per primer pair, or both NULL; size_slack is -d (-1: none).  entry_starts: the stream position
+ * where every FASTA entry starts, increasing (the keys of IndexedFastaFile, fasta_io.t:155-214).  The arrays are copied. */
+typedef struct {
+  int32_t any_orientation;  /* -a */
+  int32_t length_between;   /* -b */
+  int64_t amplicon_min;     /* -m, >= 0 */
+  int64_t amplicon_max;     /* -M */
+  int32_t size_slack;       /* -d, -1: none */
+  int32_t reserved;
+  const uint64_t *size_lb, *size_ub;
+  const int64_t *entry_starts;
+  int64_t n_entries;
+} pm_pcr_params;
+/* One surviving pair: the hit that was processed and its partner, their re-alignments, pe1 - ps (with -b: ps1 - pe), the
+ * primer pair (pind, 1-based) and the N / n characters at stream positions al[0].start .. al[0].start + amplicon_len - 1. */
+typedef struct {
+  pm_hit hit[2];
+  pm_alignment al[2];
+  int64_t amplicon_len;
+  uint32_t pair;
+  uint32_t ncount;
+} pm_pcr_amplicon;
+int pm_pcr_setup(pm_handle *h, const pm_pcr_params *p);
+/* Append n final hits from host memory to the held list (tests; callers that already have hits). */
+int pm_pcr_feed(pm_handle *h, const pm_hit *hits, size_t n);
+/* pm_scan's ranges (consecutive, increasing; end == n flushes; dense ranges are cut by the library) with the final hits
+ * appended to the held list instead of handed out; *n_new (may be NULL) = how many.  pm_scan / pm_scan_view, pm_count_scan
+ * and pm_pcr_scan cannot be mixed between two pm_reset()s (PM_E_INVALID); pm_reset empties the held list. */
+int pm_pcr_scan(pm_handle *h, int64_t begin, int64_t end, size_t *n_new);
+/* One round over the held hits (pcr_match.cc:987-1259) with scanned_to = the stream position scanned so far and more = the
+ * last find_patterns' result: a hit whose window reaches beyond scanned_to while more != 0 is deferred -- it takes part as
+ * a partner and stays held; every other hit is dropped after the round.  *out: *n survivors in a pinned buffer of the
+ * handle, valid until the next call, ordered by the processed hit in (end, id) order, its first partner id before its
+ * second, partners by end.  with_strings: alignment string and matching text (pm_align_hits_text) of hit[0] / hit[1] of
+ * survivor i at *ops / *text + (2i, 2i + 1) * stride.  2^31 candidate pairs or more in one round: PM_E_UNSUPPORTED. */
+int pm_pcr_pair(pm_handle *h, int64_t scanned_to, int more, int with_strings, size_t stride, const pm_pcr_amplicon **out, size_t *n,
+                const char **ops, const char **text);
+/* out[0] hits held before the last round, out[1] its candidate pairs, out[2] its survivors, out[3] / out[4] hits re-aligned
+ * on the device / on the host since pm_reset, out[5] bytes copied device -> host by these calls since pm_reset (survivor
+ * records and strings, records the host re-aligns).  n <= 6 values are written. */
+int pm_pcr_stats(pm_handle *h, uint64_t *out, int n);
+
 /* ---- Multi-GPU exchange (the reference has no counterpart: its scan is one serial
  * pass, primer_match.cc:1118).  One rank = one process = one GPU.  The ranks scan position shards
  * (pm_scan_candidates on local stream indices), exchange their record counts by whatever means the

@@ -223,7 +223,7 @@ struct pm_handle {
   AlignDevice ad;                     // tables of pm_align.hip, built on first use after an init (ensure_align_tables)
   bool ad_ready = false, ad_any_long = false;   // ad_any_long: some pattern is beyond the device limit of the DP
   void *ad_mem[8] = {};
-  int scan_mode = 0;                  // since pm_reset: 0 nothing scanned, 1 pm_scan / pm_scan_view, 2 pm_count_scan
+  int scan_mode = 0;                  // since pm_reset: 0 nothing scanned, 1 pm_scan / pm_scan_view, 2 pm_count_scan, 3 pm_pcr_scan
   bool counting = false;              // a pm_count_scan is in its scan_range and the finals stay on the device
   uint64_t cnt_max = 0;               // its max_count
   bool cnt_dev = false;               // the tallies live on the device (else: cnt_host)
@@ -240,6 +240,22 @@ struct pm_handle {
   std::vector<uint64_t> cnt_host;     // host tally (k > 3 or 2^22 patterns and more)
   pm_count_info cinfo{};              // the host's share of pm_counts' info
   bool cnt_has_bogus = false;
+
+  // pcr_match's pairing stage (pm_pcr_setup .. pm_pcr_pair): DESIGN.md 5e
+  bool pcr_on = false;                // pm_pcr_setup was called since init
+  PcrDevice pcr;
+  void *pcr_mem[4] = {};              // patlen, size_lb, size_ub, entry_starts
+  uint32_t pcr_nmask[8] = {};         // bit c: stream code c decodes to N or n
+  pm_hit *d_held = nullptr;           // the held hits; pm_pcr_scan appends behind held_n
+  size_t held_cap = 0, held_n = 0;
+  bool pcr_scanning = false;          // a pm_pcr_scan is in its scan_range and the finals stay on the device
+  size_t pcr_fed = 0;                 // upper bound of the records the range's finalize stage left behind held_n
+  void *d_pcr_a = nullptr, *d_pcr_b = nullptr, *d_pcr_c = nullptr;   // a round's workspaces by held hits / by candidate pairs / by survivors
+  size_t pcr_a_bytes = 0, pcr_b_bytes = 0, pcr_c_bytes = 0;
+  void *pcr_out = nullptr;            // pinned: survivor records, then their strings
+  size_t pcr_out_bytes = 0;
+  unsigned long long *pcr_h_tot = nullptr;   // pinned: totals of a round's scans
+  uint64_t pcr_stat[6] = {};
 
   std::string err;
 };
@@ -461,11 +477,15 @@ static void count_free(pm_handle *h);
 static int count_clear(pm_handle *h);
 static int count_feed_device(pm_handle *h, const pm_hit *d_hits, const unsigned long long *d_count, size_t n_upper);
 static int count_collect(pm_handle *h, size_t nfin, std::vector<pm_hit> &extra, size_t *n_out);
+static void pcr_free(pm_handle *h);
+static int pcr_land_device(pm_handle *h, const pm_hit *d_hits, size_t n_upper);
+static int pcr_collect(pm_handle *h, size_t nfin, std::vector<pm_hit> &extra, size_t *n_out);
 
 static void free_device(pm_handle *h) {
   drain_spec(h);
   win_release(h);
   count_free(h);
+  pcr_free(h);
   if (h->land) (void)hipHostFree(h->land);
   h->land = nullptr; h->land_cap = h->land_n = h->land_pos = 0;
   if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
@@ -1685,6 +1705,8 @@ extern "C" int pm_reset(pm_handle *h) {
   h->halves_fresh = true;
   h->last_count = 0;
   h->scan_mode = 0;
+  h->held_n = 0; h->pcr_fed = 0; h->pcr_scanning = false;
+  for (uint64_t &v : h->pcr_stat) v = 0;
   return count_clear(h);
 }
 
@@ -2929,6 +2951,7 @@ static int ensure_fsorted(pm_handle *h, size_t n) {
 static int land_enqueue_sort(pm_handle *h, const pm_hit *d_hits, const unsigned long long *d_count, size_t n_upper, bool *sorted) {
   *sorted = false;
   if (h->counting) return count_feed_device(h, d_hits, d_count, n_upper);   // pm_count_scan: the finals are re-aligned where they are
+  if (h->pcr_scanning) return pcr_land_device(h, d_hits, n_upper);         // pm_pcr_scan: the finals join the held list in HBM
   if (n_upper == 0 || n_upper > (size_t)INT_MAX / 2 || !h->sort_dev) return PM_OK;
   { int rcw = ensure_sort_workspace(h, n_upper, false); if (rcw) return rcw; }
   { int rcp = ensure_fpat(h); if (rcp) return rcp; }
@@ -2954,6 +2977,7 @@ static int finalize_sync(pm_handle *h, const ScanNext *next) {
 // in (end, pid, k) order.  The copy runs on the copy stream: the handle's stream may hold the next range's scan.
 static int land_collect(pm_handle *h, const pm_hit *d_hits, bool sorted, size_t nfin, std::vector<pm_hit> &extra, size_t *n_out) {
   if (h->counting) return count_collect(h, nfin, extra, n_out);
+  if (h->pcr_scanning) return pcr_collect(h, nfin, extra, n_out);
   { int rcl = ensure_landing(h, nfin + extra.size()); if (rcl) return rcl; }
   pm_hit *dst = h->land + h->land_n;
   if (nfin) {
@@ -3044,7 +3068,7 @@ static int finalize_device_impl(pm_handle *h, const void *d_cands, size_t n, int
     // record buffer itself, which the next range's scan refills from slot 0.  The records move to d_fsorted on the handle's
     // stream, in front of that scan, and land from there; a list too long for that keeps the buffer: no scan behind it.
     ScanNext after = *next;
-    if (!sorted && !h->counting && n) {
+    if (!sorted && !h->counting && !h->pcr_scanning && n) {
       if (n <= (size_t)INT_MAX / 2) {
         { int rcf = ensure_fsorted(h, n); if (rcf) return rcf; }
         HIP_TRY(h, hipMemcpyAsync(h->d_fsorted, src, n * sizeof(pm_hit), hipMemcpyDeviceToDevice, h->stream));
@@ -3545,6 +3569,7 @@ extern "C" int pm_count_scan(pm_handle *h, int64_t begin, int64_t end, uint64_t 
   if (!h || !h->inited) return fail(h, PM_E_INVALID, "pm_count_scan: handle not initialised");
   if (h->host_only) return fail(h, PM_E_INVALID, "pm_count_scan: this handle runs the host stage only");
   if (h->scan_mode == 1) return fail(h, PM_E_INVALID, "pm_count_scan after pm_scan (pm_reset first)");
+  if (h->scan_mode == 3) return fail(h, PM_E_INVALID, "pm_count_scan after pm_pcr_scan (pm_reset first)");
   if (h->scan_mode == 2 && max_count != h->cnt_max) return fail(h, PM_E_INVALID, "pm_count_scan: max_count changed between two pm_reset()s");
   HIP_TRY(h, hipSetDevice(h->cfg.device));
   h->scan_mode = 2; h->cnt_max = max_count;
@@ -3644,6 +3669,13 @@ static int scan_piece(pm_handle *h, int64_t begin, int64_t end) {
       h->next_begin = end;
       return PM_OK;
     }
+    if (h->pcr_scanning) {                                            // (finalized on the host: the hits are uploaded to the held list)
+      h->pcr_fed = 0;
+      rc = pcr_collect(h, 0, outv, nullptr);
+      if (rc) return rc;
+      h->next_begin = end;
+      return PM_OK;
+    }
     rc = ensure_landing(h, outv.size());
     if (rc) return rc;
     if (!outv.empty()) memcpy(h->land + h->land_n, outv.data(), outv.size() * sizeof(pm_hit));
@@ -3695,6 +3727,7 @@ extern "C" int pm_scan(pm_handle *h, int64_t begin, int64_t end, pm_hit *out, si
   if (n_out) *n_out = 0;
   if (more) *more = 0;
   if (h->scan_mode == 2) return fail(h, PM_E_INVALID, "pm_scan after pm_count_scan (pm_reset first)");
+  if (h->scan_mode == 3) return fail(h, PM_E_INVALID, "pm_scan after pm_pcr_scan (pm_reset first)");
   h->scan_mode = 1;
   if (end > h->n) end = h->n;
   if (end > begin) { const int rc = scan_range(h, begin, end); if (rc) return rc; }
@@ -3712,6 +3745,7 @@ extern "C" int pm_scan_view(pm_handle *h, int64_t begin, int64_t end, const pm_h
   if (!h || !h->inited || !hits || !n) return fail(h, PM_E_INVALID, "pm_scan_view: bad arguments");
   *hits = nullptr; *n = 0;
   if (h->scan_mode == 2) return fail(h, PM_E_INVALID, "pm_scan_view after pm_count_scan (pm_reset first)");
+  if (h->scan_mode == 3) return fail(h, PM_E_INVALID, "pm_scan_view after pm_pcr_scan (pm_reset first)");
   h->scan_mode = 1;
   if (end > h->n) end = h->n;
   if (h->land_pos == h->land_n) h->land_pos = h->land_n = 0;       // the span of the last call is given up
@@ -3719,5 +3753,282 @@ extern "C" int pm_scan_view(pm_handle *h, int64_t begin, int64_t end, const pm_h
   *hits = h->land + h->land_pos;
   *n = h->land_n - h->land_pos;
   h->land_pos = h->land_n;                                          // handed out; the memory stays valid until the next call
+  return PM_OK;
+}
+
+// ---- pcr_match's pairing stage on the device ---------------------------------------------------
+// The held list d_held[0 .. held_n) is what the host loop keeps in its pattern_hit_vector: pm_pcr_scan lands a range's
+// finals behind it (one more landing beside pm_scan's and pm_count_scan's), pm_pcr_feed uploads records, pm_pcr_pair runs
+// one round of pcr_match.cc:987-1259 over it and leaves the deferred hits at its front.
+
+// (the records cross the ABI and ctypes by layout: tests/test_pcr_abi.py pins the same numbers on the Python side)
+static_assert(sizeof(pm_pcr_amplicon) == 96 && sizeof(pm_pcr_params) == 64, "pm_gpu.h: the layout of pm_pcr_amplicon / pm_pcr_params is part of ABI v1");
+
+static void pcr_free(pm_handle *h) {
+  for (void *&q : h->pcr_mem) { if (q) (void)hipFree(q); q = nullptr; }
+  void *dv[] = {h->d_held, h->d_pcr_a, h->d_pcr_b, h->d_pcr_c};
+  for (void *q : dv) if (q) (void)hipFree(q);
+  if (h->pcr_out) (void)hipHostFree(h->pcr_out);
+  if (h->pcr_h_tot) (void)hipHostFree(h->pcr_h_tot);
+  h->d_held = nullptr; h->d_pcr_a = h->d_pcr_b = h->d_pcr_c = nullptr; h->pcr_out = nullptr; h->pcr_h_tot = nullptr;
+  h->held_cap = h->held_n = h->pcr_fed = h->pcr_a_bytes = h->pcr_b_bytes = h->pcr_c_bytes = h->pcr_out_bytes = 0;
+  h->pcr = PcrDevice(); h->pcr_on = false; h->pcr_scanning = false;
+}
+
+static int bits_for(uint64_t v) { int b = 1; while (b < 64 && (v >> b)) ++b; return b; }
+
+extern "C" int pm_pcr_setup(pm_handle *h, const pm_pcr_params *p) {
+  if (!h || !p) return fail(h, PM_E_INVALID, "pm_pcr_setup: no handle or no parameters");
+  // (what the patterns and the parameters alone decide comes first: these answers need no device)
+  const size_t np = h->pats.size();
+  if (np == 0 || np % 4 != 0) return fail(h, PM_E_INVALID, "pm_pcr_setup: needs 2n patterns with n even: the primers of the pairs, then their reverse complements");
+  for (size_t i = 0; i < np; ++i)
+    if (h->pats[i].id != i + 1) return fail(h, PM_E_INVALID, "pm_pcr_setup: the patterns must have been added with ids 1..2n in order");
+  if (p->amplicon_min < 0) return fail(h, PM_E_INVALID, "pm_pcr_setup: amplicon_min must not be negative");
+  if ((p->size_lb != nullptr) != (p->size_ub != nullptr)) return fail(h, PM_E_INVALID, "pm_pcr_setup: size_lb and size_ub come together");
+  if (p->n_entries < 0 || (p->n_entries && !p->entry_starts)) return fail(h, PM_E_INVALID, "pm_pcr_setup: entry_starts missing");
+  for (int64_t i = 1; i < p->n_entries; ++i)
+    if (p->entry_starts[i] < p->entry_starts[i - 1]) return fail(h, PM_E_INVALID, "pm_pcr_setup: entry_starts must not decrease");
+  if (!h->inited) return fail(h, PM_E_INVALID, "pm_pcr_setup: handle not initialised (call it after pm_init)");
+  if (h->host_only || h->win != 0 || !(h->d_text || h->n == 0))
+    return fail(h, PM_E_UNSUPPORTED, "pm_pcr_setup: the pairing stage needs the whole stream in HBM (not a windowed or host-only handle)");
+  HIP_TRY(h, hipSetDevice(h->cfg.device));
+  const int cur_mode = h->scan_mode;
+  pcr_free(h);
+  PcrDevice &d = h->pcr;
+  d.rule.n = np / 2;
+  d.rule.any_orientation = p->any_orientation != 0; d.rule.length_between = p->length_between != 0;
+  d.rule.amplicon_min = p->amplicon_min; d.rule.amplicon_max = p->amplicon_max;
+  d.rule.size_slack = p->size_slack; d.rule.has_sizes = p->size_lb != nullptr;
+  d.rule.k = h->cfg.k; d.rule.slack = h->cfg.indels ? h->cfg.k : 1;
+  d.endbits = bits_for((uint64_t)h->n + 512); d.idbits = bits_for(np); d.kbits = 8;
+  if (d.endbits + d.idbits + d.kbits > 64) return fail(h, PM_E_UNSUPPORTED, "pm_pcr_setup: stream positions and pattern ids do not fit the 64-bit sort key");
+  std::vector<int32_t> patlen(np + 1, 0);
+  for (size_t i = 0; i < np; ++i) patlen[i + 1] = (int32_t)h->pats[i].s.size();
+  const size_t npairs = np / 4;
+  PM_TRY(dev_upload(h, &h->pcr_mem[0], patlen.data(), patlen.size() * 4, 4, "pcr patlen"));
+  if (p->size_lb) {
+    PM_TRY(dev_upload(h, &h->pcr_mem[1], p->size_lb, npairs * 8, 8, "pcr size_lb"));
+    PM_TRY(dev_upload(h, &h->pcr_mem[2], p->size_ub, npairs * 8, 8, "pcr size_ub"));
+  }
+  PM_TRY(dev_upload(h, &h->pcr_mem[3], p->entry_starts, (size_t)p->n_entries * 8, 8, "pcr entry_starts"));
+  d.patlen = (const int32_t *)h->pcr_mem[0]; d.size_lb = (const uint64_t *)h->pcr_mem[1]; d.size_ub = (const uint64_t *)h->pcr_mem[2];
+  d.entry_starts = (const int64_t *)h->pcr_mem[3]; d.n_entries = p->n_entries;
+  for (uint32_t &w : h->pcr_nmask) w = 0;
+  for (int c = 0; c < std::min(h->alpha.size, 256); ++c)
+    if (h->alpha.ch[c] == 'N' || h->alpha.ch[c] == 'n') h->pcr_nmask[c >> 5] |= 1u << (c & 31);
+  HIP_TRY(h, hipHostMalloc((void **)&h->pcr_h_tot, 4 * sizeof(unsigned long long), hipHostMallocDefault));
+  h->pcr_on = true;
+  h->scan_mode = cur_mode;
+  return PM_OK;
+}
+
+// room for `need` held records, the first held_n kept
+static int pcr_ensure_held(pm_handle *h, size_t need) {
+  if (h->held_cap >= need) return PM_OK;
+  const size_t cap = std::max<size_t>(need + need / 2, (size_t)1 << 16);
+  pm_hit *nh = nullptr;
+  HIP_TRY(h, hipMalloc((void **)&nh, cap * sizeof(pm_hit)));
+  if (h->held_n) {
+    const hipError_t e = hipMemcpyAsync(nh, h->d_held, h->held_n * sizeof(pm_hit), hipMemcpyDeviceToDevice, h->stream);
+    if (e != hipSuccess || stream_wait(h) != hipSuccess) { (void)hipFree(nh); return hipfail(h, e, "pm_pcr: growing the held list"); }
+  }
+  if (h->d_held) (void)hipFree(h->d_held);
+  h->d_held = nh; h->held_cap = cap;
+  return PM_OK;
+}
+
+extern "C" int pm_pcr_feed(pm_handle *h, const pm_hit *hits, size_t n) {
+  if (!h || !h->inited || !h->pcr_on) return fail(h, PM_E_INVALID, "pm_pcr_feed: pm_pcr_setup first");
+  if (n == 0) return PM_OK;
+  if (!hits) return fail(h, PM_E_INVALID, "pm_pcr_feed: no hits");
+  if (h->held_n + n >= ((size_t)1 << 31)) return fail(h, PM_E_UNSUPPORTED, "pm_pcr_feed: 2^31 or more held hits");
+  for (size_t i = 0; i < n; ++i)
+    if (hits[i].pid < 1 || hits[i].pid > h->pats.size() || hits[i].end < 0 || hits[i].end > h->n + 512)
+      return fail(h, PM_E_INVALID, "pm_pcr_feed: a hit with an unknown pattern id or an end outside the stream");
+  HIP_TRY(h, hipSetDevice(h->cfg.device));
+  PM_TRY(pcr_ensure_held(h, h->held_n + n));
+  HIP_TRY(h, hipMemcpyAsync(h->d_held + h->held_n, hits, n * sizeof(pm_hit), hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, stream_wait(h));
+  h->held_n += n;
+  return PM_OK;
+}
+
+// pm_pcr_scan's landing, first half (on the handle's stream, in front of the next range's scan): the records at d_hits --
+// n_upper bounds their number, which the host learns later -- are copied behind the held list
+static int pcr_land_device(pm_handle *h, const pm_hit *d_hits, size_t n_upper) {
+  h->pcr_fed = 0;
+  if (n_upper == 0) return PM_OK;
+  if (h->held_n + n_upper >= ((size_t)1 << 31)) return fail(h, PM_E_UNSUPPORTED, "pm_pcr_scan: 2^31 or more held hits");
+  PM_TRY(pcr_ensure_held(h, h->held_n + n_upper));
+  HIP_TRY(h, hipMemcpyAsync(h->d_held + h->held_n, d_hits, n_upper * sizeof(pm_hit), hipMemcpyDeviceToDevice, h->stream));
+  h->pcr_fed = n_upper;
+  return PM_OK;
+}
+
+// second half: nfin of them are hits; the host-decided `extra` are uploaded behind them
+static int pcr_collect(pm_handle *h, size_t nfin, std::vector<pm_hit> &extra, size_t *n_out) {
+  if (n_out) *n_out = nfin + extra.size();
+  if (h->pcr_fed == 0) nfin = 0;
+  h->pcr_fed = 0;
+  const size_t m = extra.size();
+  if (h->held_n + nfin + m >= ((size_t)1 << 31)) return fail(h, PM_E_UNSUPPORTED, "pm_pcr_scan: 2^31 or more held hits");
+  h->held_n += nfin;
+  if (m) {
+    for (pm_hit &x : extra) x.aux[0] = x.aux[1] = x.aux[2] = 0;
+    PM_TRY(pcr_ensure_held(h, h->held_n + m));
+    // (the handle's stream may hold the next range's scan: the copy stream; the first half's copy is done, the finalize stage was waited for)
+    HIP_TRY(h, hipMemcpyAsync(h->d_held + h->held_n, extra.data(), m * sizeof(pm_hit), hipMemcpyHostToDevice, h->copy_stream));
+    HIP_TRY(h, hipStreamSynchronize(h->copy_stream));
+    h->held_n += m;
+  }
+  return PM_OK;
+}
+
+extern "C" int pm_pcr_scan(pm_handle *h, int64_t begin, int64_t end, size_t *n_new) {
+  if (n_new) *n_new = 0;
+  if (!h || !h->inited || !h->pcr_on) return fail(h, PM_E_INVALID, "pm_pcr_scan: pm_pcr_setup first");
+  if (h->scan_mode == 1) return fail(h, PM_E_INVALID, "pm_pcr_scan after pm_scan (pm_reset first)");
+  if (h->scan_mode == 2) return fail(h, PM_E_INVALID, "pm_pcr_scan after pm_count_scan (pm_reset first)");
+  HIP_TRY(h, hipSetDevice(h->cfg.device));
+  h->scan_mode = 3;
+  if (end > h->n) end = h->n;
+  if (end <= begin) return PM_OK;
+  const size_t before = h->held_n;
+  h->pcr_scanning = true;
+  const int rc = scan_range(h, begin, end);
+  h->pcr_scanning = false;
+  if (rc) { h->held_n = std::min(h->held_n, before); return rc; }
+  if (n_new) *n_new = h->held_n - before;
+  return PM_OK;
+}
+
+namespace {
+struct Carver {                                                       // hands out 256-byte aligned pieces of one allocation
+  char *base; size_t at = 0;
+  explicit Carver(void *b) : base((char *)b) {}
+  template <class T> T *take(size_t count) { T *p = base ? (T *)(base + at) : nullptr; at += (count * sizeof(T) + 255) & ~(size_t)255; return p; }
+};
+}  // namespace
+
+static int pcr_grow(pm_handle *h, void **buf, size_t *have, size_t need, const char *what) {
+  if (*have >= need) return PM_OK;
+  *have = need + need / 4;
+  return dev_regrow(h, buf, *have, what);
+}
+
+extern "C" int pm_pcr_pair(pm_handle *h, int64_t scanned_to, int more, int with_strings, size_t stride, const pm_pcr_amplicon **out, size_t *n_out,
+                           const char **ops, const char **text) {
+  if (out) *out = nullptr;
+  if (n_out) *n_out = 0;
+  if (ops) *ops = nullptr;
+  if (text) *text = nullptr;
+  if (!h || !h->inited || !h->pcr_on) return fail(h, PM_E_INVALID, "pm_pcr_pair: pm_pcr_setup first");
+  if (!out || !n_out || (with_strings && (!ops || !text || stride == 0))) return fail(h, PM_E_INVALID, "pm_pcr_pair: bad arguments");
+  HIP_TRY(h, hipSetDevice(h->cfg.device));
+  // (pm_pcr_scan may have left the next range's look-ahead scan on the handle's stream.  The round queues behind it and
+  // waits for it: at the first of its stream_waits below, or already in ensure_sort_workspace when that has to grow --
+  // hipFree synchronises -- so the scan does not overlap the round as it overlaps pm_scan's host work; the round only
+  // starts with that range scanned.  Growing is safe for the same reason and because the scan refills the record buffer
+  // only: nothing here reads that, and a scan uses the sort workspace only when it is collected)
+  const size_t n = h->held_n;
+  h->pcr_stat[0] = n; h->pcr_stat[1] = h->pcr_stat[2] = 0;
+  if (n == 0) return PM_OK;
+  if (n >= ((size_t)1 << 31)) return fail(h, PM_E_UNSUPPORTED, "pm_pcr_pair: 2^31 or more held hits");
+  PM_TRY(ensure_sort_workspace(h, n, false));
+  // workspaces by held hits
+  PcrRound w;
+  const size_t temp_a = pcr_temp_bytes(n + 1);
+  auto carve_a = [&](void *base) {
+    Carver c(base);
+    w.sorted = c.take<pm_hit>(n); w.gpos_in = c.take<uint32_t>(n); w.gpos = c.take<uint32_t>(n);
+    w.def = c.take<uint32_t>(n + 1); w.flag = c.take<uint32_t>(n + 1); w.slot = c.take<uint32_t>(n + 1);
+    w.wlo = c.take<uint32_t>(2 * n); w.whi = c.take<uint32_t>(2 * n);
+    w.cnt = c.take<unsigned long long>(n + 1); w.off = c.take<unsigned long long>(n + 1);
+    w.temp = c.take<char>(temp_a); w.temp_bytes = temp_a;
+    return c.at;
+  };
+  PM_TRY(pcr_grow(h, &h->d_pcr_a, &h->pcr_a_bytes, carve_a(nullptr), "the pairing round's workspace"));
+  carve_a(h->d_pcr_a);
+  w.keys = h->d_keys; w.keys_alt = h->d_keys_alt;
+  if (temp_a <= h->ctemp_bytes) { w.temp = h->d_ctemp; w.temp_bytes = h->ctemp_bytes; }   // the handle's sort workspace where it is large enough
+  void *const temp_n = w.temp; const size_t temp_n_bytes = w.temp_bytes;
+  HIP_TRY(h, pcr_join_device(h->pcr, h->d_held, n, scanned_to, more != 0, w, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(h->pcr_h_tot, w.off + n, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, stream_wait(h));
+  const unsigned long long npairs = h->pcr_h_tot[0];
+  h->pcr_stat[1] = npairs;
+  if (npairs >= (1ull << 31)) return fail(h, PM_E_UNSUPPORTED, "pm_pcr_pair: 2^31 or more candidate pairs in one round (hit-dense text: pair more often, or narrow -M)");
+  size_t nsurv = 0;
+  if (npairs) {
+    // the pair list and what is sized by it; the hits that take part are at most two per pair and at most all
+    const size_t st = with_strings ? stride : 0, temp_b = pcr_temp_bytes((size_t)npairs + 1);
+    const size_t mmax = (size_t)std::min<unsigned long long>(n, 2 * npairs);
+    uint2 *d_pairs; uint32_t *d_keep, *d_kof; pm_hit *d_hv; pm_alignment *d_al; char *d_ops, *d_txt, *d_temp_b;
+    auto carve_b = [&](void *base) {
+      Carver c(base);
+      d_pairs = c.take<uint2>(npairs); d_keep = c.take<uint32_t>(npairs + 1); d_kof = c.take<uint32_t>(npairs + 1);
+      d_hv = c.take<pm_hit>(mmax); d_al = c.take<pm_alignment>(mmax); d_ops = c.take<char>(mmax * st); d_txt = c.take<char>(mmax * st);
+      d_temp_b = c.take<char>(temp_b);
+      return c.at;
+    };
+    PM_TRY(pcr_grow(h, &h->d_pcr_b, &h->pcr_b_bytes, carve_b(nullptr), "the pairing round's pair list"));
+    carve_b(h->d_pcr_b);
+    HIP_TRY(h, pcr_write_device(n, w, d_pairs, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->pcr_h_tot + 1, w.slot + n, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, pcr_gather_device(n, w, d_hv, h->stream));
+    HIP_TRY(h, stream_wait(h));
+    const size_t m = (size_t)*(const uint32_t *)(h->pcr_h_tot + 1);
+    const pm_count_info before = h->cinfo;
+    // (the strings are copied whole, stride bytes each: nothing stale behind their ends)
+    if (with_strings) { HIP_TRY(h, hipMemsetAsync(d_ops, 0, m * st, h->stream)); HIP_TRY(h, hipMemsetAsync(d_txt, 0, m * st, h->stream)); }
+    PM_TRY(pm_align_hits_device(h, d_hv, m, d_al, with_strings ? d_ops : nullptr, with_strings ? d_txt : nullptr, st));
+    h->pcr_stat[3] += h->cinfo.aligned_device - before.aligned_device;
+    h->pcr_stat[4] += h->cinfo.aligned_host - before.aligned_host;
+    h->pcr_stat[5] += h->cinfo.record_bytes_to_host - before.record_bytes_to_host;
+    h->cinfo = before;                                                // (pm_counts' info is pm_count_scan's)
+    w.temp = d_temp_b; w.temp_bytes = temp_b;
+    HIP_TRY(h, pcr_filter_device(h->pcr, w, d_pairs, (size_t)npairs, d_al, d_keep, d_kof, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->pcr_h_tot + 2, d_kof + npairs, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, stream_wait(h));
+    nsurv = (size_t)*(const uint32_t *)(h->pcr_h_tot + 2);
+    if (nsurv) {
+      // survivors and their strings: a device buffer of their own, copied into the pinned one in one piece
+      const size_t rec_bytes = (nsurv * sizeof(pm_pcr_amplicon) + 255) & ~(size_t)255, str_bytes = 2 * nsurv * st;
+      PM_TRY(pcr_grow(h, &h->d_pcr_c, &h->pcr_c_bytes, rec_bytes + 2 * str_bytes + 16, "the pairing round's survivors"));
+      void *const d_res = h->d_pcr_c;
+      pm_pcr_amplicon *d_rec = (pm_pcr_amplicon *)d_res;
+      char *d_sops = (char *)d_res + rec_bytes, *d_stxt = d_sops + str_bytes;
+      hipError_t e = hipSuccess;
+      if (h->pcr_out_bytes < rec_bytes + 2 * str_bytes) {
+        if (h->pcr_out) (void)hipHostFree(h->pcr_out);
+        h->pcr_out = nullptr; h->pcr_out_bytes = (rec_bytes + 2 * str_bytes) * 2;
+        e = hipHostMalloc(&h->pcr_out, h->pcr_out_bytes, hipHostMallocDefault);
+        if (e != hipSuccess) h->pcr_out_bytes = 0;
+      }
+      if (e == hipSuccess) e = pcr_emit_device(h->pcr, w, d_pairs, (size_t)npairs, d_keep, d_kof, nsurv, d_al, with_strings ? d_ops : nullptr, with_strings ? d_txt : nullptr, st,
+                                               h->d_text, h->n, h->pcr_nmask, d_rec, d_sops, d_stxt, h->stream);
+      if (e == hipSuccess) e = hipMemcpyAsync(h->pcr_out, d_res, rec_bytes + 2 * str_bytes, hipMemcpyDeviceToHost, h->stream);
+      if (e == hipSuccess) e = stream_wait(h);
+      if (e != hipSuccess) return hipfail(h, e, "pm_pcr_pair: survivors");
+      h->pcr_stat[5] += nsurv * sizeof(pm_pcr_amplicon) + 2 * str_bytes;
+      *out = (const pm_pcr_amplicon *)h->pcr_out;
+      if (with_strings) { *ops = (const char *)h->pcr_out + rec_bytes; *text = *ops + str_bytes; }
+    }
+  }
+  h->pcr_stat[2] = nsurv;
+  *n_out = nsurv;
+  // the deferred hits stay, at the front of the list
+  w.temp = temp_n; w.temp_bytes = temp_n_bytes;
+  HIP_TRY(h, pcr_carry_device(n, w, h->d_held, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(h->pcr_h_tot + 3, w.slot + n, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, stream_wait(h));
+  h->held_n = (size_t)*(const uint32_t *)(h->pcr_h_tot + 3);
+  return PM_OK;
+}
+
+extern "C" int pm_pcr_stats(pm_handle *h, uint64_t *out, int n) {
+  if (!h || !h->inited || !out || n < 0) return fail(h, PM_E_INVALID, "pm_pcr_stats: bad arguments");
+  for (int i = 0; i < n && i < 6; ++i) out[i] = h->pcr_stat[i];
   return PM_OK;
 }

@@ -8,6 +8,7 @@
 
 #include "../../include/pm_gpu.h"
 #include "pm_align.h"
+#include "pm_pcr.h"
 
 namespace pm {
 
@@ -187,6 +188,39 @@ hipError_t align_scatter_device(const uint64_t *d_idx, size_t m, const pm_alignm
 size_t tally_temp_bytes(size_t n);
 hipError_t tally_device(const AlignDevice &a, uint64_t *d_keys, uint64_t *d_keys_alt, uint64_t *d_scan, size_t n, void *d_temp, size_t temp_bytes,
                         uint64_t max_count, unsigned long long *d_counts, unsigned long long *d_info, hipStream_t st);
+
+// ---- pcr_match's pairing stage on the device (pm_pcr.hip) --------------------------
+struct PcrDevice {                               // uploaded by pm_pcr_setup
+  pcr::Rule rule{};
+  const int32_t *patlen = nullptr;               // [2n + 1] by pattern id
+  const uint64_t *size_lb = nullptr, *size_ub = nullptr;   // [n / 2] by primer pair - 1, or NULL
+  const int64_t *entry_starts = nullptr;
+  int64_t n_entries = 0;
+  int endbits = 0, idbits = 0, kbits = 0;        // sort key = end | id | k
+};
+struct PcrRound {                                // workspaces of one round over n held hits (n + 1 entries where a scan runs)
+  uint64_t *keys = nullptr, *keys_alt = nullptr; // [n] (the handle's sort workspace); after the join keys_alt holds the id-grouped keys
+  void *temp = nullptr; size_t temp_bytes = 0;   // pcr_temp_bytes(max(n, pairs) + 1)
+  pm_hit *sorted = nullptr;                      // [n] the held hits in (key, id, k) order
+  uint32_t *gpos_in = nullptr, *gpos = nullptr;  // [n] id-grouped order -> position in `sorted`
+  uint32_t *def = nullptr, *flag = nullptr, *slot = nullptr;   // [n + 1] deferred, takes part in a pair, exclusive scan of either
+  uint32_t *wlo = nullptr, *whi = nullptr;       // [2n] the alive part of the hit's two windows in the id-grouped order
+  unsigned long long *cnt = nullptr, *off = nullptr;   // [n + 1] pairs per hit and their exclusive scan (off[n] = all pairs)
+};
+size_t pcr_temp_bytes(size_t n);
+// sort, group, count pass and scan: afterwards w.off[n] is the number of candidate pairs and w.flag is zero
+hipError_t pcr_join_device(const PcrDevice &d, const pm_hit *d_held, size_t n, int64_t scanned_to, int more, const PcrRound &w, hipStream_t st);
+// write pass + scan of the flags: d_pairs[off[n]] = (position, partner's position); w.slot[n] = hits that take part
+hipError_t pcr_write_device(size_t n, const PcrRound &w, uint2 *d_pairs, hipStream_t st);
+hipError_t pcr_gather_device(size_t n, const PcrRound &w, pm_hit *d_out, hipStream_t st);
+// filter pass over the pairs and the alignments of the gathered hits: d_keep / d_kof [npairs + 1], d_kof[npairs] = survivors
+hipError_t pcr_filter_device(const PcrDevice &d, const PcrRound &w, const uint2 *d_pairs, size_t npairs, const pm_alignment *d_al, uint32_t *d_keep, uint32_t *d_kof, hipStream_t st);
+// survivor records (and the strings of both ends at (2q, 2q + 1) * stride when d_ops != NULL) + the N count; nmask: bit c = code c decodes to N or n
+hipError_t pcr_emit_device(const PcrDevice &d, const PcrRound &w, const uint2 *d_pairs, size_t npairs, const uint32_t *d_keep, const uint32_t *d_kof, size_t nsurv,
+                           const pm_alignment *d_al, const char *d_ops, const char *d_txt, size_t stride, const uint8_t *d_text, int64_t ntext,
+                           const uint32_t nmask[8], pm_pcr_amplicon *d_out, char *d_out_ops, char *d_out_txt, hipStream_t st);
+// deferred hits -> d_held[0 .. w.slot[n])
+hipError_t pcr_carry_device(size_t n, const PcrRound &w, pm_hit *d_held, hipStream_t st);
 
 // ---- edit distance for patterns of 16..19 characters (pm_short.hip) ------------------------------
 // First stage pm_short_edit_scan (field pairs of the last 16 bases, 14 tests at k = 2, 2 at k = 1) + the automaton stage of

@@ -2,6 +2,7 @@
 #include "gpu_pattern_match.h"
 
 #include <algorithm>
+#include <chrono>
 #include <climits>
 #include <cstdio>
 #include <cstdlib>
@@ -288,6 +289,30 @@ void GpuPatternMatch::count_patterns(CharacterProducer &cp, uint64_t max_count, 
   counts.assign(npat_ * (size_t)(k_ + 1), 0);
   capped.assign(npat_, 0);
   if (pm_counts(h_, counts.data(), capped.data(), npat_, info) != PM_OK) fatal("count_patterns");
+}
+
+bool GpuPatternMatch::resident() const {
+  int64_t r[1] = {1};
+  return !group_ && pm_stream_residency(h_, r, 1) == PM_OK && r[0] == 0;
+}
+
+bool GpuPatternMatch::pcr_round(CharacterProducer &cp, unsigned long minka, size_t stride, const pm_pcr_amplicon **out, size_t *n, const char **ops,
+                                const char **text, size_t *new_hits, double *scan_seconds) {
+  unsigned long got = 0;
+  const auto t0 = std::chrono::steady_clock::now();
+  while (!cp.eof()) {                                                         // find_patterns' walk
+    const int64_t begin = cp.pos();
+    const int64_t end = begin + chunk_ < n_ ? begin + chunk_ : n_;
+    size_t cnt = 0;
+    if (pm_pcr_scan(h_, begin, end, &cnt) != PM_OK) fatal("pcr_round (scan)");
+    cp.pos(end);
+    got += cnt;
+    if (got >= minka) break;
+  }
+  if (scan_seconds) *scan_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  if (new_hits) *new_hits = got;
+  if (pm_pcr_pair(h_, cp.pos(), got > 0, 1, stride, out, n, ops, text) != PM_OK) fatal("pcr_round (pair)");
+  return got > 0;
 }
 
 void GpuPatternMatch::reset() { if (pm_reset(h_) != PM_OK) fatal("reset"); }

@@ -124,6 +124,14 @@ class GpuPatternMatch {
   // pattern's hits across the shards.
   void count_patterns(CharacterProducer &cp, uint64_t max_count, std::vector<uint64_t> &counts, std::vector<uint8_t> &capped,
                       pm_count_info *info = nullptr);
+  // One round of pcr_match's scan + pairing loop with the pairing stage on the device (pm_pcr_scan / pm_pcr_pair, after a
+  // pm_pcr_setup on handle()): the ranges find_patterns would walk are scanned until >= minka hits have joined the held
+  // list or the stream ends, then the held hits are paired with scanned_to = cp.pos().  Returns what find_patterns would
+  // (hits arrived); the survivors and their strings (at (2i, 2i + 1) * stride) lie in the handle's pinned buffer until the
+  // next call.  *new_hits: hits that arrived, *scan_seconds: the share of pm_pcr_scan.
+  bool pcr_round(CharacterProducer &cp, unsigned long minka, size_t stride, const pm_pcr_amplicon **out, size_t *n, const char **ops,
+                 const char **text, size_t *new_hits, double *scan_seconds);
+  bool resident() const;                                                      // the whole stream is in HBM (no windows, one rank)
   bool sharded() const { return group_ != nullptr; }
   int selected_semantics() const;
   int selected_kernel() const;

@@ -351,6 +351,96 @@ int main(int argc, char **argv) {
   const int slack = opt.with_indels ? opt.max_edits : 1;
   pattern_hit_vector l;
   StsEntry null_sts;
+  const bool wants_amplicon = opt.hit_format.find("%@") != std::string::npos || opt.hit_format.find("%*") != std::string::npos;
+  // one surviving pair through alignformat (:1161-1217): the hit that was processed, its partner, their re-alignments and
+  // strings.  count_here: the N's are counted from the host stream (the device route brings its own count and reads the
+  // amplicon text only when the format prints it)
+  auto report = [&](unsigned long pid, unsigned long pid1, const pm_alignment &pa, const pm_alignment &pa1, const char *ops_a, const char *mt_a,
+                    const char *ops_b, const char *mt_b, long amplicon_len, bool count_here, unsigned long ncount) {
+    const long long len = pa.end - pa.start + 1, len1 = pa1.end - pa1.start + 1;
+    const long long spe = db.get_seq_pos(pa.end), spe1 = db.get_seq_pos(pa1.end);
+    const long long sps = spe - len + 1, sps1 = spe1 - len1 + 1;
+    const long long pe = pa.end, pe1 = pa1.end, ps = pe - len + 1, ps1 = pe1 - len1 + 1;
+    bool rc = pid > n, rc1 = pid1 > n;
+    const unsigned long ind = pid - (rc ? n : 0), ind1 = pid1 - (rc1 ? n : 0);
+    const unsigned long pind = ind < ind1 ? ind / 2 + 1 : ind1 / 2 + 1;
+    const StsEntry &stsref = opt.primers_from_sts ? stsarray[pind] : null_sts;
+    if (opt.both_strands) {
+      if (ind % 2 == 0) rc = !rc;
+      else if (ind1 % 2 == 0) rc1 = !rc1;
+    }
+    const HeaderData &h = db.get_header_data(pa.end);
+    PairFields x;
+    x.ncount = ncount;
+    if (count_here || wants_amplicon) {
+      x.amplicon.resize((size_t)amplicon_len);
+      unsigned long ns = 0;
+      for (long i = 0; i < amplicon_len; ++i) {
+        const int64_t q = ps + i;
+        const char ch = q >= 0 && q < db.length() ? ff.ch(ff.code_at(q)) : '\0';
+        x.amplicon[(size_t)i] = ch;
+        if (ch == 'N' || ch == 'n') ++ns;
+      }
+      if (count_here) x.ncount = ns;
+    }
+    const std::string ops(ops_a), mt(mt_a), ops1(ops_b), mt1(mt_b);
+    x.a = End{sps, spe, rc ? spe : sps, rc ? sps : spe, ps, pe, (unsigned)pa.editdist, patarray[ind],
+              opt.primers_from_fasta ? patdefarray[ind] : std::string(), patarray[pid], with_gaps(patarray[pid], ops, '^'),
+              rc ? "R" : "F", rc ? " REVCOMP" : "", mt, with_gaps(mt, ops, 'v'), ops};
+    x.b = End{sps1, spe1, rc1 ? spe1 : sps1, rc1 ? sps1 : spe1, ps1, pe1, (unsigned)pa1.editdist, patarray[ind1],
+              opt.primers_from_fasta ? patdefarray[ind1] : std::string(), patarray[pid1], with_gaps(patarray[pid1], ops1, '^'),
+              rc1 ? "R" : "F", rc1 ? " REVCOMP" : "", mt1, with_gaps(mt1, ops1, 'v'), ops1};
+    x.i = pind; x.sts = &stsref; x.ppo = ind < ind1;
+    x.h = h.header; x.H = h.short_header; x.f = h.index;
+    alignformat(out, opt.hit_format, x);
+    ++npairs;
+  };
+
+  // ---- the pairing stage on the GPU (PM_GPU_PCR=1, one rank, the whole stream in HBM) ----------
+  const char *env_pcr = getenv("PM_GPU_PCR");
+  if (env_pcr && std::string(env_pcr) == "1" && ranks.single() && pm.resident()) {
+    std::vector<uint64_t> lb, ub;
+    if (opt.primers_from_sts)
+      for (size_t i = 1; i < stsarray.size(); ++i) { lb.push_back(stsarray[i].sizelb); ub.push_back(stsarray[i].sizeub); }
+    pm_pcr_params pp{};
+    pp.any_orientation = opt.any_orientation; pp.length_between = opt.length_between;
+    pp.amplicon_min = opt.amplicon_min; pp.amplicon_max = opt.amplicon_max; pp.size_slack = opt.size_slack;
+    pp.size_lb = opt.primers_from_sts ? lb.data() : nullptr; pp.size_ub = opt.primers_from_sts ? ub.data() : nullptr;
+    pp.entry_starts = db.entry_starts().data(); pp.n_entries = (int64_t)db.entry_starts().size();
+    const int rcs = pm_pcr_setup(pm.handle(), &pp);
+    if (rcs == PM_OK) {
+      uint64_t st[6] = {0, 0, 0, 0, 0, 0}, cands = 0;
+      for (;;) {
+        const auto ts0 = std::chrono::steady_clock::now();
+        const pm_pcr_amplicon *amp = nullptr;
+        const char *ops = nullptr, *txt = nullptr;
+        size_t namp = 0, got = 0;
+        double scan_s = 0;
+        const bool more = pm.pcr_round(ff, opt.progress_every, stride, &amp, &namp, &ops, &txt, &got, &scan_s);
+        t_scan += scan_s;
+        nhits += got;
+        (void)pm_pcr_stats(pm.handle(), st, 6);
+        cands += st[1];
+        if (!more && st[0] == 0) break;
+        for (size_t i = 0; i < namp; ++i)
+          report(amp[i].hit[0].pid, amp[i].hit[1].pid, amp[i].al[0], amp[i].al[1], ops + (2 * i) * stride, txt + (2 * i) * stride,
+                 ops + (2 * i + 1) * stride, txt + (2 * i + 1) * stride, (long)amp[i].amplicon_len, false, amp[i].ncount);
+        t_pair += std::chrono::duration<double>(std::chrono::steady_clock::now() - ts0).count() - scan_s;
+      }
+      if (opt.chatty)
+        fprintf(stderr, "scan (find_patterns) %.3f s, pairing + re-align + report %.3f s, %lu primer hits, %lu amplicons; pairing on the GPU: %llu candidate pairs, "
+                "%llu hits re-aligned on the device, %llu on the host, %llu bytes to the host\n", t_scan, t_pair, nhits, npairs,
+                (unsigned long long)cands, (unsigned long long)st[3], (unsigned long long)st[4], (unsigned long long)st[5]);
+      ph.mark("Scanned sequence database");
+      out.flush();
+      fflush(stdout);
+      fflush(stderr);
+      if (!opt.out_path.empty()) fout.close();
+      _exit(0);
+    }
+    if (rcs != PM_E_UNSUPPORTED) { fprintf(stderr, "Fatal error: pm_pcr_setup: %s\n", pm_last_error(pm.handle())); return 1; }
+    // (an option set the device route does not take: the host loop below)
+  }
   for (;;) {
     const auto ts0 = std::chrono::steady_clock::now();
     const size_t before = l.size();
@@ -436,45 +526,18 @@ int main(int argc, char **argv) {
       const pm_alignment &pa = al[slot[ja]], &pa1 = al[slot[jb]];
       if (pa.editdist < 0 || pa.editdist > opt.max_edits || pa1.editdist < 0 || pa1.editdist > opt.max_edits) continue;
       const unsigned long pid = l[ja].id, pid1 = l[jb].id;
-      const long long len = pa.end - pa.start + 1, len1 = pa1.end - pa1.start + 1;
-      const long long spe = db.get_seq_pos(pa.end), spe1 = db.get_seq_pos(pa1.end);
-      const long long sps = spe - len + 1, sps1 = spe1 - len1 + 1;
-      const long long pe = pa.end, pe1 = pa1.end, ps = pe - len + 1, ps1 = pe1 - len1 + 1;
-      bool rc = pid > n, rc1 = pid1 > n;
+      const long long pe = pa.end, pe1 = pa1.end, ps = pa.start, ps1 = pa1.start;
+      const bool rc = pid > n, rc1 = pid1 > n;
       const unsigned long ind = pid - (rc ? n : 0), ind1 = pid1 - (rc1 ? n : 0);
       const unsigned long pind = ind < ind1 ? ind / 2 + 1 : ind1 / 2 + 1;
       const StsEntry &stsref = opt.primers_from_sts ? stsarray[pind] : null_sts;
-      if (opt.both_strands) {
-        if (ind % 2 == 0) rc = !rc;
-        else if (ind1 % 2 == 0) rc1 = !rc1;
-      }
       const long amplicon_len = !opt.length_between ? (long)(pe1 - ps) : (long)(ps1 - pe);
       if (!(db.is_subseq(ps, pe1) && amplicon_len <= opt.amplicon_max && amplicon_len >= opt.amplicon_min &&
             (!opt.primers_from_sts || opt.size_slack < 0 ||
              (((unsigned long)(amplicon_len + opt.size_slack) >= stsref.sizelb) && (amplicon_len <= (long)((int)stsref.sizeub) + opt.size_slack)))))
         continue;
-      const HeaderData &h = db.get_header_data(pa.end);
-      PairFields x;
-      x.amplicon.resize((size_t)amplicon_len);
-      x.ncount = 0;
-      for (long i = 0; i < amplicon_len; ++i) {
-        const int64_t q = ps + i;
-        const char ch = q >= 0 && q < db.length() ? ff.ch(ff.code_at(q)) : '\0';
-        x.amplicon[(size_t)i] = ch;
-        if (ch == 'N' || ch == 'n') ++x.ncount;
-      }
-      const std::string ops(opsbuf.data() + slot[ja] * stride), mt(textbuf.data() + slot[ja] * stride);
-      const std::string ops1(opsbuf.data() + slot[jb] * stride), mt1(textbuf.data() + slot[jb] * stride);
-      x.a = End{sps, spe, rc ? spe : sps, rc ? sps : spe, ps, pe, (unsigned)pa.editdist, patarray[ind],
-                opt.primers_from_fasta ? patdefarray[ind] : std::string(), patarray[pid], with_gaps(patarray[pid], ops, '^'),
-                rc ? "R" : "F", rc ? " REVCOMP" : "", mt, with_gaps(mt, ops, 'v'), ops};
-      x.b = End{sps1, spe1, rc1 ? spe1 : sps1, rc1 ? sps1 : spe1, ps1, pe1, (unsigned)pa1.editdist, patarray[ind1],
-                opt.primers_from_fasta ? patdefarray[ind1] : std::string(), patarray[pid1], with_gaps(patarray[pid1], ops1, '^'),
-                rc1 ? "R" : "F", rc1 ? " REVCOMP" : "", mt1, with_gaps(mt1, ops1, 'v'), ops1};
-      x.i = pind; x.sts = &stsref; x.ppo = ind < ind1;
-      x.h = h.header; x.H = h.short_header; x.f = h.index;
-      alignformat(out, opt.hit_format, x);
-      ++npairs;
+      report(pid, pid1, pa, pa1, opsbuf.data() + slot[ja] * stride, textbuf.data() + slot[ja] * stride, opsbuf.data() + slot[jb] * stride,
+             textbuf.data() + slot[jb] * stride, amplicon_len, true, 0);
     }
 
     // keep only the hits whose window is not complete yet (:1222-1252)

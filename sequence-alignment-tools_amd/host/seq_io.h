@@ -64,6 +64,7 @@ class SeqDb {
   const HeaderData &get_header_data(int64_t pos);    // fasta_io.t:186-194
   bool is_subseq(int64_t start, int64_t end);        // fasta_io.t:204-214
   size_t entries() const { return keys_.size(); }
+  const std::vector<int64_t> &entry_starts() const { return keys_; }   // stream position of every entry's first character
  private:
   bool locate(int64_t pos, size_t *idx) const;       // last entry with key <= pos-1
   StreamChars *chars_ = nullptr;

@@ -11,6 +11,8 @@ _LIB = None
 
 HIT_DTYPE = np.dtype([("end", "<i8"), ("pid", "<u4"), ("k", "u1"), ("aux", "u1", (3,))])
 ALIGNMENT_DTYPE = np.dtype([("start", "<i8"), ("end", "<i8"), ("editdist", "<i4"), ("value", "<i4")])
+# pm_pcr_amplicon: the processed hit and its partner, their re-alignments, the amplicon length, pind and the N count
+PCR_AMPLICON_DTYPE = np.dtype([("hit", HIT_DTYPE, (2,)), ("al", ALIGNMENT_DTYPE, (2,)), ("amplicon_len", "<i8"), ("pair", "<u4"), ("ncount", "<u4")])
 
 SEM_AUTO, SEM_KEYWORD_TREE, SEM_SHIFT_AND, SEM_FILTER_BITVEC = 0, 2, 4, 5
 SEM_EXACT_BASES, SEM_EXACT_HALVES, SEM_SHIFT_AND_INEXACT = 8, 12, 100
@@ -28,6 +30,7 @@ ABI_SYMBOLS = [
     "pm_init_windowed", "pm_stream_residency", "pm_device_memory",
     "pm_init_packed", "pm_unpack_device", "pm_unpack_codes", "pm_pack_codes",
     "pm_align_hits_device", "pm_count_scan", "pm_counts",
+    "pm_pcr_setup", "pm_pcr_feed", "pm_pcr_scan", "pm_pcr_pair", "pm_pcr_stats",
     "pm_comm_unique_id", "pm_comm_create", "pm_comm_gather", "pm_comm_destroy", "pm_comm_last_error",
 ]
 
@@ -47,6 +50,13 @@ class _CountInfo(C.Structure):
     """pm_count_info"""
     _fields_ = [("tallied", C.c_uint64), ("skipped", C.c_uint64), ("aligned_device", C.c_uint64), ("aligned_host", C.c_uint64),
                 ("bogus", C.c_uint64), ("record_bytes_to_host", C.c_uint64), ("first_bogus", _Hit)]
+
+
+class _PcrParams(C.Structure):
+    """pm_pcr_params"""
+    _fields_ = [("any_orientation", C.c_int32), ("length_between", C.c_int32), ("amplicon_min", C.c_int64), ("amplicon_max", C.c_int64),
+                ("size_slack", C.c_int32), ("reserved", C.c_int32), ("size_lb", C.c_void_p), ("size_ub", C.c_void_p),
+                ("entry_starts", C.c_void_p), ("n_entries", C.c_int64)]
 
 
 class _Config(C.Structure):
@@ -135,6 +145,12 @@ def load_library():
         L.pm_align_hits_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
         L.pm_count_scan.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_uint64]
         L.pm_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(_CountInfo)]
+        L.pm_pcr_setup.argtypes = [C.c_void_p, C.POINTER(_PcrParams)]
+        L.pm_pcr_feed.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.pm_pcr_scan.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_size_t)]
+        L.pm_pcr_pair.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                  C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+        L.pm_pcr_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         _LIB = L
     return _LIB
 
@@ -518,6 +534,71 @@ class PatternMatch:
             self.count_scan(pos, end, max_count)
             pos = end
         return self.counts()
+
+    # -- pcr_match's pairing stage on the device (pm_pcr_*) ----------------------------------------
+    def pcr_setup(self, any_orientation=False, length_between=False, amplicon_min=0, amplicon_max=2000, size_slack=-1,
+                  size_lb=None, size_ub=None, entry_starts=(0,)):
+        """pm_pcr_setup, after init(): the options of pcr_match's pairing stage (-a, -b, -m, -M, -d), the UniSTS size
+        bounds per primer pair (or None) and the stream positions where the FASTA entries start.  The patterns are the
+        primers with ids 1..n (2j-1 forward, 2j reverse) and their reverse complements n+1..2n."""
+        p = _PcrParams()
+        p.any_orientation, p.length_between = int(bool(any_orientation)), int(bool(length_between))
+        p.amplicon_min, p.amplicon_max, p.size_slack = int(amplicon_min), int(amplicon_max), int(size_slack)
+        keep = []
+        if size_lb is not None:
+            lb = np.ascontiguousarray(np.asarray(size_lb, dtype=np.uint64))
+            ub = np.ascontiguousarray(np.asarray(size_ub, dtype=np.uint64))
+            if lb.size != self._npat // 4 or ub.size != lb.size:
+                raise PmError(-1, "pcr_setup: one size_lb / size_ub per primer pair")
+            keep += [lb, ub]
+            p.size_lb, p.size_ub = lb.ctypes.data, ub.ctypes.data
+        es = np.ascontiguousarray(np.asarray(entry_starts, dtype=np.int64))
+        keep.append(es)
+        p.entry_starts, p.n_entries = (es.ctypes.data if es.size else None), es.size
+        self._check(self._L.pm_pcr_setup(self._h, C.byref(p)))
+
+    def pcr_feed(self, hits):
+        """pm_pcr_feed: append final hits (HIT_DTYPE) to the list the handle holds in HBM."""
+        hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+        self._check(self._L.pm_pcr_feed(self._h, hits.ctypes.data_as(C.c_void_p), hits.size))
+
+    def pcr_scan(self, begin, end):
+        """pm_pcr_scan: the final hits of (begin, end] join the held list in HBM; returns how many."""
+        n = C.c_size_t()
+        self._check(self._L.pm_pcr_scan(self._h, begin, end, C.byref(n)))
+        self._pos = min(self._n, max(self._pos, end))
+        return n.value
+
+    def pcr_pair(self, scanned_to, more, text=False, stride=0):
+        """pm_pcr_pair: one pairing round over the held hits.  Returns the surviving pairs as a PCR_AMPLICON_DTYPE array
+        (a copy), or with text=True (survivors, alignment strings, matching texts), the strings as lists of (first hit's,
+        partner's) per survivor.  stride: bytes per string (at least the longest pattern + k + 2, as align_hits_text)."""
+        stride = max(int(stride), self._maxlen + self._k + 2)
+        out, ops, txt, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_size_t()
+        self._check(self._L.pm_pcr_pair(self._h, int(scanned_to), int(bool(more)), int(bool(text)), stride, C.byref(out), C.byref(n),
+                                        C.byref(ops), C.byref(txt)))
+        m = n.value
+        if m:
+            rec = np.ctypeslib.as_array(C.cast(out, C.POINTER(C.c_uint8)), shape=(m * PCR_AMPLICON_DTYPE.itemsize,)).view(PCR_AMPLICON_DTYPE).copy()
+        else:
+            rec = np.zeros(0, dtype=PCR_AMPLICON_DTYPE)
+        if not text:
+            return rec
+        def cut(p):
+            if not m:
+                return []
+            raw = C.string_at(p, 2 * m * stride)
+            s = [raw[i * stride:(i + 1) * stride].split(b"\0", 1)[0].decode("latin-1") for i in range(2 * m)]
+            return [(s[2 * i], s[2 * i + 1]) for i in range(m)]
+        return rec, cut(ops), cut(txt)
+
+    def pcr_stats(self):
+        """pm_pcr_stats: hits held before / candidate pairs / survivors of the last round; hits re-aligned on the device / on
+        the host and bytes copied device -> host since reset()"""
+        v = (C.c_uint64 * 6)()
+        self._check(self._L.pm_pcr_stats(self._h, v, 6))
+        names = ("held", "candidates", "survivors", "aligned_device", "aligned_host", "bytes_to_host")
+        return {k: int(v[i]) for i, k in enumerate(names)}
 
     def selected(self):
         return self._L.pm_selected_semantics(self._h), self._L.pm_selected_kernel(self._h)
