@@ -83,6 +83,7 @@ typedef enum {
 #define PM_LONG_EXACT 2    /* k = 0: patterns of 33..64 characters may run on the seed (Bloom) plan */
 #define PM_LONG_EDITS 4    /* -k 1 / -k 2: patterns of 33..64 characters may run on the edit plan */
 #define PM_LONG_HALVES 8   /* -k 1 / -k 2 under exact_halves: patterns of 33..64 characters may run on the halves plan */
+#define PM_LONG_ALIGN 16   /* -k 1 .. -k 3 (edits): hits of patterns of 33..64 characters are re-aligned on the device */
 
 /* Replaces the constructor arguments of the reference engines as pick_pattern_index passes them
  * (select.cc:19-30): nmismatch, indels, wildcard, textn, eos.  dna_mut is not supported. */
@@ -96,7 +97,8 @@ typedef struct {
   int32_t text_n;          /* -W: a text N also matches (shift_and.cc:112) */
   int32_t eos;             /* raw end-of-sequence char, '\n' in the CLIs */
   int32_t device;          /* HIP device ordinal */
-  int32_t long_patterns;   /* a bit set (PM_LONG_SUB | PM_LONG_EXACT | PM_LONG_EDITS | PM_LONG_HALVES; 0 = the routing of earlier versions).
+  int32_t long_patterns;   /* a bit set (PM_LONG_SUB | PM_LONG_EXACT | PM_LONG_EDITS | PM_LONG_HALVES | PM_LONG_ALIGN; 0 = the routing of
+                              earlier versions).
                               PM_LONG_SUB (1) = with PM_KERNEL_AUTO, -K 1 / -K 2 (substitutions only) and filter_bitvec, bare
                               shift_and_inexact or exact_halves on an A,C,G,T-normalized or raw ASCII stream, patterns
                               of 33..64 characters (A,C,G,T; or <= 16 concrete variants under -w on a plain stream)
@@ -117,7 +119,11 @@ typedef struct {
                               bases the lane carries, by pm_half_verify_wide on 64-byte records, and extended by
                               pm_seed_extend on rows of 32 codes.
                               A bit not set = they go to the bit-parallel kernels, as does every pattern of 65
-                              characters or more either way.  Each bit acts on its own option sets only.  (Took the
+                              characters or more either way.  Each bit acts on its own option sets only.
+                              PM_LONG_ALIGN (16) is no routing bit: it changes no scan kernel and not pm_describe.  With
+                              indels and 1 <= k <= 3, pm_align_hits_device, pm_count_scan and pm_pcr_pair re-align the
+                              records of patterns of 33..64 characters on the device (pm_align_hits_wide_kernel), whichever
+                              kernels found them; not set, the host aligns them as before.  (Took the
                               place of reserved[0]: same layout, same PM_ABI_VERSION.) */
   int32_t reserved[6];
 } pm_config;

@@ -9,6 +9,8 @@
 //   pm_align_hits_kernel   one lane per 16-byte hit record: the banded DP on characters (stream codes mapped through
 //                          the handle's table, patterns as the caller added them), traceback, pm_alignment and --
 //                          optionally -- the alignment string and the matching text, or one 64-bit tally key
+//   pm_align_hits_wide_kernel   the same banded DP for patterns of 33..64 characters (PM_LONG_ALIGN), over the list of records
+//                          the kernel above left on the device; its per-record code is pm_align_wide.h
 //   pm_tally_flags/decide/add   the tally over the sorted keys  pattern index(22) | end(39) | distance code(3)
 //
 // Everything a lane indexes at run time lives in LDS, byte i of lane t at i * AL_THREADS + t (a runtime-indexed
@@ -19,6 +21,7 @@
 
 #include <cstring>
 
+#include "pm_align_wide.h"
 #include "pm_internal.h"
 #include "pm_iupac.h"
 
@@ -258,6 +261,60 @@ __global__ __launch_bounds__(AL_THREADS) void pm_align_hits_kernel(AlignDevice a
   }
 }
 
+// The banded DP for patterns of 33..64 characters (PM_LONG_ALIGN; a.indels != 0, 1 <= a.k and 2 * a.k + 2 <= W): one lane
+// per record of the list pm_align_hits_kernel left on the device -- side_hits[j], the record's place side_idx[j] in the
+// caller's arrays, ctr[0] of them -- through align_wide_record (pm_align_wide.h), on the lane's column of the block's
+// LDS.  One instance per band width: W = 4, 6, 8 hold 25,600 / 34,176 / 42,752 bytes per block.  Results
+// go where the narrow kernel would have put them; what this kernel cannot take either (more than 64 characters, an empty
+// pattern) is compacted into rest_hits / rest_idx and counted in ctr[3].
+static_assert(ALW_LANES == AL_THREADS && ALW_MAXL == AL_MAXL_WIDE && ALW_MAXK == AL_MAXK, "pm_align_wide.h and pm_internal.h disagree");
+template <int W>
+__global__ __launch_bounds__(AL_THREADS) void pm_align_hits_wide_kernel(AlignDevice a, const uint8_t *text, int64_t ntext, const pm_hit *side_hits,
+                                                                        const uint64_t *side_idx, size_t n_upper, pm_alignment *out, char *ops, char *txt,
+                                                                        size_t stride, uint64_t *keys, pm_hit *rest_hits, uint64_t *rest_idx,
+                                                                        unsigned long long *ctr) {
+  __shared__ uint8_t lds[alw_lane_bytes<W>() * AL_THREADS];
+  const size_t j = blockIdx.x * (size_t)AL_THREADS + threadIdx.x;
+  size_t n = n_upper;
+  if ((size_t)ctr[0] < n) n = (size_t)ctr[0];
+  if (j >= n) return;
+  const pm_hit h = side_hits[j];
+  const size_t i = (size_t)side_idx[j];
+  const uint8_t *ch = a.tab;
+  const uint32_t *mask = (const uint32_t *)(a.tab + 256);
+  const int k = a.k;
+  int nops = 0, ntxt = 0;
+  bool fits = true;
+  char *myops = ops ? ops + i * stride : nullptr, *mytxt = ops ? txt + i * stride : nullptr;
+  auto put_op = [&](char c) { if (myops) { if ((size_t)nops + 1 < stride) myops[nops] = c; else fits = false; ++nops; } };
+  auto put_tx = [&](char c) { if (mytxt) { if ((size_t)ntxt + 1 < stride) mytxt[ntxt] = c; else fits = false; ++ntxt; } };
+  auto tchar = [&](int64_t q) -> int { return (int)ch[q < ntext ? text[q] : (uint8_t)0]; };   // q >= 0; beyond the stream: code 0
+
+  uint32_t lo = 0, hi = a.npat;                                     // first rank with ids_sorted[rank] >= pid (the narrow kernel found it)
+  while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (a.ids_sorted[mid] < h.pid) lo = mid + 1; else hi = mid; }
+  const bool known = lo < a.npat && a.ids_sorted[lo] == h.pid;
+  const uint32_t idx = known ? a.perm[lo] : 0;
+  const int L = known ? (int)(a.poff[idx + 1] - a.poff[idx]) : 0;
+  if (L <= AL_MAXL || L > AL_MAXL_WIDE) {                           // not this kernel's either: the host aligns the record
+    const unsigned long long o = wave_slot(ctr + 3);
+    if (rest_hits) rest_hits[o] = h;
+    if (rest_idx) rest_idx[o] = (uint64_t)i;
+    return;
+  }
+  WideOptions opt;
+  opt.k = k; opt.eos = a.eos; opt.wc = a.wc; opt.tn = a.tn;
+  WideAlignment w;
+  if (!align_wide_record<W>(WideLds<W>(lds, (int)threadIdx.x), opt, mask, a.pchars + a.poff[idx], L, a.esb[idx], a.eeb[idx], h.end, tchar, put_op, put_tx, &w))
+    nops = 0;
+  if (out) { pm_alignment r; r.start = w.start; r.end = w.end; r.editdist = w.editdist; r.value = w.value; out[i] = r; }
+  if (myops) {
+    myops[(size_t)nops + 1 <= stride ? nops : 0] = 0;
+    mytxt[(size_t)ntxt + 1 <= stride ? ntxt : 0] = 0;
+    if (!fits) atomicAdd(ctr + 2, 1ull);
+  }
+  if (keys) keys[i] = tally_key(idx, h.end, (w.editdist < 0 || w.editdist > k) ? TALLY_BOGUS : w.editdist);
+}
+
 // ---- the tally -------------------------------------------------------------------------------------------------
 // Sorted keys put every pattern's hits of the range side by side in order of stream end.  The cap needs, per hit, the
 // pattern's total so far (the sum of its tallies of the earlier ranges) plus the number of tallied hits before it in its
@@ -380,6 +437,24 @@ hipError_t align_hits_device(const AlignDevice &a, const uint8_t *d_text, int64_
   const unsigned blocks = (unsigned)((n_upper + AL_THREADS - 1) / AL_THREADS);
   hipLaunchKernelGGL(pm_align_hits_kernel, dim3(blocks), dim3(AL_THREADS), 0, st, a, d_text, ntext, d_hits, d_count, n_upper, d_out, d_ops, d_txt,
                      stride, d_keys, d_hostq_hits, d_hostq_idx, d_ctr);
+  return hipGetLastError();
+}
+
+hipError_t align_hits_wide_device(const AlignDevice &a, const uint8_t *d_text, int64_t ntext, const pm_hit *d_side_hits, const uint64_t *d_side_idx,
+                                  size_t n_upper, pm_alignment *d_out, char *d_ops, char *d_txt, size_t stride, uint64_t *d_keys,
+                                  pm_hit *d_rest_hits, uint64_t *d_rest_idx, unsigned long long *d_ctr, hipStream_t st) {
+  if (!a.indels || a.k < 1 || a.k > AL_MAXK || !d_side_hits || !d_side_idx) return hipErrorInvalidValue;
+  hipError_t e = hipMemsetAsync(d_ctr + 3, 0, sizeof(unsigned long long), st);
+  if (e != hipSuccess || n_upper == 0) return e;
+  // the grid covers the most the list can hold; blocks beyond its count exit at once
+  const dim3 blocks((unsigned)((n_upper + AL_THREADS - 1) / AL_THREADS)), threads(AL_THREADS);
+#define PM_WIDE_LAUNCH(W)                                                                                                                        \
+  hipLaunchKernelGGL(pm_align_hits_wide_kernel<W>, blocks, threads, 0, st, a, d_text, ntext, d_side_hits, d_side_idx, n_upper, d_out, d_ops, d_txt, \
+                     stride, d_keys, d_rest_hits, d_rest_idx, d_ctr)
+  if (a.k == 1) PM_WIDE_LAUNCH(4);
+  else if (a.k == 2) PM_WIDE_LAUNCH(6);
+  else PM_WIDE_LAUNCH(8);
+#undef PM_WIDE_LAUNCH
   return hipGetLastError();
 }
 

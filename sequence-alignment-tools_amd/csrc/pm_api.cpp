@@ -222,6 +222,7 @@ struct pm_handle {
   // counts (pm_count_scan / pm_counts) and the device re-alignment (pm_align_hits_device): DESIGN.md 5d
   AlignDevice ad;                     // tables of pm_align.hip, built on first use after an init (ensure_align_tables)
   bool ad_ready = false, ad_any_long = false;   // ad_any_long: some pattern is beyond the device limit of the DP
+  bool ad_any_wide = false;           // PM_LONG_ALIGN: some pattern of 33..64 characters is re-aligned by pm_align_hits_wide_kernel (indels, 1 <= k <= AL_MAXK)
   void *ad_mem[8] = {};
   int scan_mode = 0;                  // since pm_reset: 0 nothing scanned, 1 pm_scan / pm_scan_view, 2 pm_count_scan, 3 pm_pcr_scan
   bool counting = false;              // a pm_count_scan is in its scan_range and the finals stay on the device
@@ -231,10 +232,12 @@ struct pm_handle {
   size_t ck_cap = 0, cnt_fed = 0;     // cnt_fed: upper bound of the records the range's feed kernel looked at
   void *d_cktemp = nullptr;
   size_t cktemp_bytes = 0, cktemp_for = 0;
-  unsigned long long *d_cnt = nullptr, *d_cinfo = nullptr, *d_actr = nullptr, *h_actr = nullptr;   // tallies [npat * (k + 1)], info [4], kernel counters [3] (+ pinned copy)
+  unsigned long long *d_cnt = nullptr, *d_cinfo = nullptr, *d_actr = nullptr, *h_actr = nullptr;   // tallies [npat * (k + 1)], info [4], kernel counters [3], [4] with ad_any_wide (+ pinned copy)
   size_t cnt_words = 0;
   pm_hit *d_hostq = nullptr;          // records the feed kernel leaves to the host (patterns beyond the device limit)
   size_t hostq_cap = 0;
+  uint64_t *d_hostq_idx = nullptr;    // ad_any_wide: the indices of d_hostq's records, which the wide kernel reads, and
+  pm_hit *d_hostq2 = nullptr;         // the records that kernel leaves to the host in its turn; both hostq_cap long
   pm_hit *d_extra = nullptr;          // the range's host-decided hits, uploaded for the same kernel
   size_t d_extra_cap = 0;
   std::vector<uint64_t> cnt_host;     // host tally (k > 3 or 2^22 patterns and more)
@@ -3271,13 +3274,13 @@ static int scan_range(pm_handle *h, int64_t begin, int64_t end);
 
 static void count_free(pm_handle *h) {
   for (void *&q : h->ad_mem) { if (q) (void)hipFree(q); q = nullptr; }
-  h->ad = AlignDevice(); h->ad_ready = false; h->ad_any_long = false;
-  void *cw[] = {h->d_ck, h->d_ck_alt, h->d_ck_scan, h->d_cktemp, h->d_cnt, h->d_cinfo, h->d_actr, h->d_hostq, h->d_extra};
+  h->ad = AlignDevice(); h->ad_ready = false; h->ad_any_long = false; h->ad_any_wide = false;
+  void *cw[] = {h->d_ck, h->d_ck_alt, h->d_ck_scan, h->d_cktemp, h->d_cnt, h->d_cinfo, h->d_actr, h->d_hostq, h->d_hostq_idx, h->d_hostq2, h->d_extra};
   h->d_extra = nullptr; h->d_extra_cap = 0;
   for (void *q : cw) if (q) (void)hipFree(q);
   if (h->h_actr) (void)hipHostFree(h->h_actr);
   h->d_ck = h->d_ck_alt = h->d_ck_scan = nullptr; h->d_cktemp = nullptr; h->d_cnt = h->d_cinfo = h->d_actr = h->h_actr = nullptr;
-  h->d_hostq = nullptr; h->ck_cap = h->cktemp_bytes = h->cktemp_for = h->cnt_words = h->hostq_cap = 0;
+  h->d_hostq = nullptr; h->d_hostq_idx = nullptr; h->d_hostq2 = nullptr; h->ck_cap = h->cktemp_bytes = h->cktemp_for = h->cnt_words = h->hostq_cap = 0;
   h->cnt_host.clear(); h->cnt_dev = false; h->counting = false;
 }
 
@@ -3305,14 +3308,18 @@ static int ensure_align_tables(pm_handle *h) {
   std::vector<int32_t> esb(np), eeb(np);
   align_tables(h->alpha, tab.data());
   h->ad_any_long = false;
+  bool any_wide = false;                                            // a pattern in reach of pm_align_hits_wide_kernel
   for (size_t i = 0; i < np; ++i) {
     const Pattern &p = h->pats[i];
     chars.insert(chars.end(), p.s.begin(), p.s.end());
     off[i + 1] = (uint32_t)chars.size();
     esb[i] = p.esb; eeb[i] = p.eeb; perm[i] = (uint32_t)i;
     if (h->cfg.k > 0 && (p.s.size() > (size_t)AL_MAXL || p.s.empty())) h->ad_any_long = true;
+    if (p.s.size() > (size_t)AL_MAXL && p.s.size() <= (size_t)AL_MAXL_WIDE) any_wide = true;
   }
   if (h->cfg.k > AL_MAXK) h->ad_any_long = true;
+  h->ad_any_wide = any_wide && (h->cfg.long_patterns & PM_LONG_ALIGN) && h->cfg.indels && h->cfg.k >= 1 && h->cfg.k <= AL_MAXK;
+  const size_t nctr = h->ad_any_wide ? 4 : 3;
   // pattern ids in increasing order; of equal ids the pattern added last, as id2idx resolves them
   std::stable_sort(perm.begin(), perm.end(), [&](uint32_t x, uint32_t y) { return h->pats[x].id < h->pats[y].id; });
   for (size_t r = 0; r < np; ++r) {
@@ -3330,8 +3337,8 @@ static int ensure_align_tables(pm_handle *h) {
   a.ids_sorted = (const uint32_t *)h->ad_mem[5]; a.perm = (const uint32_t *)h->ad_mem[6]; a.idrank = (const uint32_t *)h->ad_mem[7];
   a.npat = (uint32_t)np; a.k = h->cfg.k; a.indels = h->cfg.indels != 0; a.eos = (uint8_t)h->cfg.eos;
   a.wc = h->cfg.wildcards != 0; a.tn = h->cfg.text_n != 0;
-  if (!h->d_actr) HIP_TRY(h, hipMalloc((void **)&h->d_actr, 3 * sizeof(unsigned long long)));
-  if (!h->h_actr) HIP_TRY(h, hipHostMalloc((void **)&h->h_actr, 3 * sizeof(unsigned long long), hipHostMallocDefault));
+  if (!h->d_actr) HIP_TRY(h, hipMalloc((void **)&h->d_actr, nctr * sizeof(unsigned long long)));
+  if (!h->h_actr) HIP_TRY(h, hipHostMalloc((void **)&h->h_actr, nctr * sizeof(unsigned long long), hipHostMallocDefault));
   h->ad_ready = true;
   return PM_OK;
 }
@@ -3362,21 +3369,30 @@ extern "C" int pm_align_hits_device(pm_handle *h, const void *d_hits, size_t n, 
   { int rc = ensure_align_tables(h); if (rc) return rc; }
   // records of patterns beyond the device limit: the kernel compacts them and their indices; only they cross to the host
   // and only their results are written back (pm_align_scatter)
-  uint64_t *d_idx = nullptr;
-  pm_hit *d_rec = nullptr;
+  // (PM_LONG_ALIGN: that list is the wide kernel's input, still on the device, and the list the wide kernel leaves -- d_rec2 /
+  // d_idx2, counted in d_actr[3] -- is what crosses)
+  const bool wide = h->ad_any_wide;
+  uint64_t *d_idx = nullptr, *d_idx2 = nullptr;
+  pm_hit *d_rec = nullptr, *d_rec2 = nullptr;
   void *d_back = nullptr;
-  auto release = [&]() { if (d_idx) (void)hipFree(d_idx); if (d_rec) (void)hipFree(d_rec); if (d_back) (void)hipFree(d_back); };
+  auto release = [&]() { void *q[] = {d_idx, d_rec, d_idx2, d_rec2, d_back}; for (void *x : q) if (x) (void)hipFree(x); };
   if (h->ad_any_long) {
     hipError_t ea = hipMalloc((void **)&d_idx, n * sizeof(uint64_t));
     if (ea == hipSuccess) ea = hipMalloc((void **)&d_rec, n * sizeof(pm_hit));
+    if (ea == hipSuccess && wide) ea = hipMalloc((void **)&d_idx2, n * sizeof(uint64_t));
+    if (ea == hipSuccess && wide) ea = hipMalloc((void **)&d_rec2, n * sizeof(pm_hit));
     if (ea != hipSuccess) { release(); return hipfail(h, ea, "pm_align_hits_device"); }
   }
   hipError_t e = align_hits_device(h->ad, h->d_text, h->n, (const pm_hit *)d_hits, nullptr, n, (pm_alignment *)d_out, (char *)d_ops, (char *)d_text, stride,
                                    nullptr, d_rec, d_idx, h->d_actr, h->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(h->h_actr, h->d_actr, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess && wide)
+    e = align_hits_wide_device(h->ad, h->d_text, h->n, d_rec, d_idx, n, (pm_alignment *)d_out, (char *)d_ops, (char *)d_text, stride, nullptr, d_rec2, d_idx2,
+                               h->d_actr, h->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(h->h_actr, h->d_actr, (wide ? 4 : 3) * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess) e = stream_wait(h);
   if (e != hipSuccess) { release(); return hipfail(h, e, "pm_align_hits_device"); }
-  const size_t m = (size_t)h->h_actr[0];
+  const size_t m = (size_t)h->h_actr[wide ? 3 : 0];
+  if (wide) { std::swap(d_rec, d_rec2); std::swap(d_idx, d_idx2); }   // the list that crosses
   int rc = PM_OK;
   if (h->h_actr[1]) rc = fail(h, PM_E_INVALID, "pm_align_hits_device: unknown pattern id");
   else if (h->h_actr[2]) rc = fail(h, PM_E_INVALID, "pm_align_hits_device: stride too small");
@@ -3450,6 +3466,36 @@ static int ensure_count_state(pm_handle *h) {
   return PM_OK;
 }
 
+// room for `need` records in the list the feed kernel leaves (and, with the wide kernel behind it, for their indices and
+// for the list that kernel leaves in its turn)
+static int ensure_hostq(pm_handle *h, size_t need, size_t cap) {
+  if (!h->ad_any_long || h->hostq_cap >= need) return PM_OK;
+  h->hostq_cap = 0;
+  PM_TRY(dev_regrow(h, &h->d_hostq, cap * sizeof(pm_hit), "d_hostq"));
+  if (h->ad_any_wide) {
+    PM_TRY(dev_regrow(h, &h->d_hostq_idx, cap * sizeof(uint64_t), "d_hostq_idx"));
+    PM_TRY(dev_regrow(h, &h->d_hostq2, cap * sizeof(pm_hit), "d_hostq2"));
+  }
+  h->hostq_cap = cap;
+  return PM_OK;
+}
+
+// the records' tally keys -> d_keys[0 .. n_upper), on the handle's stream: the feed kernel, behind it the wide kernel over the
+// list the feed kernel left (PM_LONG_ALIGN; no host step in between), then the counters' copy to h_actr.  The records for
+// the host are count_hostq(h) records at count_hostq_list(h) once the stream has got there.
+static int count_align(pm_handle *h, const pm_hit *d_hits, const unsigned long long *d_count, size_t n_upper, uint64_t *d_keys) {
+  const bool wide = h->ad_any_wide;
+  HIP_TRY(h, align_hits_device(h->ad, h->d_text, h->n, d_hits, d_count, n_upper, nullptr, nullptr, nullptr, 0, d_keys,
+                               h->ad_any_long ? h->d_hostq : nullptr, wide ? h->d_hostq_idx : nullptr, h->d_actr, h->stream));
+  if (wide)
+    HIP_TRY(h, align_hits_wide_device(h->ad, h->d_text, h->n, h->d_hostq, h->d_hostq_idx, n_upper, nullptr, nullptr, nullptr, 0, d_keys,
+                                      h->d_hostq2, nullptr, h->d_actr, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(h->h_actr, h->d_actr, (wide ? 4 : 3) * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+  return PM_OK;
+}
+static size_t count_hostq(const pm_handle *h) { return (size_t)h->h_actr[h->ad_any_wide ? 3 : 0]; }
+static const pm_hit *count_hostq_list(const pm_handle *h) { return h->ad_any_wide ? h->d_hostq2 : h->d_hostq; }
+
 // the device's finals of one range -> tally keys d_ck[0 .. count), before the host knows their number
 static int count_feed_device(pm_handle *h, const pm_hit *d_hits, const unsigned long long *d_count, size_t n_upper) {
   h->cnt_fed = 0;
@@ -3457,13 +3503,8 @@ static int count_feed_device(pm_handle *h, const pm_hit *d_hits, const unsigned 
   // (cannot happen: the finalize stage in front refuses 2^31 records before it touches the engine's state; not a reason to cut the range)
   if (n_upper >= ((size_t)1 << 31)) return fail(h, PM_E_INVALID, "pm_count_scan: internal: 2^31 or more final hits in one range");
   { int rc = ensure_count_keys(h, n_upper + ((size_t)1 << 12), 0); if (rc) return rc; }
-  if (h->ad_any_long && h->hostq_cap < n_upper) {
-    h->hostq_cap = n_upper + n_upper / 4;
-    PM_TRY(dev_regrow(h, &h->d_hostq, h->hostq_cap * sizeof(pm_hit), "d_hostq"));
-  }
-  HIP_TRY(h, align_hits_device(h->ad, h->d_text, h->n, d_hits, d_count, n_upper, nullptr, nullptr, nullptr, 0, h->d_ck,
-                               h->ad_any_long ? h->d_hostq : nullptr, nullptr, h->d_actr, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(h->h_actr, h->d_actr, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+  { int rc = ensure_hostq(h, n_upper, n_upper + n_upper / 4); if (rc) return rc; }
+  { int rc = count_align(h, d_hits, d_count, n_upper, h->d_ck); if (rc) return rc; }
   h->cnt_fed = n_upper;
   return PM_OK;
 }
@@ -3527,14 +3568,14 @@ static int count_collect(pm_handle *h, size_t nfin, std::vector<pm_hit> &extra, 
     if (!nq) return PM_OK;
     const size_t at = rest.size();
     rest.resize(at + nq);
-    HIP_TRY(h, hipMemcpyAsync(rest.data() + at, h->d_hostq, nq * sizeof(pm_hit), hipMemcpyDeviceToHost, h->copy_stream));
+    HIP_TRY(h, hipMemcpyAsync(rest.data() + at, count_hostq_list(h), nq * sizeof(pm_hit), hipMemcpyDeviceToHost, h->copy_stream));
     HIP_TRY(h, hipStreamSynchronize(h->copy_stream));
     h->cinfo.record_bytes_to_host += nq * sizeof(pm_hit);
     return PM_OK;
   };
   if (nfin) {
     if (h->h_actr[1]) return fail(h, PM_E_INVALID, "pm_count_scan: a final hit with an unknown pattern id");
-    const size_t nq = (size_t)h->h_actr[0];
+    const size_t nq = count_hostq(h);
     { int rc = take_hostq(nq); if (rc) return rc; }
     h->cinfo.aligned_device += nfin - nq;
   }
@@ -3545,17 +3586,12 @@ static int count_collect(pm_handle *h, size_t nfin, std::vector<pm_hit> &extra, 
       h->d_extra_cap = std::max<size_t>(2 * m, (size_t)1 << 12);
       PM_TRY(dev_regrow(h, &h->d_extra, h->d_extra_cap * sizeof(pm_hit), "d_extra"));
     }
-    if (h->ad_any_long && h->hostq_cap < m) {
-      h->hostq_cap = std::max<size_t>(2 * m, (size_t)1 << 12);
-      PM_TRY(dev_regrow(h, &h->d_hostq, h->hostq_cap * sizeof(pm_hit), "d_hostq"));
-    }
+    { int rc = ensure_hostq(h, m, std::max<size_t>(2 * m, (size_t)1 << 12)); if (rc) return rc; }
     HIP_TRY(h, hipMemcpy(h->d_extra, extra.data(), m * sizeof(pm_hit), hipMemcpyHostToDevice));
-    HIP_TRY(h, align_hits_device(h->ad, h->d_text, h->n, h->d_extra, nullptr, m, nullptr, nullptr, nullptr, 0, h->d_ck + nfin,
-                                 h->ad_any_long ? h->d_hostq : nullptr, nullptr, h->d_actr, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->h_actr, h->d_actr, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    { int rc = count_align(h, h->d_extra, nullptr, m, h->d_ck + nfin); if (rc) return rc; }
     HIP_TRY(h, stream_wait(h));
     if (h->h_actr[1]) return fail(h, PM_E_INVALID, "pm_count_scan: a final hit with an unknown pattern id");
-    const size_t nq = (size_t)h->h_actr[0];
+    const size_t nq = count_hostq(h);
     { int rc = take_hostq(nq); if (rc) return rc; }
     h->cinfo.aligned_device += m - nq;
   }

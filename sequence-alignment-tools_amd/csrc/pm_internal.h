@@ -158,6 +158,7 @@ hipError_t halves_rule_device(const pm_hit *d_in, size_t n, bool flags, int slac
 // ---- the caller's re-alignment and tally on the device (pm_align.hip) ----------------------------
 constexpr int AL_MAXL = 32, AL_MAXK = 3;         // device limit of the edit-distance DP; longer patterns are aligned by the host
 constexpr int AL_MAXL_SUB = 64;                  // ... but for -K (no indels: the DP is one diagonal), which the device walks up to this length
+constexpr int AL_MAXL_WIDE = 64;                 // ... and with indels where pm_config.long_patterns has PM_LONG_ALIGN: pm_align_hits_wide_kernel
 constexpr int AL_THREADS = 64;                   // one wave per block: every lane owns a column of the block's LDS
 constexpr uint64_t TALLY_INVALID = ~0ull;        // tally key of a record the device did not align
 constexpr int TALLY_BOGUS = 4;                   // distance code of a hit that re-aligns to more than k (or to a violation)
@@ -182,6 +183,14 @@ void align_tables(const Alphabet &alpha, uint8_t *tab);
 hipError_t align_hits_device(const AlignDevice &a, const uint8_t *d_text, int64_t ntext, const pm_hit *d_hits, const unsigned long long *d_count,
                              size_t n_upper, pm_alignment *d_out, char *d_ops, char *d_txt, size_t stride, uint64_t *d_keys,
                              pm_hit *d_hostq_hits, uint64_t *d_hostq_idx, unsigned long long *d_ctr, hipStream_t st);
+// Behind align_hits_device on the same stream, no host step in between: one lane per record of the list that call left
+// (d_side_hits, d_side_idx -- both required -- and their count d_ctr[0], n_upper as in that call).  Patterns of 33..64
+// characters with indels, 1 <= a.k <= AL_MAXK: the record's results go where that call would have put them (d_out[idx],
+// the strings at idx * stride, d_keys[idx]; any may be NULL).  Records it cannot take either go to d_rest_hits /
+// d_rest_idx, whichever is not NULL, counted in d_ctr[3]; d_ctr[2] goes on counting strings that did not fit.
+hipError_t align_hits_wide_device(const AlignDevice &a, const uint8_t *d_text, int64_t ntext, const pm_hit *d_side_hits, const uint64_t *d_side_idx,
+                                  size_t n_upper, pm_alignment *d_out, char *d_ops, char *d_txt, size_t stride, uint64_t *d_keys,
+                                  pm_hit *d_rest_hits, uint64_t *d_rest_idx, unsigned long long *d_ctr, hipStream_t st);
 // d_src[j] (and the two strings at j * stride, when d_ops != NULL) -> place d_idx[j] of d_out / d_ops / d_txt, j < m
 hipError_t align_scatter_device(const uint64_t *d_idx, size_t m, const pm_alignment *d_src, const char *d_src_ops, const char *d_src_txt, size_t stride,
                                 pm_alignment *d_out, char *d_ops, char *d_txt, hipStream_t st);
