@@ -84,6 +84,7 @@ typedef enum {
 #define PM_LONG_EDITS 4    /* -k 1 / -k 2: patterns of 33..64 characters may run on the edit plan */
 #define PM_LONG_HALVES 8   /* -k 1 / -k 2 under exact_halves: patterns of 33..64 characters may run on the halves plan */
 #define PM_LONG_ALIGN 16   /* -k 1 .. -k 3 (edits): hits of patterns of 33..64 characters are re-aligned on the device */
+#define PM_WILD_CLASS 32   /* -w, k = 0 / -K 1 / -K 2: patterns of 16..32 characters with more than 16 concrete variants may run on pm_wild_sub_scan */
 
 /* Replaces the constructor arguments of the reference engines as pick_pattern_index passes them
  * (select.cc:19-30): nmismatch, indels, wildcard, textn, eos.  dna_mut is not supported. */
@@ -97,7 +98,7 @@ typedef struct {
   int32_t text_n;          /* -W: a text N also matches (shift_and.cc:112) */
   int32_t eos;             /* raw end-of-sequence char, '\n' in the CLIs */
   int32_t device;          /* HIP device ordinal */
-  int32_t long_patterns;   /* a bit set (PM_LONG_SUB | PM_LONG_EXACT | PM_LONG_EDITS | PM_LONG_HALVES | PM_LONG_ALIGN; 0 = the routing of
+  int32_t long_patterns;   /* a bit set (PM_LONG_SUB | PM_LONG_EXACT | PM_LONG_EDITS | PM_LONG_HALVES | PM_LONG_ALIGN | PM_WILD_CLASS; 0 = the routing of
                               earlier versions).
                               PM_LONG_SUB (1) = with PM_KERNEL_AUTO, -K 1 / -K 2 (substitutions only) and filter_bitvec, bare
                               shift_and_inexact or exact_halves on an A,C,G,T-normalized or raw ASCII stream, patterns
@@ -123,8 +124,18 @@ typedef struct {
                               PM_LONG_ALIGN (16) is no routing bit: it changes no scan kernel and not pm_describe.  With
                               indels and 1 <= k <= 3, pm_align_hits_device, pm_count_scan and pm_pcr_pair re-align the
                               records of patterns of 33..64 characters on the device (pm_align_hits_wide_kernel), whichever
-                              kernels found them; not set, the host aligns them as before.  (Took the
-                              place of reserved[0]: same layout, same PM_ABI_VERSION.) */
+                              kernels found them; not set, the host aligns them as before.
+                              PM_WILD_CLASS (32) = with PM_KERNEL_AUTO and -w on a plain stream (A,C,G,T, and N only
+                              without -W; A,C,G,T-normalized or raw ASCII), substitutions only: keyword_tree or
+                              shift_and at k = 0, filter_bitvec at -K 1 / -K 2.  A pattern of 16..32 characters that
+                              has more than 16 concrete variants (three or more ambiguity letters), accepts a base at
+                              every character, is no N pattern on an N stream under filter_bitvec and expands to at
+                              most 256 keys in every field pair of its last 16 bases runs on pm_wild_sub_scan +
+                              pm_wild_sub_verify, beside the main class or alone, and not on the
+                              bit-parallel residue; a list whose expanded keys exceed 24,000 in some field pair keeps
+                              the routing without the bit.  It has nothing to do with the pattern's length: the bit
+                              lives here because this field is the one set of routing permissions.  (The field took
+                              the place of reserved[0]: same layout, same PM_ABI_VERSION.) */
   int32_t reserved[6];
 } pm_config;
 

@@ -203,6 +203,13 @@ struct pm_handle {
   std::vector<uint8_t> in_ssub;       // per pattern: 1 = scanned by pm_short_sub_scan
   size_t nssub = 0;
   ShortSubDevice ssd;
+  // -w, k = 0 / -K 1 / -K 2: primers of 16..32 characters with more than 16 concrete variants, a class of their own on
+  // pm_wild_sub_scan (PM_WILD_CLASS bit of pm_config.long_patterns) beside the main class -- Bloom or pair
+  // plan -- or without one.  Its records are the main class's; the host's edge records cover it (in_main_class).
+  std::vector<uint8_t> in_wild;       // per inner pattern: 1 = scanned by pm_wild_sub_scan
+  size_t nwild = 0;
+  bool wild_only = false;             // no main class: the wild class (and a residue, if any) is the handle's whole device stage
+  WildDevice wd;
   bool halves_fresh = true;           // no host-side exact_halves state (lasthit, carried seeds) since init / pm_reset
 
   // windowed stream (pm_init_windowed): d_text / d_packed point at the bound slot, rebased so that absolute stream
@@ -265,8 +272,10 @@ struct pm_handle {
 
 // per-tile record counts between a scan's first-stage and verify kernels: [0] unused, [1 + t] tile t, then 8 measurement counters
 // [SHORT_COUNT_AT]: seed records of the short class (all its tiles); the pair plan's short class counts its suspects there
-constexpr size_t SEEDCOUNT_WORDS = 1 + 256 + 8 + 1;
+// [WILD_COUNT_AT]: suspects of the wild class
+constexpr size_t SEEDCOUNT_WORDS = 1 + 256 + 8 + 2;
 constexpr size_t SHORT_COUNT_AT = 1 + 256 + 8;
+constexpr size_t WILD_COUNT_AT = 1 + 256 + 8 + 1;
 
 static thread_local std::string g_create_error;
 
@@ -441,6 +450,7 @@ static void read_knobs(Knobs *k) {
   k->long_exact_off = is("PM_LONG_EXACT", "off");
   k->long_edits_off = is("PM_LONG_EDITS", "off");
   k->long_halves_off = is("PM_LONG_HALVES", "off");
+  k->wild_off = is("PM_WILD_CLASS", "off");
   k->debug = getenv("PM_DEBUG") != nullptr;
 }
 
@@ -499,6 +509,7 @@ static void free_device(pm_handle *h) {
   bitpar_free(&h->bp);
   short_free(&h->shd);
   short_sub_free(&h->ssd);
+  wild_free(&h->wd);
   seed_free(&h->sd);
   for (SeedDevice &d : h->sd_more) seed_free(&d);
   h->sd_more.clear();
@@ -702,6 +713,7 @@ static bool seed_eligible(pm_handle *h, std::string *why) {
   bool pair_ok = !h->cfg.indels && (h->cfg.k == 1 || h->cfg.k == 2) && !h->pats.empty();
   for (size_t i = 0; i < h->pats.size(); ++i) {
     const Pattern &p = h->pats[i];
+    if (i < h->in_wild.size() && h->in_wild[i]) continue;           // the wild class: its own exact stage (wild_verify) knows the zones
     const bool sub = i < h->in_ssub.size() && h->in_ssub[i];        // 16..19 characters beside the pair plan: pm_short_sub_scan, the same exact verify
     pair_ok = pair_ok && p.s.size() >= (sub ? 16u : 20u) && p.s.size() <= (h->nlong ? 64u : 32u);
     for (unsigned char ch : p.s) pair_ok = pair_ok && (ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T');
@@ -807,6 +819,31 @@ static void short_sub_route(pm_handle *h, size_t maxL) {
   h->nssub = nsub;
 }
 
+// -w primers with more than 16 concrete variants: with the PM_WILD_CLASS bit of pm_config.long_patterns
+// they leave the residue for a class of their own on pm_wild_sub_scan.  The handle: no kernel asked for by name, wild_seed
+// (a plain stream; keyword_tree, shift_and or filter_bitvec), substitutions only -- keyword_tree / shift_and scan at k = 0,
+// filter_bitvec at -K 1 / -K 2 -- and a stream the pair plan takes.  The primer: refused by expand_iupac(p, 16), one
+// wild_takes holds (16..32 characters, a base at every character, <= 256 keys per field pair), no pattern_n_quirk primer
+// under filter_bitvec.  The class: wild_class_fits (run entries per field pair); a class beyond it leaves every primer where
+// it was.  Anything else, PM_WILD_CLASS=off included, leaves every handle as it was built before the class existed.
+// Called by classify_patterns with in_rest decided.
+static void wild_route(pm_handle *h) {
+  if (!(h->cfg.long_patterns & PM_WILD_CLASS) || h->knobs.wild_off || h->kern != PM_KERNEL_AUTO || !h->wild_seed) return;
+  if (h->sem == PM_SEM_FILTER_BITVEC ? (h->cfg.indels || (h->scan_k != 1 && h->scan_k != 2)) : h->scan_k != 0) return;
+  if (!stream_for_pair_plan(h)) return;
+  std::vector<std::string> variants, cls;
+  std::vector<size_t> who;
+  for (size_t i = 0; i < h->inner.size(); ++i) {
+    const Pattern &p = h->inner[i];
+    if (!h->in_rest[i] || !wild_takes(p.s, h->scan_k)) continue;
+    if (expand_iupac(p.s, 16, &variants)) continue;                 // (in the residue for another reason)
+    if (h->sem == PM_SEM_FILTER_BITVEC && pattern_n_quirk(h, p)) continue;
+    who.push_back(i); cls.push_back(p.s);
+  }
+  if (who.empty() || who.size() >= ((size_t)1 << 21) || !wild_class_fits(cls, h->scan_k)) return;
+  for (size_t i : who) { h->in_rest[i] = 0; --h->nrest; h->in_wild[i] = 1; ++h->nwild; }
+}
+
 // Which engine and class every pattern of the list goes to: in_rest (the bit-parallel residue beside the seed family),
 // in_short (16..19 characters under -k: pm_short_edit_scan), short_only, and -- short_sub_route -- in_ssub.  A pattern set is
 // rarely uniform: a few primers with an ambiguity letter, one that is too short or too long for the seed plan.  Where the
@@ -822,6 +859,8 @@ static void classify_patterns(pm_handle *h, bool want_seed, size_t maxL) {
   h->nrest = 0;
   h->in_short.assign(h->inner.size(), 0);
   h->nshort = 0; h->short_only = false;
+  h->in_wild.assign(h->inner.size(), 0);
+  h->nwild = 0; h->wild_only = false;
   if (want_seed && (!h->cfg.wildcards || h->wild_seed) && h->kern == PM_KERNEL_AUTO &&
       (h->sem == PM_SEM_KEYWORD_TREE || h->sem == PM_SEM_SHIFT_AND || h->sem == PM_SEM_SHIFT_AND_INEXACT || h->sem == PM_SEM_FILTER_BITVEC)) {
     std::vector<std::string> variants;
@@ -835,8 +874,10 @@ static void classify_patterns(pm_handle *h, bool want_seed, size_t maxL) {
       if (!ok) { h->in_rest[i] = 1; ++h->nrest; }
       else if (is_short) { h->in_short[i] = 1; ++h->nshort; }
     }
+    wild_route(h);
     // nothing for the main class and something for the residue: one engine, the bit-parallel family
-    if (h->nrest && h->nrest + h->nshort == h->inner.size()) {
+    // (a wild class stands without a main class: wild_only)
+    if (!h->nwild && h->nrest && h->nrest + h->nshort == h->inner.size()) {
       std::fill(h->in_rest.begin(), h->in_rest.end(), 0); h->nrest = 0;
       std::fill(h->in_short.begin(), h->in_short.end(), 0); h->nshort = 0;
     }
@@ -851,6 +892,7 @@ static void classify_patterns(pm_handle *h, bool want_seed, size_t maxL) {
     }
   }
   h->short_only = h->nshort != 0 && h->nshort == h->inner.size();
+  h->wild_only = h->nwild != 0 && h->nwild + h->nrest == h->inner.size();
   short_sub_route(h, maxL);
 }
 
@@ -872,7 +914,7 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
   h->eos_code = h->alpha.nch[(uint8_t)h->cfg.eos];                  // shift_and_inexact.cc:131
   int rc = resolve(h);
   if (rc) return rc;
-  bitpar_free(&h->bp); seed_free(&h->sd); short_free(&h->shd); short_sub_free(&h->ssd);
+  bitpar_free(&h->bp); seed_free(&h->sd); short_free(&h->shd); short_sub_free(&h->ssd); wild_free(&h->wd);
   for (SeedDevice &d : h->sd_more) seed_free(&d);
   h->sd_more.clear();
   for (PairDevice &d : h->pair) pair_free(&d);
@@ -906,7 +948,7 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
     bool pair_takes = true;
     for (size_t i = 0; i < h->pats.size(); ++i) {
       const std::string &ps = h->pats[i].s;
-      if (h->in_ssub[i]) continue;
+      if (h->in_ssub[i] || (i < h->in_wild.size() && h->in_wild[i])) continue;
       if (h->sem == PM_SEM_EXACT_HALVES) { for (unsigned char ch : ps) pair_takes = pair_takes && (ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T'); pair_takes = pair_takes && ps.size() <= 64; }
       else if (i < h->in_rest.size() && h->in_rest[i]) continue;
       pair_takes = pair_takes && ps.size() >= 20;
@@ -993,11 +1035,11 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
     } else if (h->wild_seed) {                    // every concrete variant of a primer is a seed-family pattern with the primer's id
       std::vector<std::string> variants;
       for (size_t i = 0; i < h->inner.size(); ++i) {
-        if (h->in_rest[i] || h->in_short[i] || h->in_ssub[i]) continue;
+        if (h->in_rest[i] || h->in_short[i] || h->in_ssub[i] || h->in_wild[i]) continue;
         expand_iupac(h->inner[i].s, 16, &variants);
         for (const std::string &v : variants) { Pattern q = h->inner[i]; q.s = v; sp.push_back(q); sid.push_back(h->inner_ids[i]); }
       }
-      if (sp.empty() && !h->short_only) { sp.push_back(Pattern{std::string(edits_mode ? 20 : 10, 'A'), 0, 0, 0}); sid.push_back(0); why = "no primer the seed family could take"; }
+      if (sp.empty() && !h->short_only && !h->wild_only) { sp.push_back(Pattern{std::string(edits_mode ? 20 : 10, 'A'), 0, 0, 0}); sid.push_back(0); why = "no primer the seed family could take"; }
     } else if (h->nrest || h->nshort || h->nssub) {
       for (size_t i = 0; i < h->inner.size(); ++i) if (!h->in_rest[i] && !h->in_short[i] && !h->in_ssub[i]) { sp.push_back(h->inner[i]); sid.push_back(h->inner_ids[i]); }
     } else { sp = h->inner; sid = h->inner_ids; }
@@ -1060,7 +1102,7 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
       h->sd.k = sk; h->sd.Lw = 20; h->sd.pb = 5; h->sd.r = 4 - sk; h->sd.ncombos = pt.ncombos; h->sd.ascii = pt.ascii;
       h->sd.maxlen = std::max(h->sd.maxlen, pt.maxlen);
     }
-    for (size_t ti = 0; ti < ntile && why.empty() && !use_pair && !h->short_only; ++ti) {
+    for (size_t ti = 0; ti < ntile && why.empty() && !use_pair && !h->short_only && !h->wild_only; ++ti) {
       const size_t lo = ti * per, hi = std::min(sp.size(), lo + per);
       std::vector<Pattern> tp(sp.begin() + lo, sp.begin() + hi);
       std::vector<uint32_t> tid(sid.begin() + lo, sid.begin() + hi);
@@ -1117,7 +1159,21 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
         h->ssd.viol_level = h->sem == PM_SEM_FILTER_BITVEC ? 3 : 0;  // as the main class's
       }
     }
+    if (why.empty() && h->nwild) {                                  // -w: the class of primers with more than 16 concrete variants
+      std::vector<Pattern> wp; std::vector<uint32_t> wid;
+      for (size_t i = 0; i < h->inner.size(); ++i) if (h->in_wild[i]) { wp.push_back(h->inner[i]); wid.push_back(h->inner_ids[i]); }
+      if (h->sem != PM_SEM_FILTER_BITVEC) for (Pattern &p : wp) { p.esb = 0; p.eeb = 0; }   // (the keyword tree and the automata know no exact zones, see above)
+      WildTables wt;
+      why = wild_build(wp, wid, h->alpha, h->scan_k, h->eos_code, &wt);
+      if (why.empty()) {
+        HIP_TRY(h, wild_upload(wt, &h->wd, h->stream));
+        h->wd.viol_level = h->sem == PM_SEM_FILTER_BITVEC ? 3 : 0;   // as the main class's
+        if (h->wild_only) { h->sd.k = sk; h->sd.Lw = 16; h->sd.ascii = wt.ascii; h->sd.maxlen = wt.maxlen; }   // (the plan facts the rest of this file reads from h->sd)
+        else h->sd.maxlen = std::max(h->sd.maxlen, wt.maxlen);
+      }
+    }
     if (!why.empty()) {
+      wild_free(&h->wd);
       seed_free(&h->sd);
       for (SeedDevice &d : h->sd_more) seed_free(&d);
       h->sd_more.clear();
@@ -1139,6 +1195,7 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
       for (SeedDevice &d : h->sd_more) mx = std::max(mx, d.maxlen);
       h->sd.maxlen = mx;
       h->kern = PM_KERNEL_SEED;
+      if (h->nwild && h->knobs.debug) fprintf(stderr, "[pm] wild class: %zu patterns with more than 16 concrete variants on pm_wild_sub_scan\n", h->nwild);
       h->seed_flags = h->sem == PM_SEM_EXACT_HALVES && !halves_mode;
       h->bases_flags = h->sem == PM_SEM_EXACT_BASES && !h->cfg.indels;
       h->bases_edits = h->sem == PM_SEM_EXACT_BASES && h->cfg.indels;
@@ -1184,6 +1241,7 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
     std::fill(h->in_rest.begin(), h->in_rest.end(), 0); h->nrest = 0;
     std::fill(h->in_short.begin(), h->in_short.end(), 0); h->nshort = 0; h->short_only = false;
     std::fill(h->in_ssub.begin(), h->in_ssub.end(), 0); h->nssub = 0;
+    std::fill(h->in_wild.begin(), h->in_wild.end(), 0); h->nwild = 0; h->wild_only = false;
     h->kern = PM_KERNEL_BITPAR;
     BitparTables tabs;
     std::string msg = bitpar_build(h->inner, h->inner_ids, h->alpha, h->scan_k, h->eos_code, &tabs,
@@ -1732,7 +1790,15 @@ static const char *pair_schedule_name(const ScanGeometry &g) {
 
 extern "C" int pm_describe(const pm_handle *h, char *buf, size_t buflen) {
   if (!h || !buf || !h->inited) return PM_E_INVALID;
-  if (h->kern == PM_KERNEL_SEED && h->short_only)
+  if (h->kern == PM_KERNEL_SEED && h->wild_only) {
+    snprintf(buf, buflen, "kernel=pm_wild_sub_scan+pm_wild_sub_verify for %zu patterns with more than 16 concrete variants (entries=%zu, pairs=%d) fields=2-of-4 x 4 bases window=16 chunk=%lld nchunks=%d grid=%d block=%d",
+             h->nwild, h->wd.max_entries, h->wd.ncombos, (long long)h->geo.seg_len, h->geo.nseg, h->geo.blocks, h->geo.threads);
+    if (h->nrest) {
+      const size_t at = strlen(buf);
+      if (at < buflen) snprintf(buf + at, buflen - at, " + %s for %zu patterns the seed plan does not take", bitpar_kernel_name(h->scan_k, h->scan_indels), h->nrest);
+    }
+  }
+  else if (h->kern == PM_KERNEL_SEED && h->short_only)
     snprintf(buf, buflen, "kernel=pm_short_edit_scan+pm_edits_verify for %zu patterns of 16..19 characters (tiles=%d, tests=%d) fields=2-of-4 x 4 bases, displaced by |d| <= %d window=16 chunk=%lld nchunks=%d grid=%d block=%d",
              h->nshort, (int)h->shd.tiles.size(), h->shd.k == 2 ? SHORT_NTESTS : 2, h->shd.k, (long long)h->geo.seg_len, h->geo.nseg, h->geo.blocks, h->geo.threads);
   else if (h->kern == PM_KERNEL_SEED && !h->pair.empty()) {
@@ -1798,6 +1864,10 @@ extern "C" int pm_describe(const pm_handle *h, char *buf, size_t buflen) {
     const size_t at = strlen(buf);
     if (at < buflen) snprintf(buf + at, buflen - at, " + pm_short_sub_scan for %zu patterns of 16..19 characters (tiles=%d, pairs=%d)", h->nssub, (int)h->ssd.tiles.size(), h->ssd.ncombos);
   }
+  if (h->kern == PM_KERNEL_SEED && h->nwild && !h->wild_only) {
+    const size_t at = strlen(buf);
+    if (at < buflen) snprintf(buf + at, buflen - at, " + pm_wild_sub_scan for %zu patterns with more than 16 concrete variants (entries=%zu, pairs=%d)", h->nwild, h->wd.max_entries, h->wd.ncombos);
+  }
   if (h->kern == PM_KERNEL_SEED) return PM_OK;
   else
     snprintf(buf, buflen, "kernel=%s tiles=%d lanes_per_tile=64 words_per_lane=%d seg_len=%lld nseg=%d grid=%d block=%d",
@@ -1809,6 +1879,24 @@ extern "C" int pm_describe(const pm_handle *h, char *buf, size_t buflen) {
 // ---- device stage ------------------------------------------------------------------------------
 static int ensure_dp_tables(pm_handle *h);
 static int ensure_fpat(pm_handle *h);
+
+// The wild class into the record buffer of the scan being enqueued, behind the main class's kernels: its 8-byte suspects use
+// the suspect list (which the main class's verify launches have read by then, stream order) under a counter of their own.
+// own_counters: the main class runs no kernel that counts in d_seed_count, so the counters are this call's to zero and copy.
+static int wild_scan(pm_handle *h, int64_t begin, int64_t end, bool own_counters) {
+  const size_t want = (size_t)((end - begin) / 128) + ((size_t)1 << 20);
+  if (!h->d_susp || h->susp_cap < want) {
+    h->susp_cap = std::max(h->susp_cap, want);
+    PM_TRY(dev_regrow(h, &h->d_susp, h->susp_cap * PAIR_SUSPECT_BYTES, "d_susp"));
+  }
+  if (!h->d_seed_count) HIP_TRY(h, hipMalloc((void **)&h->d_seed_count, SEEDCOUNT_WORDS * sizeof(unsigned long long)));
+  if (own_counters) HIP_TRY(h, hipMemsetAsync(h->d_seed_count, 0, SEEDCOUNT_WORDS * sizeof(unsigned long long), h->stream));
+  HIP_TRY(h, wild_launch(h->wd, h->d_text, h->d_packed, h->n, begin, end, h->d_cands, h->d_counter, h->cap, (uint64_t *)h->d_susp,
+                         h->d_seed_count + WILD_COUNT_AT, h->susp_cap * (PAIR_SUSPECT_BYTES / sizeof(uint64_t)), h->stream, h->wild_only ? &h->geo : nullptr));
+  h->last_launches += 2;
+  if (own_counters) HIP_TRY(h, hipMemcpyAsync(h->h_seed_count, h->d_seed_count, SEEDCOUNT_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+  return PM_OK;
+}
 
 extern "C" int pm_scan_candidates_async(pm_handle *h, int64_t begin, int64_t end) {
   if (!h || !h->inited) return fail(h, PM_E_INVALID, "pm_scan_candidates: handle not initialised");
@@ -1901,15 +1989,17 @@ extern "C" int pm_scan_candidates_async(pm_handle *h, int64_t begin, int64_t end
                                   h->d_seed_count + SHORT_COUNT_AT, h->susp_cap * (PAIR_SUSPECT_BYTES / sizeof(uint64_t)), h->stream));
       h->last_launches += (int)h->ssd.tiles.size() + 1;
     }
+    if (h->nwild) PM_TRY(wild_scan(h, begin, end, false));
     HIP_TRY(h, hipMemcpyAsync(h->h_seed_count, h->d_seed_count, SEEDCOUNT_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
     if (h->nrest) { HIP_TRY(h, bitpar_launch(h->bp, h->d_text, h->n, begin, end, h->d_cands, h->d_counter, h->cap, h->stream, nullptr)); ++h->last_launches; }
   }
   else if (h->kern == PM_KERNEL_SEED)
   {
-    HIP_TRY(h, seed_launch(h->sd, h->d_text, h->d_packed, h->n, begin, end, h->d_cands, h->d_counter, h->cap, h->stream, &h->geo));
+    if (!h->wild_only) HIP_TRY(h, seed_launch(h->sd, h->d_text, h->d_packed, h->n, begin, end, h->d_cands, h->d_counter, h->cap, h->stream, &h->geo));
     for (SeedDevice &d : h->sd_more)
       HIP_TRY(h, seed_launch(d, h->d_text, h->d_packed, h->n, begin, end, h->d_cands, h->d_counter, h->cap, h->stream, nullptr));
-    h->last_launches = 1 + (int)h->sd_more.size();
+    h->last_launches = h->wild_only ? 0 : 1 + (int)h->sd_more.size();
+    if (h->nwild) PM_TRY(wild_scan(h, begin, end, true));
     if (h->nrest) { HIP_TRY(h, bitpar_launch(h->bp, h->d_text, h->n, begin, end, h->d_cands, h->d_counter, h->cap, h->stream, nullptr)); ++h->last_launches; }
   }
   else
@@ -2300,6 +2390,19 @@ static int scan_wait_once(pm_handle *h, size_t *n_out) {
       return SCAN_AGAIN;
     }
   }
+  if (h->kern == PM_KERNEL_SEED && h->nwild) {
+    // the suspect buffer must have held the wild class's suspects (8-byte suspects in the 16-byte slots)
+    const unsigned long long worst = (h->h_seed_count[WILD_COUNT_AT] + 1) / 2;
+    h->last_peak = std::max(h->last_peak, h->h_seed_count[WILD_COUNT_AT]);
+    if (h->knobs.debug) fprintf(stderr, "[pm] wild class: %llu suspects, capacity %zu, candidates %zu\n", h->h_seed_count[WILD_COUNT_AT], 2 * h->susp_cap, cnt);
+    if (h->bound_on && worst > dense_bound(h)) return dense_fail(h, "suspects of the wild class", worst);
+    if (worst > h->susp_cap) {                                     // grow it and tell the caller to scan again
+      h->susp_cap = (size_t)worst + (size_t)worst / 8 + 1024;
+      h->last_count = 0;
+      PM_TRY(dev_regrow(h, &h->d_susp, h->susp_cap * PAIR_SUSPECT_BYTES, "d_susp"));
+      return SCAN_AGAIN;
+    }
+  }
   if (h->edits_dev) {
     // records of the stream's edges (host), then sort + unique on the device: several seeds report each candidate
     std::vector<pm_hit> extra;
@@ -2393,6 +2496,7 @@ extern "C" int pm_scan_stats(pm_handle *h, uint64_t *out, int n) {
     const size_t tiles = !h->pair.empty() ? h->pair.size() : 1 + h->sd_more.size();
     for (size_t t = 0; t < tiles && t < 256; ++t) v[1] = std::max<uint64_t>(v[1], h->h_seed_count[1 + t]);
     if (h->nshort || h->nssub) v[1] += h->h_seed_count[SHORT_COUNT_AT];   // (+ the short class's seed records / suspects)
+    if (h->nwild) v[1] += h->h_seed_count[WILD_COUNT_AT];             // (+ the wild class's suspects)
     v[3] = h->h_seed_count[257]; v[4] = h->h_seed_count[258]; v[5] = h->h_seed_count[259];
   }
   v[2] = h->internal_rescans;

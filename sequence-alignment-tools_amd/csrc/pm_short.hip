@@ -3,6 +3,9 @@
 // scan kernels are ONE scan (short_scan: bitmaps in LDS, the wave's range, the key-hit queue, its drain, reserved slot
 // blocks) around a struct each -- EditTests, SubCombos -- that says how windows become masks, how a run entry is judged
 // and how a record is packed; their host tables come from one builder (pm_short_tables.h), one upload and one free.
+// The same scan runs the wild class (pm_wild_sub_scan + pm_wild_sub_verify): -w primers of 16..32 characters
+// with more than 16 concrete variants, keys expanded per field pair, everything else compared by class (WildCombos,
+// pm_wild_tables.h).
 //
 // The edit plan of pm_seed.hip / pm_pair.hip seeds on the last 20 pattern bases, so a primer of 16..19 bases used to go
 // to the bit-parallel residue kernel.  Here the last SIXTEEN bases are four fields of four -- the four bytes of the 2-bit
@@ -28,6 +31,7 @@
 #include "pm_short_tables.h"
 #include "pm_slots.h"
 #include "pm_verify.h"
+#include "pm_wild_tables.h"
 
 #include <algorithm>
 #include <cstring>
@@ -337,6 +341,56 @@ __global__ __launch_bounds__(256) void pm_short_sub_verify(SubArgs a) {
   });
 }
 
+// ---- the wild class: -w primers with more than 16 concrete variants, compared by class -----------------
+//
+//   pm_wild_sub_scan     pm_short_sub_scan's scan -- same windows, same key lookup in LDS -- over bitmaps that hold every key in
+//                        the cross product of the classes of a field pair's eight bases (pm_wild_tables.h).  A run entry is
+//                        {primer, class word}: four bits per base for the eight bases outside the key, so one read settles a
+//                        key hit here too: the window's other eight bases become one bit each in their nibble, AND + popcount.
+//                        k = 0 runs the k = 1 instance (two bitmaps), every primer entered under one of the two pairs.
+//   pm_wild_sub_verify   wild_verify<4> of pm_verify.h per suspect: pair_verify with the per-byte verdict by class.
+//
+// N, end-of-sequence and positions outside the stream pack to arbitrary bases, as above: such a window can only gain
+// suspects, and it cannot lose a candidate -- such a character is one of the <= k mismatches and leaves two clean fields.
+struct WildArgs : SubArgs {
+  const uint8_t *pat_class;             // 16 bytes per primer (pat_codes is unused)
+  const uint8_t *pat_reg;
+  int ascii;
+};
+
+template <int K>
+struct WildCombos : SubCombos<K> {
+  struct Hit { uint32_t row, others; };                              // others: the window's eight bases outside the key (wild_others)
+  __device__ __forceinline__ Hit hit(int64_t bb, uint32_t from, uint32_t win, uint32_t c) const {
+    const typename SubCombos<K>::Hit b = SubCombos<K>::hit(bb, from, win, c);
+    const int fa = (int)((combo_fields<K>(false) >> (4u * c)) & 15u), fb = (int)((combo_fields<K>(true) >> (4u * c)) & 15u);
+    return {b.row, wild_others(b.W, fa, fb)};
+  }
+  __device__ __forceinline__ bool judge(const Hit &h, uint32_t cur, uint32_t *pi) const {
+    const uint2 r = this->a.runs[cur];
+    *pi = r.x;
+    return wild_others_within(h.others, r.y, this->a.k);
+  }
+};
+
+template <int K>
+__global__ __launch_bounds__(SHORT_THREADS) void pm_wild_sub_scan(WildArgs a) {
+  __shared__ uint32_t s_bm[sub_ncombos(K) * SHORT_BM_WORDS];
+  __shared__ uint16_t s_q[SHORT_WAVES][SHORT_QCAP];
+  WildCombos<K> combos = {{a, 0, 0, {}}};
+  short_scan(a, combos, s_bm, s_q[0]);
+}
+
+__global__ __launch_bounds__(256) void pm_wild_sub_verify(WildArgs a) {
+  unsigned long long n = *a.list_count;
+  if (n > a.list_cap) n = a.list_cap;
+  verify_staged(a, n, [&](unsigned long long i, const VerifyStage &, pm_hit *hh) __attribute__((always_inline)) {
+    const uint64_t r = a.list[i];
+    return r != ~0ull &&                                              // (a slot its wave reserved and did not need)
+           wild_verify<4>(a, (int)(r >> 61), (int64_t)(r & SHORT_POS_MASK), (uint32_t)(r >> 40) & ((1u << SUB_INDEX_BITS) - 1u), hh);
+  });
+}
+
 // ---- host: tables ------------------------------------------------------------------------------------------------------
 // What the two classes' builds share: the option and alphabet checks, the patterns' last 16 bases in the stream's packing,
 // the split into tiles.
@@ -550,6 +604,89 @@ hipError_t short_sub_launch(const ShortSubDevice &d, const uint8_t *d_text, cons
     if (e != hipSuccess) return e;
   }
   hipLaunchKernelGGL(pm_short_sub_verify, dim3(SUB_VERIFY_BLOCKS), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+// ---- the wild class: tables, launch --------------------------------------------------------------------------------
+
+static_assert(WILD_MAX_ENTRIES == SHORT_SUB_MAX_PATTERNS, "the wild class's entry cap is the short substitution class's measured ceiling (pm_wild_tables.h cannot see pm_internal.h)");
+bool wild_takes(const std::string &s, int k) { return wild_primer_fits(s, k); }
+bool wild_class_fits(const std::vector<std::string> &pats, int k) { return wild_entries_fit(pats, k); }
+
+std::string wild_build(const std::vector<Pattern> &pats, const std::vector<uint32_t> &ids, const Alphabet &alpha, int k, int eos_code, WildTables *out) {
+  WildTables &t = *out;
+  t = WildTables();
+  const bool norm = alpha.nch['A'] == 0 && alpha.nch['C'] == 1 && alpha.nch['G'] == 2 && alpha.nch['T'] == 3;
+  const bool ascii = alpha.size == 256 && alpha.nch['A'] == 'A' && alpha.nch['C'] == 'C' && alpha.nch['G'] == 'G' && alpha.nch['T'] == 'T';
+  if (!norm && !ascii) return "stream alphabet is neither A,C,G,T-normalized nor raw ASCII";
+  const size_t np = pats.size();
+  if (np >= ((size_t)1 << SUB_INDEX_BITS)) return "too many primers in the wild class";
+  std::vector<std::string> strs(np);
+  for (size_t j = 0; j < np; ++j) strs[j] = pats[j].s;
+  WildIndex x;
+  const std::string why = wild_build_index(strs, k, ascii && !norm, &x);
+  if (!why.empty()) return why;
+  t.k = k; t.ascii = x.ascii; t.eos_code = eos_code >= 0 && eos_code < 256 ? eos_code : -1; t.ncombos = x.ncombos;
+  for (int c = 0; c < x.ncombos; ++c) { t.fa[c] = x.fa[c]; t.fb[c] = x.fb[c]; }
+  t.pat_len.resize(np); t.pat_id.resize(np); t.pat_zone.assign(np, 0);
+  for (size_t j = 0; j < np; ++j) {
+    const int L = (int)strs[j].size();
+    t.maxlen = std::max(t.maxlen, L);
+    t.pat_len[j] = (uint8_t)L; t.pat_id[j] = ids[j];
+    const int es = std::max(0, std::min(L, pats[j].esb)), ee = std::max(0, std::min(L, pats[j].eeb));
+    uint32_t z = 0;
+    for (int i = 0; i < L; ++i) if (i < es || i >= L - ee) z |= 1u << i;
+    t.pat_zone[j] = z;
+  }
+  for (size_t e : x.entries) t.max_entries = std::max(t.max_entries, e);
+  t.pat_class = std::move(x.pat_class); t.pat_reg = std::move(x.reg);
+  t.bitmap = std::move(x.bitmap); t.rows = std::move(x.rows); t.runs = std::move(x.runs);
+  return "";
+}
+
+hipError_t wild_upload(const WildTables &t, WildDevice *d, hipStream_t st) {
+  wild_free(d);
+  d->k = t.k; d->maxlen = t.maxlen; d->ascii = t.ascii; d->eos_code = t.eos_code; d->ncombos = t.ncombos; d->npat = t.pat_len.size();
+  d->max_entries = t.max_entries;
+  for (int c = 0; c < SUB_MAX_COMBOS; ++c) { d->fa[c] = t.fa[c]; d->fb[c] = t.fb[c]; }
+  Upload up = {st};
+  up(t.pat_len, &d->pat_len); up(t.pat_id, &d->pat_id); up(t.pat_class, &d->pat_class); up(t.pat_reg, &d->pat_reg); up(t.pat_zone, &d->pat_zone);
+  d->tiles.resize(1);
+  up(t.bitmap, &d->tiles[0].bitmap); up(t.rows, &d->tiles[0].rows); up(t.runs, &d->tiles[0].runs);
+  return up.done();
+}
+
+void wild_free(WildDevice *d) {
+  free_tables({d->pat_len, d->pat_id, d->pat_class, d->pat_reg, d->pat_zone}, &d->tiles);
+  *d = WildDevice();
+}
+
+hipError_t wild_launch(const WildDevice &d, const uint8_t *d_text, const uint32_t *d_packed, int64_t n, int64_t begin, int64_t end,
+                       pm_hit *d_out, unsigned long long *d_counter, uint64_t cap, uint64_t *d_susp, unsigned long long *d_susp_count,
+                       uint64_t susp_cap, hipStream_t st, ScanGeometry *geo_out) {
+  if (!d_packed || !d_susp || !d_susp_count) return hipErrorInvalidValue;
+  if (end > n) end = n;
+  // a hit that ends at e (begin < e <= end) is the window whose last base is p = e - 1
+  const int64_t seg_len = end - begin >= ((int64_t)1 << 24) ? (int64_t)1 << 18 : (int64_t)1 << 16;
+  const int64_t c_lo = begin / seg_len, c_hi = end > begin ? (end - 1) / seg_len : c_lo - 1;
+  const int nseg = (int)(c_hi - c_lo + 1);
+  if (geo_out) { geo_out->seg_len = seg_len; geo_out->nseg = nseg; geo_out->blocks = nseg; geo_out->threads = SHORT_THREADS; geo_out->work_map = 0; }
+  if (end <= begin || d.tiles.empty()) return hipSuccess;
+  WildArgs a;
+  memset(&a, 0, sizeof(a));
+  a.text = d_text; a.n = n; a.packed = d_packed; a.npacked = (n + 15) / 16; a.p_lo = begin; a.p_hi = end; a.chunk0 = c_lo; a.chunk_len = seg_len;
+  a.k = d.k; a.eos_code = d.eos_code; a.ncombos = d.ncombos; a.viol_level = d.viol_level; a.ascii = d.ascii ? 1 : 0;
+  for (int c = 0; c < SUB_MAX_COMBOS; ++c) { a.fa[c] = d.fa[c]; a.fb[c] = d.fb[c]; }
+  a.pat_len = d.pat_len; a.pat_id = d.pat_id; a.pat_class = d.pat_class; a.pat_reg = d.pat_reg; a.pat_zone = d.pat_zone;
+  a.list = d_susp; a.list_count = d_susp_count; a.list_cap = susp_cap;
+  a.out = d_out; a.counter = d_counter; a.cap = cap;
+  const ShortTileDevice &x = d.tiles[0];
+  a.bitmap = x.bitmap; a.rows = x.rows; a.runs = static_cast<const uint2 *>(x.runs); a.tile_base = x.base;
+  if (d.k == 2) hipLaunchKernelGGL(pm_wild_sub_scan<2>, dim3(nseg), dim3(SHORT_THREADS), 0, st, a);
+  else hipLaunchKernelGGL(pm_wild_sub_scan<1>, dim3(nseg), dim3(SHORT_THREADS), 0, st, a);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(pm_wild_sub_verify, dim3(SUB_VERIFY_BLOCKS), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 

@@ -1,7 +1,8 @@
 // pm_verify.h -- the exact stage of the substitution plans, shared by pm_pair.hip (patterns of 20..32 characters: tail of
 // 20 bases, four fields of five) and pm_short.hip (patterns of 16..19 characters: tail of 16 bases, four fields of four),
 // the exact stage of the Bloom plan (seed_verify: pm_seed.hip, rows of 32 or 64 characters),
-// the window arithmetic of pm_short_sub_scan, and the way records leave a verify kernel (pair_emit, verify_staged: the
+// the window arithmetic of pm_short_sub_scan, the class arithmetic and the exact stage of the wild class (wild_others,
+// wild_verify: DESIGN.md 4.13, tests/test_wild_class_host.py), and the way records leave a verify kernel (pair_emit, verify_staged: the
 // loop both pm_pair_verify and pm_short_sub_verify are).  All but those two compiles with a plain C++ compiler as well:
 // tests/test_short_sub_host.py, tests/test_long_sub_host.py and tests/test_long_exact_host.py check it against plain
 // restatements.
@@ -197,6 +198,94 @@ PM_VFN uint32_t sub_key(uint32_t W, int a, int b) { return ((W >> (8 * a)) & 0xf
 // <= k substitutions on the two fields outside the key, P = the pattern's last 16 bases: the key fields of W and P are
 // equal (the run was found through the key), so the distance of the whole words is the distance of the other two fields
 PM_VFN bool sub_others_within(uint32_t W, uint32_t P, int k) { return sym_distance(W ^ P) <= k; }
+
+// ---- the wild class: pm_wild_sub_scan / pm_wild_sub_verify (pm_short.hip) ---------
+// Primers with IUPAC ambiguity letters compared by class.  A window's eight bases outside field pair (a, b), 2 bits each:
+// the lower of the two other fields in bits 0..7, the higher in bits 8..15.
+PM_VFN uint32_t wild_others(uint32_t W, int a, int b) {
+  uint32_t o = 0;
+  int at = 0;
+#pragma unroll
+  for (int f = 0; f < 4; ++f) if (f != a && f != b) { o |= ((W >> (8 * f)) & 0xffu) << (8 * at); ++at; }
+  return o;
+}
+// <= k of those eight bases outside their class: `word` holds four bits per base, bit c = the base accepts stream code c
+// (pm_wild_tables.h wild_class_word).  Every code becomes the one bit of its nibble; a base matches when that bit is set.
+PM_VFN int wild_others_mismatches(uint32_t others, uint32_t word) {
+  uint32_t x = others & 0xffffu;
+  x = (x | (x << 8)) & 0x00ff00ffu; x = (x | (x << 4)) & 0x0f0f0f0fu; x = (x | (x << 2)) & 0x33333333u;   // code j in the low bits of nibble j
+  const uint32_t lo = x & 0x11111111u, hi = (x >> 1) & 0x11111111u;
+  const uint32_t onehot = (~hi & ~lo & 0x11111111u) | ((~hi & lo) << 1) | ((hi & ~lo) << 2) | ((hi & lo) << 3);
+  return 8 - pop32(onehot & word);
+}
+PM_VFN bool wild_others_within(uint32_t others, uint32_t word, int k) { return wild_others_mismatches(others, word) <= k; }
+
+// The exact stage of the wild class: pair_verify with the per-byte verdict replaced -- a stream byte is a mismatch when it
+// is no base (code >= 4 after the raw stream's bytes are mapped to 0..3: N, any other letter) or when its bit is not set in
+// the primer's class nibble (pat_class: 16 bytes per row of 32 characters, character i in byte i / 2, even i low; bit q =
+// "ACGT"[q]).  Everything else is pair_verify's: EOS inside the window and start < 0 reject, the last bytes of the stream
+// are read one by one, zones and viol_level, "reported only through the first combo of the plan whose two fields are
+// clean", the clean-half flags, the record.  At k = 0 the combo must be the one the primer is entered under (pat_reg).
+// Args: text, n, k, eos_code, ascii, ncombos, fa, fb, pat_len, pat_id, pat_class, pat_reg, pat_zone, viol_level.
+template <int FW = 4, int CW = 32, typename Args>
+PM_VFN bool wild_verify(const Args &a, int combo, int64_t p, uint32_t pi, pm_hit *hh) {
+  static_assert(FW == 4 && CW == 32, "fields of four bases, rows of 32 characters");
+  const int L = a.pat_len[pi];
+  const int64_t start = p + 1 - L;
+  if (start < 0) return false;
+  const uint4 pcv = *reinterpret_cast<const uint4 *>(a.pat_class + (size_t)pi * (CW / 2));
+  const uint32_t pcw[4] = {pcv.x, pcv.y, pcv.z, pcv.w};
+  uint32_t tw[CW / 4];
+  if (start + CW <= a.n) {
+    uint4 t[CW / 16];
+#pragma unroll
+    for (int v = 0; v < CW / 16; ++v) __builtin_memcpy(&t[v], a.text + start + 16 * v, 16);
+#pragma unroll
+    for (int v = 0; v < CW / 16; ++v) { tw[4 * v] = t[v].x; tw[4 * v + 1] = t[v].y; tw[4 * v + 2] = t[v].z; tw[4 * v + 3] = t[v].w; }
+  } else {                                            // the last bytes of the stream
+#pragma unroll
+    for (int d = 0; d < CW / 4; ++d) {
+      tw[d] = 0;
+      for (int b = 0; b < 4; ++b) { const int64_t q = start + 4 * d + b; if (q < a.n) tw[d] |= (uint32_t)a.text[q] << (8 * b); }
+    }
+  }
+  uint32_t mism = 0, eos = 0;                         // bit i: stream byte i is outside the class of character i / is EOS
+#pragma unroll
+  for (int i = 0; i < CW; ++i) {
+    const uint32_t ch = (tw[i / 4] >> (8 * (i & 3))) & 0xffu;
+    uint32_t code = ch;                               // A,C,G,T = 0..3; anything else >= 4
+    if (a.ascii) code = ch == 'A' ? 0u : ch == 'C' ? 1u : ch == 'G' ? 2u : ch == 'T' ? 3u : 4u;
+    const uint32_t cls = (pcw[i / 8] >> (4 * (i & 7))) & 15u;
+    if (code >= 4u || !((cls >> code) & 1u)) mism |= 1u << i;
+    if ((int)ch == a.eos_code) eos |= 1u << i;
+  }
+  const uint32_t lenmask = L >= CW ? ~0u : ((1u << L) - 1u);
+  mism &= lenmask;
+  if (a.eos_code >= 0 && (eos & lenmask)) return false;   // EOS inside the window: never a candidate
+  int ham = pop32(mism);
+  if (ham > a.k) return false;
+  if (mism & a.pat_zone[pi]) {                        // a substitution inside an exact zone (pair_verify)
+    if (a.viol_level <= 0) return false;
+    ham = a.viol_level;
+  }
+  if (a.k == 0) {
+    if (combo != (int)a.pat_reg[pi]) return false;
+  } else {
+    const uint32_t tail = mism >> (L - 4 * FW);       // the bases the plan looks at
+    uint32_t dirty = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) if ((tail >> (FW * j)) & ((1u << FW) - 1u)) dirty |= 1u << j;
+    int first = -1;
+    for (int c = 0; c < a.ncombos && first < 0; ++c)
+      if (!((dirty >> a.fa[c]) & 1u) && !((dirty >> a.fb[c]) & 1u)) first = c;
+    if (first != combo) return false;
+  }
+  const int half = L / 2;
+  const bool left_clean = (mism & ((1u << half) - 1u)) == 0, right_clean = (mism >> half) == 0;
+  hh->end = p + 1; hh->pid = a.pat_id[pi]; hh->k = (uint8_t)ham;
+  hh->aux[0] = (uint8_t)((left_clean ? 1 : 0) | (right_clean ? 2 : 0)); hh->aux[1] = hh->aux[2] = 0;
+  return true;
+}
 
 #if defined(__HIPCC__)
 // Output of the verify kernels.  The record list's end is ONE counter for the whole grid and same-address atomics

@@ -223,18 +223,20 @@ class PatternMatch:
     patterns of 33..64 characters stay on the halves plan (bit 3); each acts on its own option sets.
     long_align=True (bit 4) changes no scan: with indels and k = 1 .. 3 the hits of patterns of 33..64 characters are re-aligned on
     the device by align_hits_device, count_scan and pcr_pair, not by host threads.
+    wildcard primers: wild_class=True (bit 5) lets -w primers of 16..32 characters with more than 16 concrete variants run on
+    pm_wild_sub_scan (k = 0 on keyword_tree / shift_and, -K 1 / -K 2 on filter_bitvec) and not on the bit-parallel residue.
     """
 
     def __init__(self, k=0, indels=True, eos="\n", semantics=SEM_AUTO, kernel=KERNEL_AUTO, device=0,
                  wildcards=False, text_n=False, long_patterns=False, long_exact=False, long_edits=False,
-                 long_halves=False, long_align=False):
+                 long_halves=False, long_align=False, wild_class=False):
         self._L = load_library()
         cfg = _Config()
         cfg.abi_version, cfg.semantics, cfg.kernel, cfg.k = 1, semantics, kernel, k
         cfg.indels, cfg.wildcards, cfg.text_n = int(bool(indels)), int(bool(wildcards)), int(bool(text_n))
         cfg.eos = ord(eos) if isinstance(eos, str) else int(eos)
         cfg.device = device
-        cfg.long_patterns = int(bool(long_patterns)) | (2 if long_exact else 0) | (4 if long_edits else 0) | (8 if long_halves else 0) | (16 if long_align else 0)
+        cfg.long_patterns = int(bool(long_patterns)) | (2 if long_exact else 0) | (4 if long_edits else 0) | (8 if long_halves else 0) | (16 if long_align else 0) | (32 if wild_class else 0)
         self._h = C.c_void_p()
         rc = self._L.pm_create(C.byref(cfg), C.byref(self._h))
         if rc:
