@@ -85,6 +85,7 @@ typedef enum {
 #define PM_LONG_HALVES 8   /* -k 1 / -k 2 under exact_halves: patterns of 33..64 characters may run on the halves plan */
 #define PM_LONG_ALIGN 16   /* -k 1 .. -k 3 (edits): hits of patterns of 33..64 characters are re-aligned on the device */
 #define PM_WILD_CLASS 32   /* -w, k = 0 / -K 1 / -K 2: patterns of 16..32 characters with more than 16 concrete variants may run on pm_wild_sub_scan */
+#define PM_EDIT_PAIR  64   /* -k 1 / -k 2: the edit plan's first stage may run on the pair geometry beyond -k 2 on one tile (every tile, -k 1, exact_bases) */
 
 /* Replaces the constructor arguments of the reference engines as pick_pattern_index passes them
  * (select.cc:19-30): nmismatch, indels, wildcard, textn, eos.  dna_mut is not supported. */
@@ -98,7 +99,7 @@ typedef struct {
   int32_t text_n;          /* -W: a text N also matches (shift_and.cc:112) */
   int32_t eos;             /* raw end-of-sequence char, '\n' in the CLIs */
   int32_t device;          /* HIP device ordinal */
-  int32_t long_patterns;   /* a bit set (PM_LONG_SUB | PM_LONG_EXACT | PM_LONG_EDITS | PM_LONG_HALVES | PM_LONG_ALIGN | PM_WILD_CLASS; 0 = the routing of
+  int32_t long_patterns;   /* a bit set (PM_LONG_SUB | PM_LONG_EXACT | PM_LONG_EDITS | PM_LONG_HALVES | PM_LONG_ALIGN | PM_WILD_CLASS | PM_EDIT_PAIR; 0 = the routing of
                               earlier versions).
                               PM_LONG_SUB (1) = with PM_KERNEL_AUTO, -K 1 / -K 2 (substitutions only) and filter_bitvec, bare
                               shift_and_inexact or exact_halves on an A,C,G,T-normalized or raw ASCII stream, patterns
@@ -134,7 +135,17 @@ typedef struct {
                               pm_wild_sub_verify, beside the main class or alone, and not on the
                               bit-parallel residue; a list whose expanded keys exceed 24,000 in some field pair keeps
                               the routing without the bit.  It has nothing to do with the pattern's length: the bit
-                              lives here because this field is the one set of routing permissions.  (The field took
+                              lives here because this field is the one set of routing permissions.
+                              PM_EDIT_PAIR (64) = -k 1 / -k 2 (edits) on the seed family's edit plan, patterns of 20..32
+                              characters (20..64 with PM_LONG_EDITS): the first stage runs on the pair geometry
+                              (pm_pair_edit_scan + pm_pair_edit_resolve) where it ran on the hashed-piece
+                              kernel pm_edit_scan -- lists of more than one pattern tile at -k 2 (a table set per tile),
+                              -k 1 under filter_bitvec or bare shift_and_inexact (pm_pair_edit_scan_k1: two tests per
+                              window), and exact_bases -k 1 / -k 2 (pm_bases_verify behind it; patterns of up to 32
+                              characters).  The hits are the same either way.  -k 2 on one tile without exact_bases runs
+                              there with or without the bit; PM_EDIT_SCAN=hash / bloom and PM_EDIT_PAIR=off in the
+                              environment pm_create reads keep the routing without the bit.  Not set = the routing of
+                              earlier versions.  (The field took
                               the place of reserved[0]: same layout, same PM_ABI_VERSION.) */
   int32_t reserved[6];
 } pm_config;
@@ -441,7 +452,9 @@ int pm_last_kernel_time(pm_handle *h, float *ms, int *launches);
  * waves and field pairs; out[6] times pm_scan halved its piece length since pm_init because a range's record lists would have
  * outgrown its bound (hit-dense text); out[7] look-ahead scans pm_scan / pm_scan_view enqueued since pm_init for the range
  * they expected next (see pm_scan_view).  While such a scan is in flight the call waits for it (it stays pm_scan's to
- * collect): out[1] and out[3..5] are then that scan's, out[0] the range's that was handed out.  n <= 8 values are written. */
+ * collect): out[1] and out[3..5] are then that scan's, out[0] the range's that was handed out.  out[8] suspects between
+ * pm_pair_edit_scan and pm_pair_edit_resolve where the edit plan's first stage runs on the pair geometry (the pattern tile
+ * with most; 0 elsewhere).  n <= 9 values are written. */
 int pm_scan_stats(pm_handle *h, uint64_t *out, int n);
 
 /* Measurement helper (no reference counterpart; DESIGN.md 4.6 "pair geometry for edits"): on a -K 2 handle of the pair plan,

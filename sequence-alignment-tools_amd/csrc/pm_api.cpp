@@ -98,8 +98,10 @@ struct pm_handle {
   SeedDevice sd;                      // first pattern tile (plan parameters are read from here)
   std::vector<SeedDevice> sd_more;    // further tiles when the pattern set is too large for one LDS filter
   std::vector<PairDevice> pair;       // -K 1 / -K 2 on 20..32 character patterns: the pair plan's tiles (pm_pair.hip) instead of sd
-  PairDevice epair;                   // -k 2 (filter_bitvec / shift_and_inexact): the pair geometry as the edit plan's first stage (one pattern tile)
-  bool epair_on = false;
+  std::vector<PairDevice> epair;      // the pair geometry as the edit plan's first stage: a table set per seed tile (same cut, same pattern order as sd / sd_more).
+                                      // -k 2 on one tile without exact_bases; with the PM_EDIT_PAIR bit also every tile, -k 1 and exact_bases
+  unsigned long long last_suspects = 0;   // suspects of the last scan's fullest tile (pm_scan_stats [8])
+  bool epair_on = false;              // all tiles or none: routes are never mixed across tiles
   bool seed_flags = false;            // exact_halves on whole-pattern Hamming candidates (aux flags)
   bool bases_flags = false;           // exact_bases -K on whole-pattern Hamming candidates with clean exact zones (pair plan): records are final
   bool zoned = false;                 // some pattern has exact-base constraints
@@ -273,7 +275,10 @@ struct pm_handle {
 // per-tile record counts between a scan's first-stage and verify kernels: [0] unused, [1 + t] tile t, then 8 measurement counters
 // [SHORT_COUNT_AT]: seed records of the short class (all its tiles); the pair plan's short class counts its suspects there
 // [WILD_COUNT_AT]: suspects of the wild class
-constexpr size_t SEEDCOUNT_WORDS = 1 + 256 + 8 + 2;
+// [EPAIR_COUNT_AT + t]: suspects of tile t between pm_pair_edit_scan and pm_pair_edit_resolve (the edit plan on the pair geometry);
+// a word per tile, zeroed with the others in front of the tile loop, so every tile counts from zero in stream order
+constexpr size_t SEEDCOUNT_WORDS = 1 + 256 + 8 + 2 + 256;
+constexpr size_t EPAIR_COUNT_AT = 1 + 256 + 8 + 2;
 constexpr size_t SHORT_COUNT_AT = 1 + 256 + 8;
 constexpr size_t WILD_COUNT_AT = 1 + 256 + 8 + 1;
 
@@ -451,6 +456,7 @@ static void read_knobs(Knobs *k) {
   k->long_edits_off = is("PM_LONG_EDITS", "off");
   k->long_halves_off = is("PM_LONG_HALVES", "off");
   k->wild_off = is("PM_WILD_CLASS", "off");
+  k->edit_pair_off = is("PM_EDIT_PAIR", "off");
   k->debug = getenv("PM_DEBUG") != nullptr;
 }
 
@@ -515,7 +521,8 @@ static void free_device(pm_handle *h) {
   h->sd_more.clear();
   for (PairDevice &d : h->pair) pair_free(&d);
   h->pair.clear();
-  pair_free(&h->epair); h->epair_on = false;
+  for (PairDevice &d : h->epair) pair_free(&d);
+  h->epair.clear(); h->epair_on = false;
   if (h->d_cands) (void)hipFree(h->d_cands);
   { void *hx[] = {h->d_ext, h->d_half_codes, h->d_half_len, h->d_hesb, h->d_heeb, h->d_dp_codes, h->d_dp_esb, h->d_dp_eeb, h->d_seed_count, h->d_seeds, h->d_susp}; for (void *q : hx) if (q) (void)hipFree(q); }
   h->d_seed_count = nullptr; h->d_seeds = nullptr; h->d_susp = nullptr; h->susp_cap = 0;
@@ -919,7 +926,8 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
   h->sd_more.clear();
   for (PairDevice &d : h->pair) pair_free(&d);
   h->pair.clear();
-  pair_free(&h->epair); h->epair_on = false;
+  for (PairDevice &d : h->epair) pair_free(&d);
+  h->epair.clear(); h->epair_on = false;
   // tables pm_finalize_device builds on first use depend on the alphabet mapping and the pattern
   // list of THIS init: drop the ones of an earlier init
   { void *lazy[] = {h->d_dp_codes, h->d_dp_esb, h->d_dp_eeb, h->d_fpat_len, h->d_fpat_id}; for (void *q : lazy) if (q) (void)hipFree(q); }
@@ -1203,18 +1211,36 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
       h->half_ranked_any = h->sd.half_ranked;
       for (const SeedDevice &d : h->sd_more) h->half_ranked_any = h->half_ranked_any || d.half_ranked;
       h->edits_dev = edits_mode;
-      // -k 2 on one pattern tile: the first stage runs on the PAIR geometry (pm_pair.hip, edit plan: 14 field-pair tests per
-      // window instead of 34 hashed piece triples; round 4) -- its tables are the substitution plan's with two patterns per
-      // slot, over the same pattern list as the automaton records of h->sd (seed records carry indices into it)
-      if (edits_mode && h->cfg.k == 2 && !h->bases_edits && h->sd_more.empty() && !h->knobs.edit_bloom && !h->knobs.edit_hash && !sp.empty()) {
-        PairTables pt;
-        const std::string msg = pair_build(sp, sid, h->alpha, 2, h->eos_code, &pt, h->knobs.pair_row, 2, h->nlong_edits ? PAIR_MAX_LEN_WIDE : PAIR_MAX_LEN,
-                                           (h->knobs.seed_debug & 64) != 0);   // (the tables read a pattern's last 20 bases only)
-        if (msg.empty()) {
-          HIP_TRY(h, pair_upload(pt, &h->epair, h->stream));
-          h->epair.knobs = h->knobs;
-          h->epair_on = true;
+      // The edit plan's first stage on the PAIR geometry (pm_pair.hip): -k 2 on one pattern tile (14 field-pair
+      // tests per window instead of 34 hashed piece triples; round 4) -- and, with the PM_EDIT_PAIR bit of
+      // pm_config.long_patterns, every tile of a larger list, -k 1 (2 tests instead of 8: pm_pair_edit_scan_k1) and exact_bases
+      // (pm_bases_verify behind it; tiles of up to 32 characters, as seed_launch demands).  Its tables are the substitution
+      // plan's with two patterns per slot, one set per seed tile over that tile's patterns (the same cut and order as the
+      // automaton records of h->sd / h->sd_more: seed records carry indices into them).  A tile pair_build refuses leaves
+      // the whole list on pm_edit_scan: routes are never mixed across tiles.
+      const bool epair_more = (h->cfg.long_patterns & PM_EDIT_PAIR) && !h->knobs.edit_pair_off;
+      const bool epair_base = h->cfg.k == 2 && !h->bases_edits && h->sd_more.empty();
+      if (edits_mode && (epair_base || (epair_more && (h->cfg.k == 1 || h->cfg.k == 2) && !(h->bases_edits && h->nlong_edits))) &&
+          !h->knobs.edit_bloom && !h->knobs.edit_hash && !sp.empty()) {
+        bool ok = true;
+        for (size_t ti = 0; ti < ntile && ok; ++ti) {
+          const size_t lo = ti * per, hi = std::min(sp.size(), lo + per);
+          std::vector<Pattern> tp(sp.begin() + lo, sp.begin() + hi);
+          std::vector<uint32_t> tid(sid.begin() + lo, sid.begin() + hi);
+          PairTables pt;
+          const std::string msg = pair_build(tp, tid, h->alpha, h->cfg.k, h->eos_code, &pt, h->knobs.pair_row, 2, h->nlong_edits ? PAIR_MAX_LEN_WIDE : PAIR_MAX_LEN,
+                                             (h->knobs.seed_debug & 64) != 0);   // (the tables read a pattern's last 20 bases only)
+          ok = msg.empty();
+          if (!ok) break;
+          h->epair.emplace_back();
+          HIP_TRY(h, pair_upload(pt, &h->epair.back(), h->stream));
+          h->epair.back().knobs = h->knobs;
         }
+        if (ok && h->epair.size() == 1 + h->sd_more.size()) {
+          h->epair_on = true;
+          if (h->knobs.debug) fprintf(stderr, "[pm] edit plan: first stage on the pair geometry (k = %d, %zu tiles%s)\n", h->cfg.k, h->epair.size(), h->bases_edits ? ", exact_bases" : "");
+        }
+        else { for (PairDevice &d : h->epair) pair_free(&d); h->epair.clear(); }
       }
       if (halves_mode) {
         const size_t nh = h->inner.size();
@@ -1817,11 +1843,14 @@ extern "C" int pm_describe(const pm_handle *h, char *buf, size_t buflen) {
     }
   }
   else if (h->kern == PM_KERNEL_SEED && h->edits_dev && h->epair_on) {
-    snprintf(buf, buflen, "kernel=pm_pair_edit_scan+pm_pair_edit_resolve+pm_edits_verify tiles=1 tests=14 fields=2-of-4 x 5 bases, displaced by |d| <= 2 window=20 row_slots=%d slot_patterns=2 chunk=%lld nchunks=%d grid=%d block=%d lds=%d schedule=%s",
-             h->epair.stride, (long long)h->geo.seg_len, h->geo.nseg, h->geo.blocks, h->geo.threads, PAIR_LDS_BYTES, pair_schedule_name(h->geo));
+    // (-k 1: the two undisplaced tests of pm_pair_edit_scan_k1; exact_bases: pm_bases_verify reads the seed records)
+    snprintf(buf, buflen, "kernel=pm_pair_edit_scan+pm_pair_edit_resolve+%s tiles=%d tests=%d fields=2-of-4 x 5 bases, displaced by |d| <= %d window=20 row_slots=%d slot_patterns=2 chunk=%lld nchunks=%d grid=%d block=%d lds=%d schedule=%s",
+             h->bases_edits ? "pm_bases_verify" : "pm_edits_verify", (int)h->epair.size(), h->epair[0].k == 1 ? 2 : 14, h->epair[0].k == 1 ? 0 : 2, h->epair[0].stride, (long long)h->geo.seg_len, h->geo.nseg, h->geo.blocks, h->geo.threads, PAIR_LDS_BYTES, pair_schedule_name(h->geo));
     if (h->nlong_edits) {
       const size_t at = strlen(buf);
-      if (at < buflen) snprintf(buf + at, buflen - at, " with %zu patterns of 33..64 characters (pm_edits_verify_wide, wide tiles=%d)", h->nlong_edits, h->sd.wide ? 1 : 0);
+      int wide = h->sd.wide ? 1 : 0;
+      for (const SeedDevice &d : h->sd_more) wide += d.wide ? 1 : 0;
+      if (at < buflen) snprintf(buf + at, buflen - at, " with %zu patterns of 33..64 characters (pm_edits_verify_wide, wide tiles=%d)", h->nlong_edits, wide);
     }
     if (h->nrest) {
       const size_t at = strlen(buf);
@@ -1941,20 +1970,21 @@ extern "C" int pm_scan_candidates_async(pm_handle *h, int64_t begin, int64_t end
         es.own_lo = h->own_begin; es.own_hi = h->own_end;
       }
       const SeedDevice &d = t == 0 ? h->sd : h->sd_more[t - 1];
-      if (h->epair_on && h->edits_dev && t == 0) {
+      if (h->epair_on && h->edits_dev) {
         // first stage on the pair geometry: windows whose frame can hold an end in (begin, end] are the positions begin - 3 .. end + 1
+        // (every tile: its own tables and suspect counter; the suspect and seed lists are reused tile after tile in stream order)
         const size_t want_susp = (size_t)((end - begin) / 10) + ((size_t)1 << 20);
         if (!h->d_susp || h->susp_cap < want_susp) {
           h->susp_cap = std::max(h->susp_cap, want_susp);
           PM_TRY(dev_regrow(h, &h->d_susp, h->susp_cap * PAIR_SUSPECT_BYTES, "d_susp"));
         }
-        HIP_TRY(h, pair_launch(h->epair, h->d_text, h->d_packed, h->n, std::max<int64_t>(0, begin - 3), std::min<int64_t>(h->n, end + 2), h->d_cands, h->d_counter, h->cap,
-                               h->d_susp, h->d_seed_count + 260, h->susp_cap, h->stream, &h->geo, nullptr, 3, h->d_seeds, h->d_seed_count + 1, h->seed_cap));
+        HIP_TRY(h, pair_launch(h->epair[(size_t)t], h->d_text, h->d_packed, h->n, std::max<int64_t>(0, begin - 3), std::min<int64_t>(h->n, end + 2), h->d_cands, h->d_counter, h->cap,
+                               h->d_susp, h->d_seed_count + EPAIR_COUNT_AT + t, h->susp_cap, h->stream, t == 0 ? &h->geo : nullptr, nullptr, 3, h->d_seeds, h->d_seed_count + 1 + t, h->seed_cap));
         es.skip_scan = true;
       }
       HIP_TRY(h, seed_launch(d, h->d_text, h->d_packed, h->n, begin, end, h->d_cands, h->d_counter, h->cap, h->stream, t == 0 && !es.skip_scan ? &h->geo : nullptr, &es));
     }
-    h->last_launches = 2 * ntiles + (h->epair_on && h->edits_dev ? 1 : 0);
+    h->last_launches = (h->epair_on && h->edits_dev ? 3 : 2) * ntiles;
     if (h->nshort) {
       // the short class into the same record buffer; its seed records reuse the seed list, which the main class's automaton
       // launch has read by then (stream order), under a counter of their own
@@ -2335,7 +2365,7 @@ static int scan_wait_once(pm_handle *h, size_t *n_out) {
   if (h->h_seed_count && h->kern == PM_KERNEL_SEED && (h->edits_dev || (h->halves_dev && h->half_ranked_any) || !h->pair.empty())) {
     const size_t tiles = !h->pair.empty() ? h->pair.size() : 1 + h->sd_more.size();
     for (size_t t = 0; t < tiles && t < 256; ++t) h->last_peak = std::max(h->last_peak, h->h_seed_count[1 + t]);
-    h->last_peak = std::max(h->last_peak, h->h_seed_count[260]);
+    for (size_t t = 0; t < h->epair.size() && t < 256; ++t) h->last_peak = std::max(h->last_peak, h->h_seed_count[EPAIR_COUNT_AT + t]);
     if (h->nshort || h->nssub) h->last_peak = std::max(h->last_peak, h->h_seed_count[SHORT_COUNT_AT]);
   }
   if (h->bound_on && cnt > dense_bound(h)) return dense_fail(h, "candidate records", cnt);
@@ -2354,10 +2384,13 @@ static int scan_wait_once(pm_handle *h, size_t *n_out) {
       PM_TRY(dev_regrow(h, &h->d_seeds, h->seed_cap * sizeof(uint64_t), "d_seeds"));
       return SCAN_AGAIN;
     }
-    if (h->bound_on && h->epair_on && h->edits_dev && h->h_seed_count[260] > dense_bound(h))
-      return dense_fail(h, "suspects of the edit-distance plan", h->h_seed_count[260]);
-    if (h->epair_on && h->edits_dev && h->h_seed_count[260] > h->susp_cap) {   // the pair geometry's suspect list between its two kernels
-      h->susp_cap = (size_t)h->h_seed_count[260] + (size_t)h->h_seed_count[260] / 8 + 1024;
+    unsigned long long worst_susp = 0;                             // the pair geometry's suspect list between its two kernels: the tile with most
+    if (h->epair_on && h->edits_dev) for (size_t t = 0; t < h->epair.size() && t < 256; ++t) worst_susp = std::max(worst_susp, h->h_seed_count[EPAIR_COUNT_AT + t]);
+    h->last_suspects = worst_susp;
+    if (h->bound_on && worst_susp > dense_bound(h))
+      return dense_fail(h, "suspects of the edit-distance plan", worst_susp);
+    if (worst_susp > h->susp_cap) {
+      h->susp_cap = (size_t)worst_susp + (size_t)worst_susp / 8 + 1024;
       h->last_count = 0;
       PM_TRY(dev_regrow(h, &h->d_susp, h->susp_cap * PAIR_SUSPECT_BYTES, "d_susp"));
       return SCAN_AGAIN;
@@ -2488,7 +2521,7 @@ extern "C" int pm_candidates_device(pm_handle *h, void **d_records, size_t *n) {
 
 extern "C" int pm_scan_stats(pm_handle *h, uint64_t *out, int n) {
   if (!h || !h->inited || !out || n < 0) return PM_E_INVALID;
-  uint64_t v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  uint64_t v[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   // pm_scan's look-ahead scan copies its counters into h_seed_count when it ends: wait for it (it stays pm_scan's to collect)
   if (h->spec && h->scan_pending) (void)hipStreamSynchronize(h->stream);
   v[0] = h->last_count;
@@ -2502,7 +2535,8 @@ extern "C" int pm_scan_stats(pm_handle *h, uint64_t *out, int n) {
   v[2] = h->internal_rescans;
   v[6] = h->range_splits;
   v[7] = h->lookaheads;
-  for (int i = 0; i < n && i < 8; ++i) out[i] = v[i];
+  v[8] = h->last_suspects;
+  for (int i = 0; i < n && i < 9; ++i) out[i] = v[i];
   return PM_OK;
 }
 

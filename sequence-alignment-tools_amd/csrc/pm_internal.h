@@ -29,7 +29,7 @@ struct Alphabet {
 };
 
 // Test and measurement knobs (PM_SEED_CHUNK, PM_SEED_GROUP, PM_SEED_DEBUG, PM_SEED_TILE, PM_PAIR, PM_PAIR_ROW, PM_PAIR_MAP, PM_HALF_SCAN,
-// PM_EDIT_SCAN, PM_EDIT_TABLE_LOG, PM_SHORT_SCAN, PM_SHORT_TILE, PM_SHORT_SUB, PM_LONG_SUB, PM_LONG_EXACT, PM_LONG_EDITS, PM_LONG_HALVES, PM_WILD_CLASS, PM_BITPAR_TP, PM_BITPAR_SEGLEN, PM_DEBUG).  The environment is read ONCE, by
+// PM_EDIT_SCAN, PM_EDIT_PAIR, PM_EDIT_TABLE_LOG, PM_SHORT_SCAN, PM_SHORT_TILE, PM_SHORT_SUB, PM_LONG_SUB, PM_LONG_EXACT, PM_LONG_EDITS, PM_LONG_HALVES, PM_WILD_CLASS, PM_BITPAR_TP, PM_BITPAR_SEGLEN, PM_DEBUG).  The environment is read ONCE, by
 // pm_create (pm_api.cpp read_knobs), into the handle: nothing on the init or launch path calls getenv, and a
 // handle's behaviour does not change when its caller's environment does.  Every field's 0 / -1 / false = unset.
 struct Knobs {
@@ -42,7 +42,8 @@ struct Knobs {
   int pair_map = -1;                 // PM_PAIR_MAP: workgroup -> (field pair, chunk) of the pair kernels (pm_workmap.h PAIR_MAP_*; -1: by range size)
   bool half_bloom = false;           // exact_halves -k on the round-1 form (PM_HALF_SCAN=bloom)
   bool edit_bloom = false;           // edits: first stage = the round-1 pm_seed_scan instance (PM_EDIT_SCAN=bloom)
-  bool edit_hash = false;            // edits: first stage = round 2's pm_edit_scan (PM_EDIT_SCAN=hash) where the pair geometry would run (-k 2, one tile)
+  bool edit_hash = false;            // edits: first stage = round 2's pm_edit_scan (PM_EDIT_SCAN=hash) wherever the pair geometry would run
+  bool edit_pair_off = false;        // PM_EDIT_PAIR=off: the pair geometry runs as the edit plan's first stage only where it ran without the PM_EDIT_PAIR bit of pm_config.long_patterns (A/B runs, tests)
   int edit_table_log = 0;            // edits: log2 of the key map's bits
   int bitpar_tp = -1;                // force the text-parallel (1) / tile (0) form of the bit-parallel kernel
   long long bitpar_seglen = 0;

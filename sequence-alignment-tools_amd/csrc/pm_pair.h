@@ -86,6 +86,8 @@ hipError_t pair_launch(const PairDevice &d, const uint8_t *d_text, const uint32_
                        uint64_t *seed_out = nullptr, unsigned long long *seed_count = nullptr, uint64_t seed_cap = 0);
 // floor_mode 3 = the edit-distance plan on the pair geometry (-k 2): pm_pair_edit_scan<3> (14 tests per window, edit_cost) +
 // pm_pair_edit_resolve, seed records (pattern index << 40 | position) into seed_out for pm_edits_verify; tables built
-// with slot_patterns = 2.  floor_mode 1, 2: measurement kernels (pm_measure_pair_edit_floor).
+// with slot_patterns = 2.  On tables built with k = 1 (two field pairs) floor_mode 3 runs the one-edit instance:
+// pm_pair_edit_scan_k1 (the tests (0,1,0) and (2,3,0)) + pm_pair_edit_resolve<1>.  floor_mode 1, 2: measurement kernels
+// (pm_measure_pair_edit_floor).
 
 }  // namespace pm

@@ -226,12 +226,13 @@ __device__ __forceinline__ int region_cost(uint32_t p, uint32_t wlo, uint32_t wh
 // match in place, one key hit in a thousand.  So the scan tries the sets that cost <= 1 in each region (three shifts instead
 // of five, no order check) and lets everything through whose one region is exact: 0.2 % more suspects from these three tests,
 // which were 40 % of the compare's instructions.
-template <int A, int B, int DSP, bool LOOSE = false>
+// K = the edit budget of the plan (2: -k 2; 1: -k 1, whose two tests (0,1,0) and (2,3,0) leave one region and one edit).
+template <int A, int B, int DSP, bool LOOSE = false, int K = 2>
 __device__ __forceinline__ int edit_cost(uint32_t o, uint32_t wlo, uint32_t whi) {
   constexpr int C = (A != 0 && B != 0) ? 0 : ((A != 1 && B != 1) ? 1 : 2);
   constexpr int D = (A != 3 && B != 3) ? 3 : ((A != 2 && B != 2) ? 2 : 1);
-  constexpr int AD = DSP < 0 ? -DSP : DSP, BUD = 2 - AD;
-  constexpr int BUD2 = LOOSE && DSP == 0 ? 1 : BUD;                  // two regions, nothing forced: see above
+  constexpr int AD = DSP < 0 ? -DSP : DSP, BUD = K - AD;
+  constexpr int BUD2 = LOOSE && DSP == 0 && BUD > 1 ? 1 : BUD;                  // two regions, nothing forced: see above
   static_assert(B > A + 1 || DSP == 0, "adjacent key fields are not displaced");
   if constexpr (A == 0 && B == 1) return region_cost<REG_R, 10, 10, 0, 0, BUD>(o, wlo, whi);                       // fields 2, 3 behind B
   else if constexpr (A == 2 && B == 3) return region_cost<REG_L, 10, 0, 0, 0, BUD>(o, wlo, whi);                   // fields 0, 1 in front of A
@@ -282,7 +283,16 @@ __device__ __forceinline__ void edit_variant(int v, F &&f) {
     default: break;
   }
 }
+// -k 1: the two tests the one-edit cover needs (tests/test_short_cover.py K1), under the numbers they have among the 14, on
+// the two tables pair_build makes for k = 1 (field pairs (0,1) and (2,3))
+template <typename F>
+__device__ __forceinline__ void edit_variant_k1(int v, F &&f) {
+  using std::integral_constant;
+  if (v == 0) f(integral_constant<int, 0>(), integral_constant<int, 1>(), integral_constant<int, 0>());
+  else if (v == 13) f(integral_constant<int, 2>(), integral_constant<int, 3>(), integral_constant<int, 0>());
+}
 __device__ __host__ __forceinline__ int edit_variant_table(int var) { return var == 0 ? 0 : (var <= 3 ? 1 : (var <= 8 ? 2 : (var == 9 ? 3 : (var <= 12 ? 4 : 5)))); }
+__device__ __forceinline__ int edit_variant_table_k1(int var) { return var == 13 ? 1 : 0; }
 
 // pair_verify<5> (the exact part of the verify), pair_emit and its LDS stage: pm_verify.h, shared with pm_short.hip
 
@@ -368,7 +378,8 @@ __global__ __launch_bounds__(256) void pm_pair_verify_wide(PairArgs a) { pair_ve
 // two patterns of the slot, the cheapest necessary condition for "<= 2 edits on the other ten bases" that was found: mismatch
 // masks at five shifts, tiered AND / popcount tests.  Neither produces a hit list: they exist to be timed.  With DSP = 0 and
 // FLOOR = 0 (the product's instantiations) every `if constexpr` below takes the branch that was there before.
-template <int A, int B, int DSP = 0, int FLOOR = 0>
+// K (FLOOR = 3 only): the edit budget edit_cost runs with, and the cost a key hit may have.
+template <int A, int B, int DSP = 0, int FLOOR = 0, int K = 2>
 __device__ __forceinline__ void pair_scan_body(const PairArgs &a, const int combo, const int cj, const int variant = 0) {
   constexpr int C = (A != 0 && B != 0) ? 0 : ((A != 1 && B != 1) ? 1 : 2);
   constexpr int D = (A != 3 && B != 3) ? 3 : ((A != 2 && B != 2) ? 2 : 1);
@@ -518,10 +529,10 @@ __device__ __forceinline__ void pair_scan_body(const PairArgs &a, const int comb
     // any sign bit = suspicious (if the entry holds a window at all)
     if constexpr (FLOOR == 3) {
       // the slot's two patterns (the table of the edit plan holds two per key; more: walk flag): can the other ten bases be
-      // brought to the text with the edits that are left?  cost - 3 < 0 = yes as far as edit_cost can tell
+      // brought to the text with the edits that are left?  cost - (K + 1) < 0 = yes as far as edit_cost can tell
       const uint32_t lo = e_wo[PH], hi = e_hi[PH];
-      const int d1 = edit_cost<A, B, DSP, true>(e_sl[PH].x & f20v, lo, hi) - 3;
-      const int d2 = edit_cost<A, B, DSP, true>(__builtin_amdgcn_alignbit(e_sl[PH].y, e_sl[PH].x, 20) & f20v, lo, hi) - 3;
+      const int d1 = edit_cost<A, B, DSP, true, K>(e_sl[PH].x & f20v, lo, hi) - (K + 1);
+      const int d2 = edit_cost<A, B, DSP, true, K>(__builtin_amdgcn_alignbit(e_sl[PH].y, e_sl[PH].x, 20) & f20v, lo, hi) - (K + 1);
       const bool susp = (int)(((uint32_t)(d1 | d2) | e_sl[PH].y) & e_okm[PH]) < 0;
       enqueue(susp, lo, hi, ((e_rel[PH] >> 4) << 10) + 16u * (uint32_t)lane + (e_rel[PH] & 15u));
     } else if constexpr (FLOOR == 2) {
@@ -736,6 +747,27 @@ __global__ __launch_bounds__(PAIR_THREADS) void pm_pair_edit_scan(PairArgs a) {
   }
 }
 
+// The one-edit instance (-k 1): one edit leaves fields {0,1} or fields {2,3} of the last 20 bases untouched and in place
+// relative to each other, so the cover is the two undisplaced tests (0,1,0) and (2,3,0) -- a.ncombos = 2, on the two tables
+// pair_build makes for k = 1 -- and what remains is ONE region of ten bases with one edit: edit_cost<.., K = 1> runs
+// region_cost<REG_R, 10, 10, 0, 0, 1> / region_cost<REG_L, 10, 0, 0, 0, 1> (in place, one insertion, one deletion) and a key hit
+// passes at cost <= 1.  The suspects carry the tests' numbers among the 14 (0 and 13) for pm_pair_edit_resolve<1>.  The frame
+// has field B in place, so a match ends within one base of the window's last one: inside position - 1 .. position + 3, the
+// ends pm_edits_verify reads.
+__global__ __launch_bounds__(PAIR_THREADS) void pm_pair_edit_scan_k1(PairArgs a) {
+  extern __shared__ uint32_t lds[];
+  int table, cj;
+  if (!pair_block_item(a, &table, &cj)) return;
+  {
+    const u32x4 *src = reinterpret_cast<const u32x4 *>(a.image + (size_t)table * PAIR_BITMAP_WORDS);
+    u32x4 *dst = reinterpret_cast<u32x4 *>(lds);
+    for (int i = threadIdx.x; i < PAIR_BITMAP_WORDS / 4; i += PAIR_THREADS) dst[i] = src[i];
+  }
+  __syncthreads();
+  if (table == 0) pair_scan_body<0, 1, 0, 3, 1>(a, 0, cj, 0);       // wave-uniform
+  else pair_scan_body<2, 3, 0, 3, 1>(a, 1, cj, 13);
+}
+
 // Second kernel of the edit plan: a suspect = {window bits, position | test << 40}.  Every pattern that has the key of the
 // test goes through edit_cost again (here every lane is busy and a key's run of patterns is one contiguous list); what
 // passes leaves as a seed record (pattern index, position) for the automaton (pm_edits_verify), whose last five steps read
@@ -743,6 +775,11 @@ __global__ __launch_bounds__(PAIR_THREADS) void pm_pair_edit_scan(PairArgs a) {
 // staged in LDS and join the list in batches (one atomic per few thousand: the list's end is one counter for the grid).
 constexpr int ESTAGE = 2048;                                        // 8-byte records a workgroup stages (16 KiB)
 constexpr int EWORK = 3072;                                         // (suspect, pattern of its key's run) items a workgroup queues per trip
+// K: the plan's edit budget -- the tests a suspect can name, their tables, edit_cost's budget and the cost that passes.
+// K = 2 is the kernel of -k 2; K = 1 (-k 1) applies its scan's budget (edit_cost<.., K = 1>, cost <= 1) as an instance of its
+// own, not from a.k: with the budget a run-time value the kernel would keep the two-edit shift sets alive for every item, and
+// its seed records (what pm_edits_verify pays an automaton run for) would be those of the loose two-edit test.
+template <int K>
 __global__ __launch_bounds__(256) void pm_pair_edit_resolve(PairArgs a) {
   __shared__ uint64_t s_rec[ESTAGE];
   __shared__ uint4 s_susp[256];                                     // this trip's suspects: {window lo, window hi, position lo, position hi | test << 8}
@@ -786,11 +823,13 @@ __global__ __launch_bounds__(256) void pm_pair_edit_resolve(PairArgs a) {
     bool ok = false;
     uint64_t rec = 0;
     if (live) {
-      const int table = edit_variant_table(var);
+      int table;
+      if constexpr (K == 1) table = edit_variant_table_k1(var); else table = edit_variant_table(var);
       const uint32_t o = a.olist[(size_t)table * a.np + t];
       int c = 9;
-      edit_variant(var, [&](auto A_, auto B_, auto D_) __attribute__((always_inline)) { c = edit_cost<decltype(A_)::value, decltype(B_)::value, decltype(D_)::value>(o, wlo, whi); });
-      ok = c <= 2;
+      auto cost = [&](auto A_, auto B_, auto D_) __attribute__((always_inline)) { c = edit_cost<decltype(A_)::value, decltype(B_)::value, decltype(D_)::value, false, K>(o, wlo, whi); };
+      if constexpr (K == 1) edit_variant_k1(var, cost); else edit_variant(var, cost);
+      ok = c <= K;
       if (ok) rec = ((uint64_t)a.order[(size_t)table * a.np + t] << 40) | pos40;
     }
     emit(ok, rec);
@@ -803,8 +842,10 @@ __global__ __launch_bounds__(256) void pm_pair_edit_resolve(PairArgs a) {
     if (r.w != 0xffffffffu) {                                       // (all ones: a slot its wave reserved and did not need; a real record's test number is < 14)
       const int var = (int)((r.w >> 8) & 15u);
       uint32_t key = 0;
-      edit_variant(var, [&](auto A_, auto B_, auto D_) __attribute__((always_inline)) { key = edit_key<decltype(A_)::value, decltype(B_)::value, decltype(D_)::value>(r.x, r.y); });
-      const int table = edit_variant_table(var);
+      auto key_of = [&](auto A_, auto B_, auto D_) __attribute__((always_inline)) { key = edit_key<decltype(A_)::value, decltype(B_)::value, decltype(D_)::value>(r.x, r.y); };
+      if constexpr (K == 1) edit_variant_k1(var, key_of); else edit_variant(var, key_of);
+      int table;
+      if constexpr (K == 1) table = edit_variant_table_k1(var); else table = edit_variant_table(var);
       const uint32_t row = key & 0x7fffu, bit = key >> 15;
       const uint32_t wd = a.image[(size_t)table * PAIR_BITMAP_WORDS + row];
       if ((wd >> bit) & 1u) {
@@ -1054,10 +1095,11 @@ hipError_t pair_launch(const PairDevice &d, const uint8_t *d_text, const uint32_
                        uint64_t *seed_out, unsigned long long *seed_count, uint64_t seed_cap) {
   if (!d_packed) return hipErrorInvalidValue;
   if (end > n) end = n;
-  if (floor_mode && (d.k != 2 || d.ncombos != 6)) return hipErrorInvalidValue;
+  const bool one_edit = floor_mode == 3 && d.k == 1 && d.ncombos == 2;   // -k 1: pm_pair_edit_scan_k1, two tests on the tile's two tables
+  if (floor_mode && !one_edit && (d.k != 2 || d.ncombos != 6)) return hipErrorInvalidValue;
   if (floor_mode == 3 && (!seed_out || !seed_count)) return hipErrorInvalidValue;
   ScanGeometry g = pair_geometry(d, begin, end);
-  if (floor_mode) {
+  if (floor_mode && !one_edit) {
     g.blocks = g.nseg * 14;
     // the edit plan keeps the superchunk map: its 14 tests share 6 tables in runs of 1 - 5 tests, so an XCD mostly holds one
     // table already, and the XCD superchunk map's pieces of tests of unequal cost took 4 % longer
@@ -1085,6 +1127,14 @@ hipError_t pair_launch(const PairDevice &d, const uint8_t *d_text, const uint32_
   a.susp = reinterpret_cast<uint4 *>(d_susp); a.susp_count = d_susp_count; a.susp_cap = susp_cap;   // *d_susp_count zeroed by the caller (stream order)
   a.stats = d_stats;
   a.seed_out = seed_out; a.seed_count = seed_count; a.seed_cap = seed_cap;
+  if (one_edit) {                                                   // a test per table: the grid and its map are pm_pair_scan's for -K 1
+    hipError_t fe;
+    if ((fe = hipFuncSetAttribute(reinterpret_cast<const void *>(pm_pair_edit_scan_k1), hipFuncAttributeMaxDynamicSharedMemorySize, PAIR_LDS_BYTES)) != hipSuccess) return fe;
+    hipLaunchKernelGGL(pm_pair_edit_scan_k1, dim3(g.blocks), dim3(PAIR_THREADS), PAIR_LDS_BYTES, st, a);
+    if ((fe = hipGetLastError()) != hipSuccess) return fe;
+    hipLaunchKernelGGL(pm_pair_edit_resolve<1>, dim3(16384), dim3(256), 0, st, a);
+    return hipGetLastError();
+  }
   if (floor_mode) {                                                 // measurement: 14 (pair, displacement) variants, no verify kernel
     a.ncombos = 14;
     hipError_t fe;
@@ -1098,7 +1148,7 @@ hipError_t pair_launch(const PairDevice &d, const uint8_t *d_text, const uint32_
       if ((fe = hipFuncSetAttribute(reinterpret_cast<const void *>(pm_pair_edit_scan<3>), hipFuncAttributeMaxDynamicSharedMemorySize, PAIR_LDS_BYTES)) != hipSuccess) return fe;
       hipLaunchKernelGGL(pm_pair_edit_scan<3>, dim3(g.blocks), dim3(PAIR_THREADS), PAIR_LDS_BYTES, st, a);
       if ((fe = hipGetLastError()) != hipSuccess) return fe;
-      hipLaunchKernelGGL(pm_pair_edit_resolve, dim3(16384), dim3(256), 0, st, a);
+      hipLaunchKernelGGL(pm_pair_edit_resolve<2>, dim3(16384), dim3(256), 0, st, a);
     }
     return hipGetLastError();
   }

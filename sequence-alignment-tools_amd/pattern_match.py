@@ -225,18 +225,22 @@ class PatternMatch:
     the device by align_hits_device, count_scan and pcr_pair, not by host threads.
     wildcard primers: wild_class=True (bit 5) lets -w primers of 16..32 characters with more than 16 concrete variants run on
     pm_wild_sub_scan (k = 0 on keyword_tree / shift_and, -K 1 / -K 2 on filter_bitvec) and not on the bit-parallel residue.
+    edit_pair=True (bit 6) lets the edit plan's first stage run on the pair geometry (pm_pair_edit_scan + pm_pair_edit_resolve)
+    wherever its tables can be built, not only at -k 2 on one pattern tile: every tile of a larger list at -k 2, -k 1 under
+    filter_bitvec / bare shift_and_inexact (two tests per window) and exact_bases -k 1 / -k 2.  The hits do not change.
     """
 
     def __init__(self, k=0, indels=True, eos="\n", semantics=SEM_AUTO, kernel=KERNEL_AUTO, device=0,
                  wildcards=False, text_n=False, long_patterns=False, long_exact=False, long_edits=False,
-                 long_halves=False, long_align=False, wild_class=False):
+                 long_halves=False, long_align=False, wild_class=False, edit_pair=False):
         self._L = load_library()
         cfg = _Config()
         cfg.abi_version, cfg.semantics, cfg.kernel, cfg.k = 1, semantics, kernel, k
         cfg.indels, cfg.wildcards, cfg.text_n = int(bool(indels)), int(bool(wildcards)), int(bool(text_n))
         cfg.eos = ord(eos) if isinstance(eos, str) else int(eos)
         cfg.device = device
-        cfg.long_patterns = int(bool(long_patterns)) | (2 if long_exact else 0) | (4 if long_edits else 0) | (8 if long_halves else 0) | (16 if long_align else 0) | (32 if wild_class else 0)
+        cfg.long_patterns = int(bool(long_patterns)) | (2 if long_exact else 0) | (4 if long_edits else 0) | (8 if long_halves else 0) | (16 if long_align else 0) | (32 if wild_class else 0) | (64 if edit_pair else 0)
+        self.long_patterns_bits = int(cfg.long_patterns)           # pm_config.long_patterns as handed to pm_create
         self._h = C.c_void_p()
         rc = self._L.pm_create(C.byref(cfg), C.byref(self._h))
         if rc:
@@ -615,9 +619,9 @@ class PatternMatch:
     def scan_stats(self):
         """pm_scan_stats: counters of the last scan (see include/pm_gpu.h).  Waits for a look-ahead scan that scan() / scan_view()
         left in flight: polled between ranges it takes away the overlap of that scan with the caller's work."""
-        v = (C.c_uint64 * 8)()
-        self._check(self._L.pm_scan_stats(self._h, v, 8))
-        names = ("candidates", "between_stages", "internal_rescans", "blocks", "rounds", "key_hits", "range_splits", "lookahead")
+        v = (C.c_uint64 * 9)()
+        self._check(self._L.pm_scan_stats(self._h, v, 9))
+        names = ("candidates", "between_stages", "internal_rescans", "blocks", "rounds", "key_hits", "range_splits", "lookahead", "edit_suspects")
         return {k: int(v[i]) for i, k in enumerate(names)}
 
     def residency(self):
