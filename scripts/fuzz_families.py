@@ -8,9 +8,13 @@ host cluster / halves rules or the stream-edge records is invisible to this form
 
 --oracle: the library (its own choice of kernel family) against oracle/pm_oracle.c, the CPU restatement pinned to the real
 reference, on the small cases of tests/adversarial.py (300 .. 8000 characters: what the oracle finishes in well under a
-second) -- the open-ended form of tests/test_gpu_adversarial.py, which keeps 600 fixed seeds in the suite.
+second) -- the open-ended form of tests/test_gpu_adversarial.py, which keeps 600 fixed seeds in the suite.  With --classes
+the cases are those of tests/adversarial_classes.py (lists that fill the main class, wide tiles, the 16..19 character
+classes, the degenerate -w class and the residue at once, the permission bits of pm_config.long_patterns set): the
+open-ended form of tests/test_gpu_adversarial_classes.py, whose 400 fixed seeds are the first this form draws (first_seed
+900 unless given).  It ends at the first difference and at the first error and tries nothing twice.
 
-    python scripts/fuzz_families.py [seconds] [first_seed] [--oracle [--dense-bound RECORDS | --edge-cuts]]
+    python scripts/fuzz_families.py [seconds] [first_seed] [--oracle [--classes] [--dense-bound RECORDS | --edge-cuts]]
 
 Prints one line per case and a summary; exit status 1 on the first difference."""
 import os
@@ -25,6 +29,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import sat_amd  # noqa: E402
 import adversarial as A  # noqa: E402
+import adversarial_classes as AC  # noqa: E402
 from adversarial import make_stream, make_patterns  # noqa: E402
 
 TABLE = b"ACGT\n"
@@ -83,8 +88,10 @@ def main_oracle(budget, seed):
     t_end = time.time() + budget
     cases = bad = skipped = 0
     fam = {sat_amd.KERNEL_SEED: 0, sat_amd.KERNEL_BITPAR: 0}
+    routes = {}
     while time.time() < t_end:
-        c = A.small_case(seed)
+        c = AC.class_case(seed) if CLASSES else A.small_case(seed)
+        route = c.get("route")
         want = A.oracle_hits(c)
         note = ""
         try:
@@ -95,7 +102,7 @@ def main_oracle(budget, seed):
                     os.environ["PM_DENSE_BOUND"] = str(bound)
                     try:
                         st = {}
-                        got = A.gpu_hits(c, kernel=sat_amd.KERNEL_AUTO, mode=0, stats=st) if c["mode"] % 2 == 0 else A.gpu_hits(c, kernel=sat_amd.KERNEL_AUTO, mode=1)
+                        got = A.gpu_hits(c, kernel=sat_amd.KERNEL_AUTO, mode=0, stats=st, route=route) if c["mode"] % 2 == 0 else A.gpu_hits(c, kernel=sat_amd.KERNEL_AUTO, mode=1, route=route)
                         CUT[0] += st.get("range_splits", 0) > 0
                         break
                     except sat_amd.PmError as e2:                      # more records in 256 positions than the bound: not what is tested here
@@ -107,9 +114,9 @@ def main_oracle(budget, seed):
                 n = c["n"]
                 r = np.random.default_rng(seed)
                 cuts = list(np.cumsum(r.integers(1, 12, size=8))) + [n - int(x) for x in np.cumsum(r.integers(1, 12, size=8))] + [int(x) for x in r.integers(0, n + 1, size=3)]
-                got = A.gpu_hits(c, kernel=sat_amd.KERNEL_AUTO, cuts=cuts)
+                got = A.gpu_hits(c, kernel=sat_amd.KERNEL_AUTO, cuts=cuts, route=route)
             else:
-                got = A.gpu_hits(c, kernel=sat_amd.KERNEL_AUTO)
+                got = A.gpu_hits(c, kernel=sat_amd.KERNEL_AUTO, route=route)
         except sat_amd.PmError as err:
             if want is None and err.code in (-6, -2):
                 skipped += 1
@@ -118,11 +125,14 @@ def main_oracle(budget, seed):
             if err.code != -2 or c["mode"] < 2:
                 raise
             note = " (mode %d not available: %s; resumable scan instead)" % (c["mode"], str(err)[:60])
-            got = A.gpu_hits(c, kernel=sat_amd.KERNEL_AUTO, mode=1)
+            got = A.gpu_hits(c, kernel=sat_amd.KERNEL_AUTO, mode=1, route=route)
         cases += 1
         fam[c["selected"][1]] += 1
+        if CLASSES:
+            for name in ROUTE_PHRASES:
+                routes[name] = routes.get(name, 0) + (ROUTE_PHRASES[name] in c["kernel_desc"])
         same = want is not None and got == want
-        print("%s: %d hits %s%s  %s" % (A.describe(c), len(got), "ok" if same else "DIFFERENT (oracle %s)" % (None if want is None else len(want)), note, c["kernel_desc"][:50]), flush=True)
+        print("%s: %d hits %s%s  %s" % ((AC.describe if CLASSES else A.describe)(c), len(got), "ok" if same else "DIFFERENT (oracle %s)" % (None if want is None else len(want)), note, c["kernel_desc"][:50]), flush=True)
         if not same:
             bad += 1
             sg, sw = set(got), set(want or [])
@@ -131,6 +141,8 @@ def main_oracle(budget, seed):
         seed += 1
     print("oracle form: cases %d (seed family %d, bit-parallel family %d), rejected by reference and library alike %d, failures %d, next seed %d" % (
         cases, fam[sat_amd.KERNEL_SEED], fam[sat_amd.KERNEL_BITPAR], skipped, bad, seed))
+    if CLASSES:
+        print("class cases that named a route: %s" % ", ".join("%s %d" % kv for kv in sorted(routes.items())))
     if DENSE_BOUND:
         print("with PM_DENSE_BOUND=%d: three-range cases that were scanned in pieces: %d" % (DENSE_BOUND, CUT[0]))
     sys.exit(1 if bad else 0)
@@ -138,19 +150,25 @@ def main_oracle(budget, seed):
 
 DENSE_BOUND = 0
 EDGE_CUTS = False
+CLASSES = False
+# describe() phrases of the opt-in routes (csrc/pm_api.cpp pm_describe)
+ROUTE_PHRASES = {"pair_wide": "pm_pair_verify_wide", "exact_wide": "(wide rows, wide tiles=", "edits_wide": "pm_edits_verify_wide", "halves_wide": "pm_half_verify_wide",
+                 "wild": "pm_wild_sub_scan", "short_edit": "pm_short_edit_scan", "short_sub": "pm_short_sub_scan", "edit_pair": "pm_pair_edit_scan",
+                 "residue": "the seed plan does not take"}
 CUT = [0]
 
 
 def main():
-    global DENSE_BOUND, EDGE_CUTS
+    global DENSE_BOUND, EDGE_CUTS, CLASSES
     EDGE_CUTS = "--edge-cuts" in sys.argv[1:]
-    argv = [a for a in sys.argv[1:] if a not in ("--oracle", "--edge-cuts")]
+    CLASSES = "--classes" in sys.argv[1:]
+    argv = [a for a in sys.argv[1:] if a not in ("--oracle", "--edge-cuts", "--classes")]
     if "--dense-bound" in argv:
         i = argv.index("--dense-bound")
         DENSE_BOUND = int(argv[i + 1])
         del argv[i:i + 2]
     budget = float(argv[0]) if len(argv) > 0 else 300.0
-    seed = int(argv[1]) if len(argv) > 1 else 1000
+    seed = int(argv[1]) if len(argv) > 1 else (900 if CLASSES else 1000)
     if "--oracle" in sys.argv[1:]:
         return main_oracle(budget, seed)
     t_end = time.time() + budget

@@ -165,15 +165,16 @@ class knobs:
                 os.environ[name] = self.old[name]
 
 
-def gpu_hits(c, kernel=sat_amd.KERNEL_SEED, mode=None, guard=256, stats=None, cuts=None):
+def gpu_hits(c, kernel=sat_amd.KERNEL_SEED, mode=None, guard=256, stats=None, cuts=None, route=None):
     """the case through the library; sorted (end, pid, k) tuples.  mode 0: find_all over the whole stream; 1: find_all in
     small consecutive ranges (resumable pm_scan); 2: one scan + the device finalize (bench.py's single-rank step); 3: two
     position shards, each finalized on its own with a guard band (bench.py's multi-rank step).  Raises PmError(-2) where
-    the library says the mode does not apply to the option set."""
+    the library says the mode does not apply to the option set.  route: further keyword arguments of PatternMatch (the permission
+    bits of pm_config.long_patterns, tests/adversarial_classes.py); None: the handle as it is by default."""
     import torch
     mode = c["mode"] if mode is None else mode
     with knobs(c["env"]):
-        pm = sat_amd.PatternMatch(k=c["k"], indels=c["indels"], kernel=kernel, semantics=c["sem"], wildcards=c["wild"])
+        pm = sat_amd.PatternMatch(k=c["k"], indels=c["indels"], kernel=kernel, semantics=c["sem"], wildcards=c["wild"], **(route or {}))
     try:
         for i, p in enumerate(c["patterns"]):
             z = c["zones"][i] if c["zones"] else (0, 0)

@@ -26,11 +26,12 @@ def hit_array(tuples):
     return h
 
 
-def make_handle(c, init="auto", patterns=None):
-    """the case's handle; init: auto (pm_init for c['host'], else pm_init_device), host, device, packed"""
+def make_handle(c, init="auto", patterns=None, route=None):
+    """the case's handle; init: auto (pm_init for c['host'], else pm_init_device), host, device, packed; route: further
+    keyword arguments of PatternMatch (the permission bits of pm_config.long_patterns), None: the default handle"""
     import torch
     with A.knobs(c["env"]):
-        pm = sat_amd.PatternMatch(k=c["k"], indels=c["indels"], semantics=c["sem"], wildcards=c["wild"])
+        pm = sat_amd.PatternMatch(k=c["k"], indels=c["indels"], semantics=c["sem"], wildcards=c["wild"], **(route or {}))
     for i, p in enumerate(patterns or c["patterns"]):
         z = c["zones"][i] if c["zones"] else (0, 0)
         pm.add_pattern(p, i + 1, z[0], z[1])
