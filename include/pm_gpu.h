@@ -86,6 +86,7 @@ typedef enum {
 #define PM_LONG_ALIGN 16   /* -k 1 .. -k 3 (edits): hits of patterns of 33..64 characters are re-aligned on the device */
 #define PM_WILD_CLASS 32   /* -w, k = 0 / -K 1 / -K 2: patterns of 16..32 characters with more than 16 concrete variants may run on pm_wild_sub_scan */
 #define PM_EDIT_PAIR  64   /* -k 1 / -k 2: the edit plan's first stage may run on the pair geometry beyond -k 2 on one tile (every tile, -k 1, exact_bases) */
+#define PM_WILD_LONG  128  /* with PM_WILD_CLASS: patterns of 33..64 characters with more than 16 concrete variants may join that class (a wide class verify) */
 
 /* Replaces the constructor arguments of the reference engines as pick_pattern_index passes them
  * (select.cc:19-30): nmismatch, indels, wildcard, textn, eos.  dna_mut is not supported. */
@@ -99,7 +100,7 @@ typedef struct {
   int32_t text_n;          /* -W: a text N also matches (shift_and.cc:112) */
   int32_t eos;             /* raw end-of-sequence char, '\n' in the CLIs */
   int32_t device;          /* HIP device ordinal */
-  int32_t long_patterns;   /* a bit set (PM_LONG_SUB | PM_LONG_EXACT | PM_LONG_EDITS | PM_LONG_HALVES | PM_LONG_ALIGN | PM_WILD_CLASS | PM_EDIT_PAIR; 0 = the routing of
+  int32_t long_patterns;   /* a bit set (PM_LONG_SUB | PM_LONG_EXACT | PM_LONG_EDITS | PM_LONG_HALVES | PM_LONG_ALIGN | PM_WILD_CLASS | PM_EDIT_PAIR | PM_WILD_LONG; 0 = the routing of
                               earlier versions).
                               PM_LONG_SUB (1) = with PM_KERNEL_AUTO, -K 1 / -K 2 (substitutions only) and filter_bitvec, bare
                               shift_and_inexact or exact_halves on an A,C,G,T-normalized or raw ASCII stream, patterns
@@ -145,7 +146,13 @@ typedef struct {
                               characters).  The hits are the same either way.  -k 2 on one tile without exact_bases runs
                               there with or without the bit; PM_EDIT_SCAN=hash / bloom and PM_EDIT_PAIR=off in the
                               environment pm_create reads keep the routing without the bit.  Not set = the routing of
-                              earlier versions.  (The field took
+                              earlier versions.
+                              PM_WILD_LONG (128) acts only together with PM_WILD_CLASS: under that bit's conditions a
+                              pattern of 33..64 characters with more than 16 concrete variants joins the class under the
+                              same per-pattern rules (its keys are its last 16 characters').  A class that holds such a
+                              pattern is verified by pm_wild_sub_verify_wide on rows of 64 characters;
+                              the scan is the same.  It needs none of PM_LONG_SUB .. PM_LONG_ALIGN.  Alone, or with
+                              PM_WILD_LONG=off in the environment pm_create reads, it changes nothing.  (The field took
                               the place of reserved[0]: same layout, same PM_ABI_VERSION.) */
   int32_t reserved[6];
 } pm_config;

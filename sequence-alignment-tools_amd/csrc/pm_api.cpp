@@ -205,11 +205,12 @@ struct pm_handle {
   std::vector<uint8_t> in_ssub;       // per pattern: 1 = scanned by pm_short_sub_scan
   size_t nssub = 0;
   ShortSubDevice ssd;
-  // -w, k = 0 / -K 1 / -K 2: primers of 16..32 characters with more than 16 concrete variants, a class of their own on
+  // -w, k = 0 / -K 1 / -K 2: primers of 16..32 (with PM_WILD_LONG: 16..64) characters with more than 16 concrete variants, a class of their own on
   // pm_wild_sub_scan (PM_WILD_CLASS bit of pm_config.long_patterns) beside the main class -- Bloom or pair
   // plan -- or without one.  Its records are the main class's; the host's edge records cover it (in_main_class).
   std::vector<uint8_t> in_wild;       // per inner pattern: 1 = scanned by pm_wild_sub_scan
   size_t nwild = 0;
+  size_t nwild_long = 0;              // of them: primers of 33..64 characters (PM_WILD_LONG): the class's verify is pm_wild_sub_verify_wide
   bool wild_only = false;             // no main class: the wild class (and a residue, if any) is the handle's whole device stage
   WildDevice wd;
   bool halves_fresh = true;           // no host-side exact_halves state (lasthit, carried seeds) since init / pm_reset
@@ -456,6 +457,7 @@ static void read_knobs(Knobs *k) {
   k->long_edits_off = is("PM_LONG_EDITS", "off");
   k->long_halves_off = is("PM_LONG_HALVES", "off");
   k->wild_off = is("PM_WILD_CLASS", "off");
+  k->wild_long_off = is("PM_WILD_LONG", "off");
   k->edit_pair_off = is("PM_EDIT_PAIR", "off");
   k->debug = getenv("PM_DEBUG") != nullptr;
 }
@@ -833,22 +835,26 @@ static void short_sub_route(pm_handle *h, size_t maxL) {
 // wild_takes holds (16..32 characters, a base at every character, <= 256 keys per field pair), no pattern_n_quirk primer
 // under filter_bitvec.  The class: wild_class_fits (run entries per field pair); a class beyond it leaves every primer where
 // it was.  Anything else, PM_WILD_CLASS=off included, leaves every handle as it was built before the class existed.
+// With the PM_WILD_LONG bit as well a primer of 33..64 characters joins under the same rules -- its keys are
+// those of its last 16 characters -- whatever the main class's longest primer is (maxL of classify_patterns): such a primer
+// is in the residue under either classification, for its length or for its variants.  PM_WILD_LONG=off keeps 32.
 // Called by classify_patterns with in_rest decided.
 static void wild_route(pm_handle *h) {
   if (!(h->cfg.long_patterns & PM_WILD_CLASS) || h->knobs.wild_off || h->kern != PM_KERNEL_AUTO || !h->wild_seed) return;
   if (h->sem == PM_SEM_FILTER_BITVEC ? (h->cfg.indels || (h->scan_k != 1 && h->scan_k != 2)) : h->scan_k != 0) return;
   if (!stream_for_pair_plan(h)) return;
+  const size_t maxWL = (h->cfg.long_patterns & PM_WILD_LONG) && !h->knobs.wild_long_off ? 64 : 32;
   std::vector<std::string> variants, cls;
   std::vector<size_t> who;
   for (size_t i = 0; i < h->inner.size(); ++i) {
     const Pattern &p = h->inner[i];
-    if (!h->in_rest[i] || !wild_takes(p.s, h->scan_k)) continue;
+    if (!h->in_rest[i] || !wild_takes(p.s, h->scan_k, maxWL)) continue;
     if (expand_iupac(p.s, 16, &variants)) continue;                 // (in the residue for another reason)
     if (h->sem == PM_SEM_FILTER_BITVEC && pattern_n_quirk(h, p)) continue;
     who.push_back(i); cls.push_back(p.s);
   }
   if (who.empty() || who.size() >= ((size_t)1 << 21) || !wild_class_fits(cls, h->scan_k)) return;
-  for (size_t i : who) { h->in_rest[i] = 0; --h->nrest; h->in_wild[i] = 1; ++h->nwild; }
+  for (size_t i : who) { h->in_rest[i] = 0; --h->nrest; h->in_wild[i] = 1; ++h->nwild; if (h->inner[i].s.size() > 32) ++h->nwild_long; }
 }
 
 // Which engine and class every pattern of the list goes to: in_rest (the bit-parallel residue beside the seed family),
@@ -867,7 +873,7 @@ static void classify_patterns(pm_handle *h, bool want_seed, size_t maxL) {
   h->in_short.assign(h->inner.size(), 0);
   h->nshort = 0; h->short_only = false;
   h->in_wild.assign(h->inner.size(), 0);
-  h->nwild = 0; h->wild_only = false;
+  h->nwild = 0; h->nwild_long = 0; h->wild_only = false;
   if (want_seed && (!h->cfg.wildcards || h->wild_seed) && h->kern == PM_KERNEL_AUTO &&
       (h->sem == PM_SEM_KEYWORD_TREE || h->sem == PM_SEM_SHIFT_AND || h->sem == PM_SEM_SHIFT_AND_INEXACT || h->sem == PM_SEM_FILTER_BITVEC)) {
     std::vector<std::string> variants;
@@ -1267,7 +1273,7 @@ static int init_common(pm_handle *h, const uint8_t *table, int32_t table_len) {
     std::fill(h->in_rest.begin(), h->in_rest.end(), 0); h->nrest = 0;
     std::fill(h->in_short.begin(), h->in_short.end(), 0); h->nshort = 0; h->short_only = false;
     std::fill(h->in_ssub.begin(), h->in_ssub.end(), 0); h->nssub = 0;
-    std::fill(h->in_wild.begin(), h->in_wild.end(), 0); h->nwild = 0; h->wild_only = false;
+    std::fill(h->in_wild.begin(), h->in_wild.end(), 0); h->nwild = 0; h->nwild_long = 0; h->wild_only = false;
     h->kern = PM_KERNEL_BITPAR;
     BitparTables tabs;
     std::string msg = bitpar_build(h->inner, h->inner_ids, h->alpha, h->scan_k, h->eos_code, &tabs,
@@ -1816,9 +1822,11 @@ static const char *pair_schedule_name(const ScanGeometry &g) {
 
 extern "C" int pm_describe(const pm_handle *h, char *buf, size_t buflen) {
   if (!h || !buf || !h->inited) return PM_E_INVALID;
+  char wild_long[96] = "";                                          // the wild class's primers of 33..64 characters; none: the text it always had
+  if (h->nwild_long) snprintf(wild_long, sizeof(wild_long), ", %zu of them of 33..64 characters: pm_wild_sub_verify_wide", h->nwild_long);
   if (h->kern == PM_KERNEL_SEED && h->wild_only) {
-    snprintf(buf, buflen, "kernel=pm_wild_sub_scan+pm_wild_sub_verify for %zu patterns with more than 16 concrete variants (entries=%zu, pairs=%d) fields=2-of-4 x 4 bases window=16 chunk=%lld nchunks=%d grid=%d block=%d",
-             h->nwild, h->wd.max_entries, h->wd.ncombos, (long long)h->geo.seg_len, h->geo.nseg, h->geo.blocks, h->geo.threads);
+    snprintf(buf, buflen, "kernel=pm_wild_sub_scan+pm_wild_sub_verify for %zu patterns with more than 16 concrete variants (entries=%zu, pairs=%d%s) fields=2-of-4 x 4 bases window=16 chunk=%lld nchunks=%d grid=%d block=%d",
+             h->nwild, h->wd.max_entries, h->wd.ncombos, wild_long, (long long)h->geo.seg_len, h->geo.nseg, h->geo.blocks, h->geo.threads);
     if (h->nrest) {
       const size_t at = strlen(buf);
       if (at < buflen) snprintf(buf + at, buflen - at, " + %s for %zu patterns the seed plan does not take", bitpar_kernel_name(h->scan_k, h->scan_indels), h->nrest);
@@ -1895,7 +1903,7 @@ extern "C" int pm_describe(const pm_handle *h, char *buf, size_t buflen) {
   }
   if (h->kern == PM_KERNEL_SEED && h->nwild && !h->wild_only) {
     const size_t at = strlen(buf);
-    if (at < buflen) snprintf(buf + at, buflen - at, " + pm_wild_sub_scan for %zu patterns with more than 16 concrete variants (entries=%zu, pairs=%d)", h->nwild, h->wd.max_entries, h->wd.ncombos);
+    if (at < buflen) snprintf(buf + at, buflen - at, " + pm_wild_sub_scan for %zu patterns with more than 16 concrete variants (entries=%zu, pairs=%d%s)", h->nwild, h->wd.max_entries, h->wd.ncombos, wild_long);
   }
   if (h->kern == PM_KERNEL_SEED) return PM_OK;
   else
@@ -2153,7 +2161,7 @@ static int edits_start_candidates(pm_handle *h, std::vector<pm_hit> *out) {
 // L + k + 8 characters -- its last bit depends on the last L + k only -- (from the stream-start state when that
 // is the whole stream); duplicates of the kernel's records leave with the dedup.  Computed once per stream.
 // Found by scripts/fuzz_families.py (seed 1308).
-static int edge_reach(const pm_handle *h) { return h->nlong || h->nlong_exact || h->nlong_edits || h->nlong_halves ? 64 : 32; }
+static int edge_reach(const pm_handle *h) { return h->nlong || h->nlong_exact || h->nlong_edits || h->nlong_halves || h->nwild_long ? 64 : 32; }   // (the wild class's primers are main-class primers to the host's edge records)
 static int edits_end_candidates(pm_handle *h, std::vector<pm_hit> *out) {
   const int k = h->cfg.k;
   const int64_t n = h->n;

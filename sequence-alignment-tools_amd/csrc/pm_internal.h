@@ -29,7 +29,7 @@ struct Alphabet {
 };
 
 // Test and measurement knobs (PM_SEED_CHUNK, PM_SEED_GROUP, PM_SEED_DEBUG, PM_SEED_TILE, PM_PAIR, PM_PAIR_ROW, PM_PAIR_MAP, PM_HALF_SCAN,
-// PM_EDIT_SCAN, PM_EDIT_PAIR, PM_EDIT_TABLE_LOG, PM_SHORT_SCAN, PM_SHORT_TILE, PM_SHORT_SUB, PM_LONG_SUB, PM_LONG_EXACT, PM_LONG_EDITS, PM_LONG_HALVES, PM_WILD_CLASS, PM_BITPAR_TP, PM_BITPAR_SEGLEN, PM_DEBUG).  The environment is read ONCE, by
+// PM_EDIT_SCAN, PM_EDIT_PAIR, PM_EDIT_TABLE_LOG, PM_SHORT_SCAN, PM_SHORT_TILE, PM_SHORT_SUB, PM_LONG_SUB, PM_LONG_EXACT, PM_LONG_EDITS, PM_LONG_HALVES, PM_WILD_CLASS, PM_WILD_LONG, PM_BITPAR_TP, PM_BITPAR_SEGLEN, PM_DEBUG).  The environment is read ONCE, by
 // pm_create (pm_api.cpp read_knobs), into the handle: nothing on the init or launch path calls getenv, and a
 // handle's behaviour does not change when its caller's environment does.  Every field's 0 / -1 / false = unset.
 struct Knobs {
@@ -55,6 +55,7 @@ struct Knobs {
   bool long_exact_off = false;       // PM_LONG_EXACT=off: k = 0 patterns of 33..64 characters stay off the seed plan whatever pm_config.long_patterns says (A/B runs, tests)
   bool long_edits_off = false;       // PM_LONG_EDITS=off: -k patterns of 33..64 characters stay off the edit plan whatever pm_config.long_patterns says (A/B runs, tests)
   bool long_halves_off = false;      // PM_LONG_HALVES=off: exact_halves -k lists with patterns of 33..64 characters stay off the halves plan whatever pm_config.long_patterns says (A/B runs, tests)
+  bool wild_long_off = false;        // PM_WILD_LONG=off: -w primers of 33..64 characters with more than 16 concrete variants stay on the bit-parallel residue whatever pm_config.long_patterns says (A/B runs, tests)
   bool wild_off = false;             // PM_WILD_CLASS=off: -w primers with more than 16 concrete variants stay on the bit-parallel residue whatever pm_config.long_patterns says (A/B runs, tests)
   bool debug = false;                // PM_DEBUG: stage timings on stderr
 };
@@ -325,19 +326,22 @@ hipError_t short_sub_launch(const ShortSubDevice &d, const uint8_t *d_text, cons
                             pm_hit *d_out, unsigned long long *d_counter, uint64_t cap, uint64_t *d_susp, unsigned long long *d_susp_count,
                             uint64_t susp_cap, hipStream_t st);
 
-// ---- the wild class: -w primers of 16..32 characters with more than 16 concrete variants (pm_short.hip) ----
+// ---- the wild class: -w primers of 16..32 (16..64: DESIGN.md 4.14) characters with more than 16 concrete variants (pm_short.hip) ----
 // A class beside (or without) the seed family's main class at k = 0 (keyword_tree, shift_and) and -K 1 / -K 2 (filter_bitvec):
 // pm_wild_sub_scan -- pm_short_sub_scan's scan with keys expanded per field pair and 8-byte run entries {primer, class word}
 // (pm_wild_tables.h) -- + pm_wild_sub_verify, which runs pm_verify.h's wild_verify<4>: records of the main class's meaning.
+// A class that holds a primer of 33..64 characters is WIDE as a whole: rows of pat_class are 32 bytes, rows of pat_zone two
+// dwords, and pm_wild_sub_verify_wide (wild_verify<4, 64>) reads them; the key index and the scan are the same.
 struct WildTables {                // host-built, then uploaded
   int k = 0, maxlen = 0, eos_code = -1, ncombos = 0;
-  bool ascii = false;
+  bool ascii = false, wide = false;
   int fa[SUB_MAX_COMBOS] = {}, fb[SUB_MAX_COMBOS] = {};
   std::vector<uint8_t> pat_len;    // per primer of the class
   std::vector<uint32_t> pat_id;
-  std::vector<uint8_t> pat_class;  // 16 bytes per primer: a class nibble per character
+  std::vector<uint8_t> pat_class;  // 16 bytes per primer (wide: 32): a class nibble per character
   std::vector<uint8_t> pat_reg;    // the field pair the primer is entered under at k = 0
-  std::vector<uint32_t> pat_zone;  // bit i: character i lies in an exact zone
+  std::vector<uint32_t> pat_zone;  // bit i: character i lies in an exact zone (wide: two dwords per primer, low dword first)
+  size_t nlong = 0;                // primers of 33..64 characters
   std::vector<uint32_t> bitmap, rows;
   std::vector<uint64_t> runs;      // class index of the primer | class word << 32, by field pair and key
   size_t max_entries = 0;          // run entries of the fullest field pair
@@ -345,19 +349,19 @@ struct WildTables {                // host-built, then uploaded
 
 struct WildDevice {
   int k = 0, maxlen = 0, eos_code = -1, ncombos = 0;
-  bool ascii = false;
+  bool ascii = false, wide = false;
   int fa[SUB_MAX_COMBOS] = {}, fb[SUB_MAX_COMBOS] = {};
-  size_t npat = 0, max_entries = 0;
+  size_t npat = 0, max_entries = 0, nlong = 0;
   uint8_t *pat_len = nullptr, *pat_class = nullptr, *pat_reg = nullptr;
   uint32_t *pat_id = nullptr, *pat_zone = nullptr;
   std::vector<ShortTileDevice> tiles;            // one tile (the entry cap keeps the class small)
   int viol_level = 0;              // as PairDevice::viol_level (set by the caller after wild_upload)
 };
 
-// The routing's two questions (pm_wild_tables.h wild_primer_fits, wild_entries_fit): a primer the class can hold -- 16..32
-// characters, a base accepted at every character, at most 256 keys in every field pair of the plan -- and a class whose
-// run entries stay within SHORT_SUB_MAX_PATTERNS per field pair.
-bool wild_takes(const std::string &s, int k);
+// The routing's two questions (pm_wild_tables.h wild_primer_fits, wild_entries_fit): a primer the class can hold -- 16..maxL
+// characters (maxL: 32 or 64), a base accepted at every character, at most 256 keys in every field pair of the plan -- and a
+// class whose run entries stay within SHORT_SUB_MAX_PATTERNS per field pair.
+bool wild_takes(const std::string &s, int k, size_t maxL);
 bool wild_class_fits(const std::vector<std::string> &pats, int k);
 // Primers as added (with their letters); every one must pass wild_primer_fits (pm_wild_tables.h).  Returns "" or why the
 // class is refused as a whole.

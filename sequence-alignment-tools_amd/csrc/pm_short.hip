@@ -349,11 +349,13 @@ __global__ __launch_bounds__(256) void pm_short_sub_verify(SubArgs a) {
 //                        key hit here too: the window's other eight bases become one bit each in their nibble, AND + popcount.
 //                        k = 0 runs the k = 1 instance (two bitmaps), every primer entered under one of the two pairs.
 //   pm_wild_sub_verify   wild_verify<4> of pm_verify.h per suspect: pair_verify with the per-byte verdict by class.
+//   pm_wild_sub_verify_wide   the same loop over wild_verify<4, 64>, for a class that holds a primer of 33..64 characters
+//                        (DESIGN.md 4.14).  The scan, the suspects and their counter are the same.
 //
 // N, end-of-sequence and positions outside the stream pack to arbitrary bases, as above: such a window can only gain
 // suspects, and it cannot lose a candidate -- such a character is one of the <= k mismatches and leaves two clean fields.
 struct WildArgs : SubArgs {
-  const uint8_t *pat_class;             // 16 bytes per primer (pat_codes is unused)
+  const uint8_t *pat_class;             // 16 bytes per primer, 32 in a wide class (pat_codes is unused)
   const uint8_t *pat_reg;
   int ascii;
 };
@@ -388,6 +390,17 @@ __global__ __launch_bounds__(256) void pm_wild_sub_verify(WildArgs a) {
     const uint64_t r = a.list[i];
     return r != ~0ull &&                                              // (a slot its wave reserved and did not need)
            wild_verify<4>(a, (int)(r >> 61), (int64_t)(r & SHORT_POS_MASK), (uint32_t)(r >> 40) & ((1u << SUB_INDEX_BITS) - 1u), hh);
+  });
+}
+
+// a class that holds a primer of 33..64 characters: rows of 64 class nibbles, zone masks of two dwords
+__global__ __launch_bounds__(256) void pm_wild_sub_verify_wide(WildArgs a) {
+  unsigned long long n = *a.list_count;
+  if (n > a.list_cap) n = a.list_cap;
+  verify_staged(a, n, [&](unsigned long long i, const VerifyStage &, pm_hit *hh) __attribute__((always_inline)) {
+    const uint64_t r = a.list[i];
+    return r != ~0ull &&                                              // (a slot its wave reserved and did not need)
+           wild_verify<4, 64>(a, (int)(r >> 61), (int64_t)(r & SHORT_POS_MASK), (uint32_t)(r >> 40) & ((1u << SUB_INDEX_BITS) - 1u), hh);
   });
 }
 
@@ -610,7 +623,7 @@ hipError_t short_sub_launch(const ShortSubDevice &d, const uint8_t *d_text, cons
 // ---- the wild class: tables, launch --------------------------------------------------------------------------------
 
 static_assert(WILD_MAX_ENTRIES == SHORT_SUB_MAX_PATTERNS, "the wild class's entry cap is the short substitution class's measured ceiling (pm_wild_tables.h cannot see pm_internal.h)");
-bool wild_takes(const std::string &s, int k) { return wild_primer_fits(s, k); }
+bool wild_takes(const std::string &s, int k, size_t maxL) { return wild_primer_fits(s, k, maxL); }
 bool wild_class_fits(const std::vector<std::string> &pats, int k) { return wild_entries_fit(pats, k); }
 
 std::string wild_build(const std::vector<Pattern> &pats, const std::vector<uint32_t> &ids, const Alphabet &alpha, int k, int eos_code, WildTables *out) {
@@ -628,15 +641,19 @@ std::string wild_build(const std::vector<Pattern> &pats, const std::vector<uint3
   if (!why.empty()) return why;
   t.k = k; t.ascii = x.ascii; t.eos_code = eos_code >= 0 && eos_code < 256 ? eos_code : -1; t.ncombos = x.ncombos;
   for (int c = 0; c < x.ncombos; ++c) { t.fa[c] = x.fa[c]; t.fb[c] = x.fb[c]; }
-  t.pat_len.resize(np); t.pat_id.resize(np); t.pat_zone.assign(np, 0);
+  t.wide = x.row_bytes == 32;                                        // (a primer of 33..64 characters: every row of the class is wide)
+  const size_t zw = t.wide ? 2 : 1;
+  t.pat_len.resize(np); t.pat_id.resize(np); t.pat_zone.assign(np * zw, 0);
   for (size_t j = 0; j < np; ++j) {
     const int L = (int)strs[j].size();
     t.maxlen = std::max(t.maxlen, L);
+    if (L > 32) ++t.nlong;
     t.pat_len[j] = (uint8_t)L; t.pat_id[j] = ids[j];
     const int es = std::max(0, std::min(L, pats[j].esb)), ee = std::max(0, std::min(L, pats[j].eeb));
-    uint32_t z = 0;
-    for (int i = 0; i < L; ++i) if (i < es || i >= L - ee) z |= 1u << i;
-    t.pat_zone[j] = z;
+    uint64_t z = 0;
+    for (int i = 0; i < L; ++i) if (i < es || i >= L - ee) z |= 1ull << i;
+    t.pat_zone[j * zw] = (uint32_t)z;
+    if (t.wide) t.pat_zone[j * zw + 1] = (uint32_t)(z >> 32);
   }
   for (size_t e : x.entries) t.max_entries = std::max(t.max_entries, e);
   t.pat_class = std::move(x.pat_class); t.pat_reg = std::move(x.reg);
@@ -646,7 +663,7 @@ std::string wild_build(const std::vector<Pattern> &pats, const std::vector<uint3
 
 hipError_t wild_upload(const WildTables &t, WildDevice *d, hipStream_t st) {
   wild_free(d);
-  d->k = t.k; d->maxlen = t.maxlen; d->ascii = t.ascii; d->eos_code = t.eos_code; d->ncombos = t.ncombos; d->npat = t.pat_len.size();
+  d->k = t.k; d->maxlen = t.maxlen; d->ascii = t.ascii; d->wide = t.wide; d->nlong = t.nlong; d->eos_code = t.eos_code; d->ncombos = t.ncombos; d->npat = t.pat_len.size();
   d->max_entries = t.max_entries;
   for (int c = 0; c < SUB_MAX_COMBOS; ++c) { d->fa[c] = t.fa[c]; d->fb[c] = t.fb[c]; }
   Upload up = {st};
@@ -686,7 +703,8 @@ hipError_t wild_launch(const WildDevice &d, const uint8_t *d_text, const uint32_
   else hipLaunchKernelGGL(pm_wild_sub_scan<1>, dim3(nseg), dim3(SHORT_THREADS), 0, st, a);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(pm_wild_sub_verify, dim3(SUB_VERIFY_BLOCKS), dim3(256), 0, st, a);
+  if (d.wide) hipLaunchKernelGGL(pm_wild_sub_verify_wide, dim3(SUB_VERIFY_BLOCKS), dim3(256), 0, st, a);   // (the class's rows hold 64 characters)
+  else hipLaunchKernelGGL(pm_wild_sub_verify, dim3(SUB_VERIFY_BLOCKS), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 

@@ -227,51 +227,68 @@ PM_VFN bool wild_others_within(uint32_t others, uint32_t word, int k) { return w
 // are read one by one, zones and viol_level, "reported only through the first combo of the plan whose two fields are
 // clean", the clean-half flags, the record.  At k = 0 the combo must be the one the primer is entered under (pat_reg).
 // Args: text, n, k, eos_code, ascii, ncombos, fa, fb, pat_len, pat_id, pat_class, pat_reg, pat_zone, viol_level.
+//
+// CW = characters a row holds: 32, or 64 for a class that holds a primer of 33..64 characters -- rows of
+// pat_class are then 32 bytes, rows of pat_zone two dwords, low dword first, and the verdicts 64 bits (verify_mask<CW>, as
+// pair_verify<5, 64>).  One body for both: the row is judged in groups of 32 characters -- one uint4 of class nibbles and
+// two 16-byte stream reads per group, or, where the group's 32 bytes do not fit in front of n, the bytes below n one by one --
+// and everything behind the verdicts is written once on the mask type.  The stream is read inside [start, min(start + CW, n)).
 template <int FW = 4, int CW = 32, typename Args>
 PM_VFN bool wild_verify(const Args &a, int combo, int64_t p, uint32_t pi, pm_hit *hh) {
-  static_assert(FW == 4 && CW == 32, "fields of four bases, rows of 32 characters");
+  static_assert(FW == 4 && (CW == 32 || CW == 64), "fields of four bases, rows of 32 or 64 characters");
+  typedef typename verify_mask<CW>::type mask_t;
   const int L = a.pat_len[pi];
   const int64_t start = p + 1 - L;
   if (start < 0) return false;
-  const uint4 pcv = *reinterpret_cast<const uint4 *>(a.pat_class + (size_t)pi * (CW / 2));
-  const uint32_t pcw[4] = {pcv.x, pcv.y, pcv.z, pcv.w};
-  uint32_t tw[CW / 4];
-  if (start + CW <= a.n) {
-    uint4 t[CW / 16];
+  const uint4 *pcv = reinterpret_cast<const uint4 *>(a.pat_class + (size_t)pi * (CW / 2));
+  mask_t mism = 0, eos = 0;                           // bit i: stream byte i is outside the class of character i / is EOS
 #pragma unroll
-    for (int v = 0; v < CW / 16; ++v) __builtin_memcpy(&t[v], a.text + start + 16 * v, 16);
+  for (int g = 0; g < CW / 32; ++g) {
+    const uint4 pc = pcv[g];
+    const uint32_t pcw[4] = {pc.x, pc.y, pc.z, pc.w};
+    const int64_t from = start + 32 * g;
+    uint32_t tw[8];
+    if (from + 32 <= a.n) {
+      uint4 t[2];
 #pragma unroll
-    for (int v = 0; v < CW / 16; ++v) { tw[4 * v] = t[v].x; tw[4 * v + 1] = t[v].y; tw[4 * v + 2] = t[v].z; tw[4 * v + 3] = t[v].w; }
-  } else {                                            // the last bytes of the stream
+      for (int v = 0; v < 2; ++v) __builtin_memcpy(&t[v], a.text + from + 16 * v, 16);
 #pragma unroll
-    for (int d = 0; d < CW / 4; ++d) {
-      tw[d] = 0;
-      for (int b = 0; b < 4; ++b) { const int64_t q = start + 4 * d + b; if (q < a.n) tw[d] |= (uint32_t)a.text[q] << (8 * b); }
+      for (int v = 0; v < 2; ++v) { tw[4 * v] = t[v].x; tw[4 * v + 1] = t[v].y; tw[4 * v + 2] = t[v].z; tw[4 * v + 3] = t[v].w; }
+    } else {                                          // the last bytes of the stream
+#pragma unroll
+      for (int d = 0; d < 8; ++d) {
+        tw[d] = 0;
+        for (int b = 0; b < 4; ++b) { const int64_t q = from + 4 * d + b; if (q < a.n) tw[d] |= (uint32_t)a.text[q] << (8 * b); }
+      }
     }
-  }
-  uint32_t mism = 0, eos = 0;                         // bit i: stream byte i is outside the class of character i / is EOS
+    uint32_t m32 = 0, e32 = 0;
 #pragma unroll
-  for (int i = 0; i < CW; ++i) {
-    const uint32_t ch = (tw[i / 4] >> (8 * (i & 3))) & 0xffu;
-    uint32_t code = ch;                               // A,C,G,T = 0..3; anything else >= 4
-    if (a.ascii) code = ch == 'A' ? 0u : ch == 'C' ? 1u : ch == 'G' ? 2u : ch == 'T' ? 3u : 4u;
-    const uint32_t cls = (pcw[i / 8] >> (4 * (i & 7))) & 15u;
-    if (code >= 4u || !((cls >> code) & 1u)) mism |= 1u << i;
-    if ((int)ch == a.eos_code) eos |= 1u << i;
+    for (int i = 0; i < 32; ++i) {
+      const uint32_t ch = (tw[i / 4] >> (8 * (i & 3))) & 0xffu;
+      uint32_t code = ch;                             // A,C,G,T = 0..3; anything else >= 4
+      if (a.ascii) code = ch == 'A' ? 0u : ch == 'C' ? 1u : ch == 'G' ? 2u : ch == 'T' ? 3u : 4u;
+      const uint32_t cls = (pcw[i / 8] >> (4 * (i & 7))) & 15u;
+      if (code >= 4u || !((cls >> code) & 1u)) m32 |= 1u << i;
+      if ((int)ch == a.eos_code) e32 |= 1u << i;
+    }
+    mism |= (mask_t)m32 << (32 * g);
+    eos |= (mask_t)e32 << (32 * g);
   }
-  const uint32_t lenmask = L >= CW ? ~0u : ((1u << L) - 1u);
+  const mask_t lenmask = L >= CW ? ~(mask_t)0 : (((mask_t)1 << L) - 1u);   // (a shift by the mask's width is undefined)
   mism &= lenmask;
   if (a.eos_code >= 0 && (eos & lenmask)) return false;   // EOS inside the window: never a candidate
-  int ham = pop32(mism);
+  int ham = pop_mask(mism);
   if (ham > a.k) return false;
-  if (mism & a.pat_zone[pi]) {                        // a substitution inside an exact zone (pair_verify)
+  mask_t zone = a.pat_zone[(size_t)pi * (CW / 32)];
+  if (CW == 64) zone |= (mask_t)((uint64_t)a.pat_zone[(size_t)pi * (CW / 32) + (CW / 32 - 1)] << (CW - 32));
+  if (mism & zone) {                                  // a substitution inside an exact zone (pair_verify)
     if (a.viol_level <= 0) return false;
     ham = a.viol_level;
   }
   if (a.k == 0) {
     if (combo != (int)a.pat_reg[pi]) return false;
   } else {
-    const uint32_t tail = mism >> (L - 4 * FW);       // the bases the plan looks at
+    const uint32_t tail = (uint32_t)(mism >> (L - 4 * FW));   // the bases the plan looks at (shifted in the mask's width: L - 16 reaches 48)
     uint32_t dirty = 0;
 #pragma unroll
     for (int j = 0; j < 4; ++j) if ((tail >> (FW * j)) & ((1u << FW) - 1u)) dirty |= 1u << j;
@@ -280,8 +297,8 @@ PM_VFN bool wild_verify(const Args &a, int combo, int64_t p, uint32_t pi, pm_hit
       if (!((dirty >> a.fa[c]) & 1u) && !((dirty >> a.fb[c]) & 1u)) first = c;
     if (first != combo) return false;
   }
-  const int half = L / 2;
-  const bool left_clean = (mism & ((1u << half) - 1u)) == 0, right_clean = (mism >> half) == 0;
+  const int half = L / 2;                             // (<= 32 < the width of a 64-bit mask; <= 16 at CW = 32)
+  const bool left_clean = (mism & (((mask_t)1 << half) - 1u)) == 0, right_clean = (mism >> half) == 0;
   hh->end = p + 1; hh->pid = a.pat_id[pi]; hh->k = (uint8_t)ham;
   hh->aux[0] = (uint8_t)((left_clean ? 1 : 0) | (right_clean ? 2 : 0)); hh->aux[1] = hh->aux[2] = 0;
   return true;

@@ -1,5 +1,5 @@
-// pm_wild_tables.h -- the key index of the wild class (pm_wild_sub_scan, pm_short.hip; DESIGN.md 4.13): primers of 16..32
-// characters with IUPAC ambiguity letters, compared by CLASS.  The geometry is pm_short_sub_scan's -- a primer's last 16
+// pm_wild_tables.h -- the key index of the wild class (pm_wild_sub_scan, pm_short.hip; DESIGN.md 4.13, 4.14): primers of 16..32
+// -- 16..64 with PM_WILD_LONG -- characters with IUPAC ambiguity letters, compared by CLASS.  The geometry is pm_short_sub_scan's -- a primer's last 16
 // characters as four fields of four, the field pairs of sub_fa / sub_fb (pm_verify.h) -- but a key multiplies over the
 // ambiguity letters of its own two fields only, and a run entry carries the classes of the eight bases outside the key.
 // Plain C++: tests/test_wild_class_host.py compiles it with the host compiler and checks it against a restatement.
@@ -42,10 +42,12 @@ inline size_t wild_pair_keys(const std::string &s, int a, int b) {
   for (int f : {a, b}) for (int i = 0; i < 4; ++i) n *= (size_t)wild_pop4(wild_class_of((unsigned char)s[L - 16 + 4 * f + i]));
   return n;
 }
-// A primer the class can hold at all (its number of concrete variants is the routing's business): 16..32 characters, a
+// A primer the class can hold at all (its number of concrete variants is the routing's business): 16..maxL characters, a
 // base accepted at every character, at most WILD_MAX_PAIR_KEYS keys in every field pair of the plan (k = 0: the plan of k = 1).
-inline bool wild_primer_fits(const std::string &s, int k) {
-  if (s.size() < 16 || s.size() > 32) return false;
+// maxL: the largest length the caller admits -- 32, or 64 where the class may be verified by wild_verify<4, 64>.
+// The keys come from the last 16 characters whatever the length.
+inline bool wild_primer_fits(const std::string &s, int k, size_t maxL = 32) {
+  if (s.size() < 16 || s.size() > maxL || maxL > 64) return false;
   for (unsigned char ch : s) if (!wild_class_of(ch)) return false;
   const int kk = k == 2 ? 2 : 1;
   for (int c = 0; c < sub_ncombos(kk); ++c) if (wild_pair_keys(s, sub_fa(kk, c), sub_fb(kk, c)) > WILD_MAX_PAIR_KEYS) return false;
@@ -75,7 +77,8 @@ struct WildIndex {
   std::vector<uint64_t> runs;      // by pair and key: class index of the primer | class word << 32
   std::vector<size_t> entries;     // [field pair] run entries
   std::vector<uint8_t> reg;        // per primer: the pair it is entered under at k = 0 (0xff: under every pair)
-  std::vector<uint8_t> pat_class;  // per primer 16 bytes: one nibble per character (A,C,G,T = bits 0..3), character i in byte i / 2, even i low
+  std::vector<uint8_t> pat_class;  // per primer row_bytes bytes: one nibble per character (A,C,G,T = bits 0..3), character i in byte i / 2, even i low
+  size_t row_bytes = 16;           // 16, or 32 when the class holds a primer of 33..64 characters (every row of the class is then wide)
 };
 
 // The class word of a primer for field pair (a, b): four bits per base -- the set of stream codes the base accepts --
@@ -105,8 +108,10 @@ inline void wild_pair_key_list(const std::string &s, int a, int b, bool ascii, s
   }
 }
 
-// Build the index of primers that all pass wild_primer_fits(s, k).  Returns "" or why the class is refused as a whole
-// (some field pair's run entries exceed WILD_MAX_ENTRIES): *out is then unspecified.
+// Build the index of primers that all pass wild_primer_fits(s, k, 64).  Returns "" or why the class is refused as a whole
+// (some field pair's run entries exceed WILD_MAX_ENTRIES): *out is then unspecified.  The key index -- bitmaps, rows, run
+// entries, reg -- does not depend on the primers' lengths; the rows of pat_class are as wide as the class's longest primer
+// asks (row_bytes): a class without a primer of 33..64 characters gets the tables it always had.
 inline std::string wild_build_index(const std::vector<std::string> &pats, int k, bool ascii, WildIndex *out) {
   WildIndex &x = *out;
   x = WildIndex();
@@ -116,11 +121,14 @@ inline std::string wild_build_index(const std::vector<std::string> &pats, int k,
   for (int c = 0; c < x.ncombos; ++c) { x.fa[c] = sub_fa(kk, c); x.fb[c] = sub_fb(kk, c); }
   const size_t m = pats.size();
   x.reg.assign(m, 0xff);
-  x.pat_class.assign(m * 16, 0);
   for (size_t j = 0; j < m; ++j) {
-    if (!wild_primer_fits(pats[j], k)) return "primer the wild class does not take";
+    if (!wild_primer_fits(pats[j], k, 64)) return "primer the wild class does not take";
+    if (pats[j].size() > 32) x.row_bytes = 32;
+  }
+  x.pat_class.assign(m * x.row_bytes, 0);
+  for (size_t j = 0; j < m; ++j) {
     if (k == 0) x.reg[j] = (uint8_t)wild_registered_pair(pats[j]);
-    for (size_t i = 0; i < pats[j].size(); ++i) x.pat_class[j * 16 + i / 2] |= (uint8_t)(wild_class_of((unsigned char)pats[j][i]) << (4 * (i & 1)));
+    for (size_t i = 0; i < pats[j].size(); ++i) x.pat_class[j * x.row_bytes + i / 2] |= (uint8_t)(wild_class_of((unsigned char)pats[j][i]) << (4 * (i & 1)));
   }
   x.bitmap.assign((size_t)x.ncombos * SHORT_BM_WORDS, 0);
   x.rows.assign((size_t)x.ncombos * SHORT_ROWS, 0);

@@ -64,13 +64,14 @@ GpuPatternMatch::GpuPatternMatch(int kernel, unsigned int k, char eos, bool wc, 
   cfg.semantics = semantics; cfg.kernel = kernel; cfg.k = (int32_t)k; cfg.indels = indels ? 1 : 0;
   cfg.wildcards = wc ? 1 : 0; cfg.text_n = tn ? 1 : 0; cfg.eos = (unsigned char)eos;
   cfg.device = group_ ? group_->device() : device;
-  // PM_GPU_LONG = 1 .. 127, the bits of pm_config.long_patterns (default 0): 1 = -K 1 / -K 2 primers of 33..64 nt may run
+  // PM_GPU_LONG = 1 .. 255, the bits of pm_config.long_patterns (default 0): 1 = -K 1 / -K 2 primers of 33..64 nt may run
   // on the pair plan, 2 = at k = 0 they may run on the seed plan, 4 = under -k 1 / -k 2 they may run on the edit plan,
   // 8 = under exact_halves -k 1 / -k 2 they may run on the halves plan, 16 = with indels their hits are re-aligned on the device
   // (counts, the pairing stage; no scan changes), 32 = under -w primers of 16..32 nt with more than 16 concrete variants may
   // run on pm_wild_sub_scan (k = 0, -K 1 / -K 2), 64 = under -k 1 / -k 2 the edit plan's first stage may run on the pair geometry
-  // for every tile, at -k 1 and under exact_bases; sums combine them; any other value is 0
-  if (const char *lp = getenv("PM_GPU_LONG")) { const int v = atoi(lp); cfg.long_patterns = v >= 1 && v <= 127 ? v : 0; }
+  // for every tile, at -k 1 and under exact_bases, 128 = together with 32, such -w primers of 33..64 nt may join that class;
+  // sums combine them; any other value is 0
+  if (const char *lp = getenv("PM_GPU_LONG")) { const int v = atoi(lp); cfg.long_patterns = v >= 1 && v <= 255 ? v : 0; }
   device_ = cfg.device;
   k_ = k;
   if (pm_create(&cfg, &h_) != PM_OK) { fprintf(stderr, "Fatal error: %s\n", pm_last_error(nullptr)); exit(1); }

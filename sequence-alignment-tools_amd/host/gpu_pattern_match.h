@@ -106,9 +106,9 @@ class GpuPatternMatch {
   // group: the ranks of a position-sharded run (pm_ranks.h), or null / single.  With N ranks every
   // rank scans its own shard of the stream on its own GPU and rank 0's find_patterns hands out the
   // hits of the WHOLE stream; the other ranks' find_patterns returns nothing.
-  // Environment: PM_GPU_LONG=1 .. 127 sets pm_config.long_patterns, a bit set (1: -K 1 / -K 2 primers of 33..64 nt on the
+  // Environment: PM_GPU_LONG=1 .. 255 sets pm_config.long_patterns, a bit set (1: -K 1 / -K 2 primers of 33..64 nt on the
   // pair plan; 2: k = 0 primers of 33..64 nt on the seed plan; 4: -k 1 / -k 2 primers of 33..64 nt on the edit plan;
-  // 8: exact_halves -k 1 / -k 2 primers of 33..64 nt on the halves plan; 16: with indels, hits of primers of 33..64 nt re-aligned on the device; 32: -w primers of 16..32 nt with more than 16 concrete variants on pm_wild_sub_scan; 64: the -k 1 / -k 2 edit plan's first stage on the pair geometry for every tile, at -k 1 and under exact_bases; sums combine them; default and any other value: 0), read where PM_GPU_PACKED and PM_GPU_WINDOW are: by this class, for every program built on it.
+  // 8: exact_halves -k 1 / -k 2 primers of 33..64 nt on the halves plan; 16: with indels, hits of primers of 33..64 nt re-aligned on the device; 32: -w primers of 16..32 nt with more than 16 concrete variants on pm_wild_sub_scan; 64: the -k 1 / -k 2 edit plan's first stage on the pair geometry for every tile, at -k 1 and under exact_bases; 128: together with 32, such -w primers of 33..64 nt on that class as well; sums combine them; default and any other value: 0), read where PM_GPU_PACKED and PM_GPU_WINDOW are: by this class, for every program built on it.
   GpuPatternMatch(int kernel, unsigned int k, char eos = '\n', bool wc = false, bool tn = false,
                   bool indels = true, bool dna_mut = false, int semantics = PM_SEM_AUTO, int device = 0,
                   RankGroup *group = nullptr);

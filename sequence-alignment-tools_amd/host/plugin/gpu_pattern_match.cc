@@ -32,13 +32,13 @@ gpu_pattern_match::gpu_pattern_match(int kernel, unsigned int k, char eos, bool 
   cfg.text_n = tn ? 1 : 0;
   cfg.eos = (unsigned char)eos;
   if (const char *dev = getenv("PM_GPU_DEVICE")) cfg.device = atoi(dev);
-  // PM_GPU_LONG = 1 .. 127, the bits of pm_config.long_patterns (default 0): 1 = -K 1 / -K 2 primers of 33..64 nt may run
+  // PM_GPU_LONG = 1 .. 255, the bits of pm_config.long_patterns (default 0): 1 = -K 1 / -K 2 primers of 33..64 nt may run
   // on the pair plan, 2 = at k = 0 they may run on the seed plan, 4 = under -k 1 / -k 2 they may run on the edit plan,
   // 8 = under exact_halves -k 1 / -k 2 they may run on the halves plan, 16 = with indels their hits are re-aligned on the device
   // (counts, the pairing stage; no scan changes), 32 = under -w primers of 16..32 nt with more than 16 concrete variants may run on
   // pm_wild_sub_scan, 64 = under -k 1 / -k 2 the edit plan's first stage may run on the pair geometry for every tile, at -k 1 and
-  // under exact_bases; sums combine them; any other value is 0
-  if (const char *lp = getenv("PM_GPU_LONG")) { const int v = atoi(lp); cfg.long_patterns = v >= 1 && v <= 127 ? v : 0; }
+  // under exact_bases, 128 = together with 32, such -w primers of 33..64 nt may join that class; sums combine them; any other value is 0
+  if (const char *lp = getenv("PM_GPU_LONG")) { const int v = atoi(lp); cfg.long_patterns = v >= 1 && v <= 255 ? v : 0; }
   device_ = cfg.device;
   if (pm_create(&cfg, &h_) != PM_OK) {
     std::string msg = std::string("Fatal error: ") + pm_last_error(0);

@@ -228,18 +228,21 @@ class PatternMatch:
     edit_pair=True (bit 6) lets the edit plan's first stage run on the pair geometry (pm_pair_edit_scan + pm_pair_edit_resolve)
     wherever its tables can be built, not only at -k 2 on one pattern tile: every tile of a larger list at -k 2, -k 1 under
     filter_bitvec / bare shift_and_inexact (two tests per window) and exact_bases -k 1 / -k 2.  The hits do not change.
+    wild_long=True (bit 7) acts only together with wild_class: -w primers of 33..64 characters with more than 16 concrete
+    variants join that class under the same rules (their keys are their last 16 characters'); a class that holds one is
+    verified by pm_wild_sub_verify_wide on rows of 64 characters.  Alone it changes nothing.
     """
 
     def __init__(self, k=0, indels=True, eos="\n", semantics=SEM_AUTO, kernel=KERNEL_AUTO, device=0,
                  wildcards=False, text_n=False, long_patterns=False, long_exact=False, long_edits=False,
-                 long_halves=False, long_align=False, wild_class=False, edit_pair=False):
+                 long_halves=False, long_align=False, wild_class=False, edit_pair=False, wild_long=False):
         self._L = load_library()
         cfg = _Config()
         cfg.abi_version, cfg.semantics, cfg.kernel, cfg.k = 1, semantics, kernel, k
         cfg.indels, cfg.wildcards, cfg.text_n = int(bool(indels)), int(bool(wildcards)), int(bool(text_n))
         cfg.eos = ord(eos) if isinstance(eos, str) else int(eos)
         cfg.device = device
-        cfg.long_patterns = int(bool(long_patterns)) | (2 if long_exact else 0) | (4 if long_edits else 0) | (8 if long_halves else 0) | (16 if long_align else 0) | (32 if wild_class else 0) | (64 if edit_pair else 0)
+        cfg.long_patterns = int(bool(long_patterns)) | (2 if long_exact else 0) | (4 if long_edits else 0) | (8 if long_halves else 0) | (16 if long_align else 0) | (32 if wild_class else 0) | (64 if edit_pair else 0) | (128 if wild_long else 0)
         self.long_patterns_bits = int(cfg.long_patterns)           # pm_config.long_patterns as handed to pm_create
         self._h = C.c_void_p()
         rc = self._L.pm_create(C.byref(cfg), C.byref(self._h))
