@@ -12,9 +12,14 @@ second) -- the open-ended form of tests/test_gpu_adversarial.py, which keeps 600
 the cases are those of tests/adversarial_classes.py (lists that fill the main class, wide tiles, the 16..19 character
 classes, the degenerate -w class and the residue at once, the permission bits of pm_config.long_patterns set): the
 open-ended form of tests/test_gpu_adversarial_classes.py, whose 400 fixed seeds are the first this form draws (first_seed
-900 unless given).  It ends at the first difference and at the first error and tries nothing twice.
+900 unless given).  It ends at the first difference and at the first error and tries nothing twice.  With --classes,
+--door windowed|packed|counts|pcr sends the cases through another way into the library -- pm_init_windowed, pm_init_packed
+(resident, and windowed on every second case), pm_count_scan / pm_counts (M in 0, 1, 3; whole, in three ranges and in
+ranges of 193 positions) or the pairing stage in three rounds -- with the helpers and the expectations of
+tests/test_gpu_adversarial_classes_streams.py and tests/test_gpu_adversarial_classes_stages.py, whose fixed seeds are again
+the first drawn.
 
-    python scripts/fuzz_families.py [seconds] [first_seed] [--oracle [--classes] [--dense-bound RECORDS | --edge-cuts]]
+    python scripts/fuzz_families.py [seconds] [first_seed] [--oracle [--classes [--door DOOR]] [--dense-bound RECORDS | --edge-cuts]]
 
 Prints one line per case and a summary; exit status 1 on the first difference."""
 import os
@@ -81,6 +86,71 @@ def hits_of(pats, k, indels, kernel, sem, dev, cap, mode=0, rng=None, table=TABL
     finally:
         pm.close()
     return sort3(h["end"], h["pid"], h["k"]) + (sel, desc)
+
+
+def door_case(c, want):
+    """one class case through DOOR; returns (what was compared, a note) or None where the door does not take the case;
+    raises AssertionError on a difference"""
+    if DOOR in ("windowed", "packed"):
+        if DOOR == "packed" and c["table"] is None:
+            return None
+        window, chunk = AC.window_of(c)
+        if DOOR == "packed" and c["seed"] % 2 == 0:
+            window, chunk = None, 1 << 26
+        got, res, desc = AC.stream_hits(c, window=window, packed=DOOR == "packed", chunk=chunk)
+        c["kernel_desc"] = desc
+        assert got == want, "hits differ: only GPU %s, only oracle %s" % (sorted(set(got) - set(want))[:6], sorted(set(want) - set(got))[:6])
+        assert res["window"] == (window or 0) and (window is None or c["n"] <= 2 * window or res["loads"] > 1), res
+        return len(got), "window %s loads %d" % (window, res["loads"])
+    if DOOR == "counts":
+        from test_gpu_adversarial_classes_stages import check_counts
+        pm = AC.handle(c)
+        try:
+            c["kernel_desc"] = pm.describe()
+            n = c["n"]
+            for M in (0, 1, 3):
+                check_counts(c, want, M, pm.count_all(max_count=M), "count_all")
+                check_counts(c, want, M, AC.count_walk(pm, c, (n // 3, 2 * (n // 3), n), M), "three ranges")
+                check_counts(c, want, M, AC.count_walk(pm, c, list(range(193, n, 193)) + [n], M), "ranges of 193")
+            info = pm.counts()[2]
+        finally:
+            pm.close()
+        return len(want), "re-aligned device/host %d/%d" % (info["aligned_device"], info["aligned_host"])
+    if not AC.pcr_eligible(c) or len(want) > AC.PCR_DENSE:
+        return None
+    c["kernel_desc"] = ""
+    f = AC.pcr_run(c, want)
+    return len(want), "candidates %d amplicons %d early %d late %d" % (f["candidates"], f["survivors"], f["early"], f["late"])
+
+
+def main_door(budget, seed):
+    """class cases through DOOR, library against oracle and rules"""
+    t_end = time.time() + budget
+    cases = passed_by = bad = skipped = 0
+    while time.time() < t_end:
+        c = AC.class_case(seed)
+        want = A.oracle_hits(c)
+        try:
+            r = door_case(c, want)
+        except sat_amd.PmError as err:
+            if want is None and err.code in (-6, -2):
+                skipped += 1
+                seed += 1
+                continue
+            raise
+        except AssertionError as err:
+            print("%s: DIFFERENT through %s: %s" % (AC.describe(c), DOOR, str(err)[:600]), flush=True)
+            bad += 1
+            break
+        if r is None:
+            passed_by += 1
+        else:
+            assert want is not None, "the oracle rejects what the library accepts: " + AC.describe(c)
+            cases += 1
+            print("%s: %s %d hits ok, %s  %s" % (AC.describe(c), DOOR, r[0], r[1], c["kernel_desc"][:50]), flush=True)
+        seed += 1
+    print("door %s: cases %d, not of the door's form %d, rejected by reference and library alike %d, failures %d, next seed %d" % (DOOR, cases, passed_by, skipped, bad, seed))
+    sys.exit(1 if bad else 0)
 
 
 def main_oracle(budget, seed):
@@ -151,6 +221,7 @@ def main_oracle(budget, seed):
 DENSE_BOUND = 0
 EDGE_CUTS = False
 CLASSES = False
+DOOR = None
 # describe() phrases of the opt-in routes (csrc/pm_api.cpp pm_describe)
 ROUTE_PHRASES = {"pair_wide": "pm_pair_verify_wide", "exact_wide": "(wide rows, wide tiles=", "edits_wide": "pm_edits_verify_wide", "halves_wide": "pm_half_verify_wide",
                  "wild": "pm_wild_sub_scan", "short_edit": "pm_short_edit_scan", "short_sub": "pm_short_sub_scan", "edit_pair": "pm_pair_edit_scan",
@@ -159,7 +230,7 @@ CUT = [0]
 
 
 def main():
-    global DENSE_BOUND, EDGE_CUTS, CLASSES
+    global DENSE_BOUND, EDGE_CUTS, CLASSES, DOOR
     EDGE_CUTS = "--edge-cuts" in sys.argv[1:]
     CLASSES = "--classes" in sys.argv[1:]
     argv = [a for a in sys.argv[1:] if a not in ("--oracle", "--edge-cuts", "--classes")]
@@ -167,8 +238,16 @@ def main():
         i = argv.index("--dense-bound")
         DENSE_BOUND = int(argv[i + 1])
         del argv[i:i + 2]
+    if "--door" in argv:
+        i = argv.index("--door")
+        DOOR = argv[i + 1]
+        del argv[i:i + 2]
+        if DOOR not in ("windowed", "packed", "counts", "pcr") or not CLASSES or "--oracle" not in sys.argv[1:]:
+            sys.exit("--door windowed|packed|counts|pcr goes with --oracle --classes")
     budget = float(argv[0]) if len(argv) > 0 else 300.0
     seed = int(argv[1]) if len(argv) > 1 else (900 if CLASSES else 1000)
+    if DOOR:
+        return main_door(budget, seed)
     if "--oracle" in sys.argv[1:]:
         return main_oracle(budget, seed)
     t_end = time.time() + budget

@@ -3313,7 +3313,10 @@ static int finalize_device_impl(pm_handle *h, const void *d_cands, size_t n, int
 // (pattern_alignment.cc:29-43) for k == 0, else editdist_alignment(key, key, k, eos, wc, tn,
 // indels, dm, esb, eeb, yesno=false) with its traceback; editdist == INT32_MAX is the CLI's
 // "Bogus hit" (constraint violation).
-static int align_hits_impl(pm_handle *h, const pm_hit *hits, size_t n, pm_alignment *out, char *ops, char *text, size_t stride);
+// none_empty: a record whose DP gives up at a row (no alignment: start = 0, editdist = INT32_MAX, value = 0) gets two empty
+// strings, as pm_align_hits_kernel writes them -- the form pm_align_hits_device needs for the records it hands to the host;
+// without it such a record cannot be asked for strings and the call fails (pm_align_hits_text).
+static int align_hits_impl(pm_handle *h, const pm_hit *hits, size_t n, pm_alignment *out, char *ops, char *text, size_t stride, bool none_empty = false);
 
 extern "C" int pm_align_hits(pm_handle *h, const pm_hit *hits, size_t n, pm_alignment *out) {
   return align_hits_impl(h, hits, n, out, nullptr, nullptr, 0);
@@ -3324,7 +3327,7 @@ extern "C" int pm_align_hits_text(pm_handle *h, const pm_hit *hits, size_t n, pm
   return align_hits_impl(h, hits, n, out, ops, text, stride);
 }
 
-static int align_hits_impl(pm_handle *h, const pm_hit *hits, size_t n, pm_alignment *out, char *ops, char *text, size_t stride) {
+static int align_hits_impl(pm_handle *h, const pm_hit *hits, size_t n, pm_alignment *out, char *ops, char *text, size_t stride, bool none_empty) {
   if (!h || !h->inited || (!hits && n) || (!out && n)) return fail(h, PM_E_INVALID, "pm_align_hits: bad arguments");
   const bool wc_exact = h->cfg.wildcards && h->cfg.k == 0;      // exact_wc_alignment (pattern_alignment.cc:70-93) reads the text
   HIP_TRY(h, hipSetDevice(h->cfg.device));
@@ -3382,7 +3385,9 @@ static int align_hits_impl(pm_handle *h, const pm_hit *hits, size_t n, pm_alignm
     AlignResult r = editdist_align(h->winbuf.data() + wins[i].off, wins[i].start, hits[i].end, hits[i].end,
                                    pp[i]->s.data(), L, pp[i]->esb, pp[i]->eeb, prm, scratch, ops ? &opstr : nullptr);
     out[i].start = r.start; out[i].end = r.end; out[i].editdist = r.editdist; out[i].value = r.value;
-    if (ops) {
+    if (ops && none_empty && r.editdist == INT32_MAX && r.start == 0 && r.value == 0) {
+      ops[i * stride] = 0; text[i * stride] = 0;
+    } else if (ops) {
       const int64_t tl = r.end - r.start;                              // matching text (pattern_alignment.cc:603-606)
       if (opstr.size() + 1 > stride || tl < 0 || (size_t)tl + 1 > stride) return false;
       memcpy(ops + i * stride, opstr.data(), opstr.size()); ops[i * stride + opstr.size()] = 0;
@@ -3503,7 +3508,7 @@ extern "C" int pm_align_hits_device(pm_handle *h, const void *d_hits, size_t n, 
     std::vector<pm_alignment> al(n);
     std::vector<char> ho, ht;
     if (strings) { ho.assign(n * stride, 0); ht.assign(n * stride, 0); }
-    { int rc = align_hits_impl(h, all.data(), n, al.data(), strings ? ho.data() : nullptr, strings ? ht.data() : nullptr, stride); if (rc) return rc; }
+    { int rc = align_hits_impl(h, all.data(), n, al.data(), strings ? ho.data() : nullptr, strings ? ht.data() : nullptr, stride, true); if (rc) return rc; }
     h->cinfo.aligned_host += n;
     HIP_TRY(h, hipMemcpy(d_out, al.data(), n * sizeof(pm_alignment), hipMemcpyHostToDevice));
     if (strings) {
@@ -3550,7 +3555,7 @@ extern "C" int pm_align_hits_device(pm_handle *h, const void *d_hits, size_t n, 
     if (strings) { ho.assign(m * stride, 0); ht.assign(m * stride, 0); }
     e = hipMemcpy(hh.data(), d_rec, m * sizeof(pm_hit), hipMemcpyDeviceToHost);
     h->cinfo.record_bytes_to_host += m * sizeof(pm_hit);
-    if (e == hipSuccess) rc = align_hits_impl(h, hh.data(), m, al.data(), strings ? ho.data() : nullptr, strings ? ht.data() : nullptr, stride);
+    if (e == hipSuccess) rc = align_hits_impl(h, hh.data(), m, al.data(), strings ? ho.data() : nullptr, strings ? ht.data() : nullptr, stride, true);
     if (e == hipSuccess && rc == PM_OK) {
       h->cinfo.aligned_host += m;
       const size_t ab = m * sizeof(pm_alignment), sb = strings ? m * stride : 0;
